@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """bench.py — Gauss-Newton iterations/s of the sliding-window photometric bundle adjustment on MI355X.
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  The headline is timed over ONE
+region of exactly K steps; "ms_per_step" is that region's milliseconds / K.  `--dump-outputs DIR` writes what the last timed step
+left in rank 0's window (energy, poses, affine brightness, inverse depths) to DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
   step      = one Gauss-Newton iteration of the LM loop = linearize + calculateStep + calculateEnergy + accept
               (levenberg_marquardt_algorithm.hpp:77-128 of the reference)
   workload  = C1 of BASELINE.json (configs[1]): 7-keyframe window, 2000 active points per GPU, 640x480, full clique,
@@ -163,8 +166,8 @@ class Job:
 
 def timed_blocks(job, torch, run_iterations, steps, min_seconds=0.2, max_blocks=200):
     """Times blocks of EXACTLY `steps` GN iterations, each bracketed by barrier + torch.cuda.synchronize() on both sides, max
-    over ranks per block; blocks are repeated until min_seconds of timed work have accumulated (one block at the driver's
-    --steps 20 is 1 ms: a single sample).  Returns (median block seconds, all block seconds)."""
+    over ranks per block; blocks are repeated until min_seconds of timed work have accumulated, at most max_blocks of them (the
+    headline passes max_blocks=1: --steps is the number of timed steps).  Returns (median block seconds, all block seconds)."""
     times = []
     n_blocks = 1
     while len(times) < n_blocks:
@@ -178,6 +181,34 @@ def timed_blocks(job, torch, run_iterations, steps, min_seconds=0.2, max_blocks=
         if len(times) == 1:   # every rank derives the same count from the all-reduced first block
             n_blocks = int(min(max_blocks, max(1, np.ceil(min_seconds / max(dt, 1e-6)))))
     return float(np.median(times)), times
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def window_outputs(g, win, energy):
+    """what a caller of the timed path receives: the energy of the last solve and the window state it left behind (every
+    keyframe's pose and affine brightness, every landmark's inverse depth, frames in window order)"""
+    poses, affine, idepth = [], [], []
+    for f in win.frames:
+        T, ab = g.get_pose(f.frame_id)
+        poses.append(T)
+        affine.append(ab)
+        idepth.append(g.get_landmarks(f.frame_id, with_hpib=False)["idepth"])
+    return {"energy": np.array([energy], dtype=np.float64), "poses": np.array(poses, dtype=np.float64),
+            "affine_brightness": np.array(affine, dtype=np.float64), "idepth": np.concatenate(idepth).astype(np.float64)}
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """writes every array as out_dir/<name>.npy; an array that would push the total past max_bytes is replaced by a fixed, seeded
+    sample of its entries (same indices for the same size, so two runs stay comparable entry for entry)"""
+    os.makedirs(out_dir, exist_ok=True)
+    small = sum(a.nbytes for k, a in arrays.items() if k != "idepth")
+    for name, a in arrays.items():
+        if name == "idepth" and small + a.nbytes > max_bytes:
+            keep = (max_bytes - small) // a.itemsize
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def run_sharded_workload(job, torch, capi, syn, distributed, name, args, dtype, scaling=None, solo_first=False):
@@ -246,6 +277,9 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the large-window roofline, the tracker (C2) timing and the other extras")
     ap.add_argument("--no-group", action="store_true", help="N > 1: skip the single-process window-group measurement (row g-1)")
     ap.add_argument("--group-timeout", type=int, default=150, help="seconds the window-group process may take")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (energy, poses, affine brightness, inverse depths "
+                         "of rank 0's window) to DIR/<name>.npy, for output-for-output comparison of two builds")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -313,19 +347,25 @@ def main():
     job.attach(g, stream)
     g.snapshot()
 
+    last_energy = [None]
+
     def run_iterations(n_target):
         """executes exactly n_target GN iterations as repeated LM loops from the snapshot ({restore; optimize} per solve,
         every solve with its own read-back + stream sync; the loop itself runs inside the library so that the gap between
         two solves is not Python's call overhead); returns iterations done"""
-        done, _ = g.optimize_repeated(n_target)
+        done, last_energy[0] = g.optimize_repeated(n_target)
         if done < n_target:
             raise RuntimeError("LM loop made no progress")
         return done
 
     warmup = max(args.warmup, 7)
     run_iterations(warmup)
-    block_s, block_times = timed_blocks(job, torch, run_iterations, args.steps)
+    # ONE timed region of exactly --steps GN iterations: the count the caller asked for is the count that was timed
+    block_s, block_times = timed_blocks(job, torch, run_iterations, args.steps, max_blocks=1)
     steps_done = args.steps
+    if args.dump_outputs and rank == 0:
+        # the window as the last timed step left it (the profiling passes below run further iterations on it)
+        dump_outputs(args.dump_outputs, window_outputs(g, win, last_energy[0]))
 
     # ---- live per-kernel timing (HIP events on the library's stream) -> roofline of the dominant kernel
     g.set_profiling(True)
@@ -418,14 +458,14 @@ def main():
             "warmup": args.warmup,  # as given; a warm-up shorter than one LM solve (7 iterations) is rounded up to one:
             "warmup_effective": warmup,
             "ms_per_step": ms_per_step,
-            "timed_region_s": block_s,   # the median timed block: `steps` iterations between two barrier + synchronize pairs
+            "timed_region_s": block_s,   # the timed block: `steps` iterations between two barrier + synchronize pairs
             "higher_is_better": True,
             "scaling": scaling,
             "vs_baseline": None,
             "dtype": args.dtype,
             "data": "synthetic",
-            "timing": {"what": f"median over {len(block_times)} timed blocks of {steps_done} GN iterations each (barrier + synchronize on both sides "
-                               "of every block, max over ranks per block); inside a block the LM solves (7 iterations each, the "
+            "timing": {"what": f"one timed block of exactly {steps_done} GN iterations (= --steps; barrier + synchronize on both sides, "
+                               "max over ranks); inside the block the LM solves (7 iterations each, the "
                                "window restored in front of every solve) are enqueued back to back, their results fetched with one copy at the "
                                "end of the block: no host synchronisation between solves",
                        "blocks": len(block_times), "block_ms_min": min(block_times) * 1e3, "block_ms_median": block_s * 1e3,

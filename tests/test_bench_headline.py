@@ -60,3 +60,42 @@ def test_emit_writes_extras_file(tmp_path, monkeypatch, capsys):
     out = capsys.readouterr()
     assert out.out == ""          # stdout belongs to the headline alone; the full result goes to stderr
     assert "tick_sequence" in out.err
+
+
+def test_dump_outputs_writes_npy_within_budget(tmp_path):
+    """--dump-outputs: one float64 .npy per array; an oversized landmark array becomes the same seeded sample every time"""
+    import numpy as np
+    arrays = {"energy": np.array([1.5]), "poses": np.ones((7, 7)), "affine_brightness": np.zeros((7, 2)), "idepth": np.arange(5000.0)}
+    budget = 8 * (1 + 49 + 14 + 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, max_bytes=budget)
+    total = 0
+    for name, a in arrays.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float64 and np.array_equal(x, y)
+        total += x.nbytes
+        if name != "idepth":
+            assert np.array_equal(x, a)
+    idp = np.load(tmp_path / "a" / "idepth.npy")
+    assert idp.size == 1000 and np.all(np.diff(idp) > 0) and total <= budget
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert np.array_equal(np.load(tmp_path / "c" / "idepth.npy"), arrays["idepth"])   # under the default budget: written whole
+
+
+@pytest.mark.gpu
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K GN iterations, ms_per_step is that region / K, and --dump-outputs leaves the C1 window's results"""
+    import subprocess
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "7", "--no-extras",
+                        "--no-cpu", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 10 and d["timing"]["blocks"] == 1
+    assert abs(d["ms_per_step"] * 10 - d["timed_region_s"] * 1e3) <= 1e-9 * d["ms_per_step"] * 10
+    e, T, ab, idp = (np.load(out / f"{n}.npy") for n in ("energy", "poses", "affine_brightness", "idepth"))
+    assert e.shape == (1,) and T.shape == (7, 7) and ab.shape == (7, 2) and idp.shape == (2000,)
+    for a in (e, T, ab, idp):
+        assert a.dtype == np.float64 and np.all(np.isfinite(a))
+    assert e[0] > 0
