@@ -447,7 +447,7 @@ class HipWindow:
         _chk(lib().dsopp_hip_window_set_deterministic(self._h, int(bool(enable))))
 
     def set_lm_mode(self, mode: int):
-        """0 fused device loop (default), 1 host-driven stages, 2 unfused device loop"""
+        """0 fused device loop (default), 1 host-driven stages"""
         _chk(lib().dsopp_hip_window_set_lm_mode(self._h, int(mode)))
 
     def snapshot(self):

@@ -59,7 +59,7 @@ struct HostFrame {
   // sample neighbouring texels, i.e. share 64-byte granules — the sweep is bound by the rate of those requests.  Invariant that keeps the
   // residual tables' prefix meaning ("landmark i has a residual in target t iff i < n_res[t]"): for every entry e of batch_end the device
   // indices [0, e) hold exactly the caller indices [0, e).  A connection that ends INSIDE a batch splits it (splitBatchAt).
-  std::vector<int> to_internal, to_caller;  // caller index <-> device index; empty = identity (order kept: DSOPP_HIP_LANDMARK_ORDER=caller)
+  std::vector<int> to_internal, to_caller;  // caller index <-> device index; empty = identity (no landmarks yet)
   std::vector<int> batch_end;
   DeviceBuffer<int> d_to_internal;          // the caller -> device map on the device (export kernels un-permute there)
   bool permuted() const { return !to_internal.empty(); }
@@ -122,7 +122,7 @@ struct dsopp_hip_window {
   const LmControl *fused_final_ctrl = nullptr;  // control block the enqueued fused loop ends in
   bool async_pending = false;                   // dsopp_hip_window_optimize_async enqueued, _wait not called yet
   bool begun_with_first_estimate = true;        // the solve in progress started with firstEstimate() (stageBegin) rather than fusedBegin
-  int lm_mode = 0;  // 0: fused device loop (3 launches / iteration), 1: host-driven stages, 2: unfused device loop (5 launches)
+  int lm_mode = 0;  // 0: fused device loop (3 launches / iteration), 1: host-driven stages
   double *dHppRaw() const { return d_reduce.ptr; }
   double *dbppRaw() const { return d_reduce.ptr + static_cast<size_t>(K()) * K(); }
   double *dHsc() const { return dbppRaw() + K(); }
@@ -302,12 +302,6 @@ void collectTimings(W &w) {
     w.event_pool.push_back(t.b);
   }
   w.timed.clear();
-}
-
-/** does the device hold the landmarks in its own (spatial) order?  DSOPP_HIP_LANDMARK_ORDER=caller keeps the caller's (A/B aid) */
-bool sortLandmarksInternally() {
-  static const bool keep = std::getenv("DSOPP_HIP_LANDMARK_ORDER") != nullptr && std::string(std::getenv("DSOPP_HIP_LANDMARK_ORDER")) == "caller";
-  return !keep;
 }
 
 /** rows of `row_bytes` bytes gathered from absolute row indices: dst[k] = src[rows[k]] (the rare re-ordering of a landmark batch) */
@@ -640,13 +634,11 @@ void syncTopology(W &w) {
   // (scratch kept per thread: the tables are rebuilt twice per keyframe — pushFrame's fold-in and solve — and 500 vector constructions +
   // their growth were a good part of the 125 us a rebuild cost on the host; DSOPP_HIP_HOST_TIMES)
   static thread_local std::vector<FrameDev> fd;
-  static thread_local std::vector<SweepBlock> sweep;  // (listed on the host only by the XCD-banded launch order experiment)
   static thread_local std::vector<SchurBlock> schur;
   static thread_local std::vector<SweepBlock> pair_tmpl;  // one template per frame pair (slot r * kMaxFrames + t)
   static thread_local std::vector<int> pair_items;       // its entries of kItemsPerBlock items (0: no residuals)
   fd.assign(static_cast<size_t>(kMaxFrames), FrameDev{});
   std::memset(fd.data(), 0, fd.size() * sizeof(FrameDev));
-  sweep.clear();
   schur.clear();
   pair_tmpl.resize(kMaxFrames * kMaxFrames);
   pair_items.assign(kMaxFrames * kMaxFrames, 0);
@@ -654,17 +646,15 @@ void syncTopology(W &w) {
   size_t total_items = 0;
   for (int r = 0; r < F; ++r)
     for (const auto &kv : w.frames[static_cast<size_t>(r)]->residuals) total_items += static_cast<size_t>(kv.second->n);
-  static const int groups_override = std::getenv("DSOPP_HIP_SWEEP_GROUPS") ? std::atoi(std::getenv("DSOPP_HIP_SWEEP_GROUPS")) : 0;  // tuning aid
   // measured: 7 KF / 20k points (120k items) 36.8 / 33.1 / 38.8 us at 2 / 4 / 6 groups; 12 KF / 50k points (550k items) 143 / 125 / 119 us
-  const int groups = groups_override > 0 ? groups_override : (total_items >= 300000 ? 6 : (total_items >= 30000 ? 4 : 1));
+  const int groups = total_items >= 300000 ? 6 : (total_items >= 30000 ? 4 : 1);
   std::vector<int> pair_first(kMaxFrames * kMaxFrames, -1), pair_count(kMaxFrames * kMaxFrames, 0);
   for (int r = 0; r < F; ++r) {
     HostFrame &f = *w.frames[static_cast<size_t>(r)];
     FrameDev &d = fd[static_cast<size_t>(r)];
     const LevelView lv = f.pyramid->view(f.level);
     d.texels = hbm(lv.texels);
-    static const bool no_iplane = std::getenv("DSOPP_HIP_NO_IPLANE") != nullptr;  // tuning aid (A/B of the counter traffic)
-    d.iplane = no_iplane ? nullptr : hbm(f.pyramid->intensityPlane(f.level, st));
+    d.iplane = hbm(f.pyramid->intensityPlane(f.level, st));
     f.pyramid_generation = f.pyramid->generation;
     d.itiles = f.pyramid->itilesX(f.level);
     d.width = lv.width;
@@ -706,9 +696,8 @@ void syncTopology(W &w) {
       d.snap_status[t] = hbm(rt.snap_status.ptr);
       if (d.first_conn < 0) d.first_conn = t;
       // the pair's entries differ in three fields (first landmark, row of the sums, groups of the coarse table): the host states ONE
-      // template per pair, the entries are written from it — on the device (applyAppendsKernel, kind 4), or below for the experiment that
-      // re-orders them.  (Listing them here and sending them whole was 25 us of host time and 350 KB through the queue per rebuild, twice per
-      // keyframe of the tracker.)
+      // template per pair, the entries are written from it on the device (applyAppendsKernel, kind 4).  (Listing them here and sending
+      // them whole was 25 us of host time and 350 KB through the queue per rebuild, twice per keyframe of the tracker.)
       SweepBlock sb;
       std::memset(&sb, 0, sizeof(sb));
       sb.r = r;
@@ -762,17 +751,8 @@ void syncTopology(W &w) {
   // Order of the sweep table: TARGET-major — all pairs that sample the same target image run back to back, so that an XCD's L2 (4 MB,
   // against 9.8 MB of texels per 640 x 480 image) sees the second and later visits of a texel line while it may still hold it: the
   // sweep is bound by the rate at which the fabric serves randomly placed 64-byte requests, and every L2 hit is one
-  // request less.  (Reference-major until round 4: consecutive pairs switched the image.)  DSOPP_HIP_SWEEP_ORDER=rt restores it (A/B).
-  static const bool reference_major = std::getenv("DSOPP_HIP_SWEEP_ORDER") != nullptr && std::string(std::getenv("DSOPP_HIP_SWEEP_ORDER")) == "rt";
-  // entry k of a pair in the sweep table / in the fine table (what applyAppendsKernel's kind 4 writes on the device)
-  const int step = groups > 1 ? groups : 1;
-  auto sweepEntry = [&](const SweepBlock &tmpl, int n_all, int first, int k) {
-    SweepBlock sb = tmpl;
-    sb.offset = k * step * kItemsPerBlock;
-    sb.n_groups = groups > 1 ? std::min(step, n_all - k * step) : 1;
-    sb.partial_row = first + k;
-    return sb;
-  };
+  // request less.  (Reference-major until round 4: consecutive pairs switched the image.)
+  const int step = groups > 1 ? groups : 1;  // groups of items per sweep entry
   struct PairRange {
     size_t pi;
     int first_sweep, n_sweep, first_fine, n_fine;
@@ -780,9 +760,8 @@ void syncTopology(W &w) {
   static thread_local std::vector<PairRange> ranges;
   ranges.clear();
   int total_sweep = 0, total_fine = 0;
-  for (int outer = 0; outer < F; ++outer)
-    for (int inner = 0; inner < F; ++inner) {
-      const int r = reference_major ? outer : inner, t = reference_major ? inner : outer;
+  for (int t = 0; t < F; ++t)
+    for (int r = 0; r < F; ++r) {
       const size_t pi = static_cast<size_t>(r * kMaxFrames + t);
       const int n_all = pair_items[pi];
       if (n_all == 0) continue;
@@ -802,41 +781,6 @@ void syncTopology(W &w) {
       total_sweep += n_sweep;
       total_fine += groups > 1 ? n_all : 0;
     }
-  // EXPERIMENT (DSOPP_HIP_SWEEP_XCD_BANDS=1, off by default): launch order such that XCD x (= blockIdx % 8 under round-robin dispatch)
-  // sweeps the x-th eighth of every pair's landmarks.  With landmarks in a spatial order (rows of the image) an XCD then samples one
-  // band of a target image from all reference frames — 1.2 MB of texels, which its 4 MB L2 holds — instead of the whole image.
-  // Measures how much of the 2.6-fold re-use of texel lines across pairs an L2-aware order could turn into hits.
-  // A measurement aid for the sweep only: the point-status kernels walk the same table, padding entries included, and solve()'s statuses /
-  // inlier counts then differ from the checker's (tests/test_gpu_fullres.py::test_full_solve_parity_at_1280x1024 fails under the switch,
-  // as it did when the experiment was built in round 5).
-  static const bool xcd_bands = std::getenv("DSOPP_HIP_SWEEP_XCD_BANDS") != nullptr && std::atoi(std::getenv("DSOPP_HIP_SWEEP_XCD_BANDS")) != 0;
-  if (xcd_bands)  // (this experiment re-orders the entries: they are listed on the host, as all tables were until round 6)
-    for (const PairRange &pr : ranges)
-      for (int k = 0; k < pr.n_sweep; ++k) sweep.push_back(sweepEntry(pair_tmpl[pr.pi], pair_items[pr.pi], pr.first_sweep, k));
-  if (xcd_bands && !sweep.empty()) {
-    std::vector<std::vector<int>> queue(8);
-    for (size_t b = 0; b < sweep.size(); ++b) {
-      const SweepBlock &sb = sweep[b];
-      const int band = std::min(7, static_cast<int>((static_cast<long long>(sb.offset) * 8) / std::max(1, sb.n_res)));
-      queue[static_cast<size_t>(band)].push_back(static_cast<int>(b));
-    }
-    size_t longest = 0;
-    for (const auto &q : queue) longest = std::max(longest, q.size());
-    std::vector<SweepBlock> launch;
-    int pad_row = static_cast<int>(sweep.size());
-    for (size_t k = 0; k < longest; ++k)
-      for (int x = 0; x < 8; ++x) {
-        if (k < queue[static_cast<size_t>(x)].size()) {
-          launch.push_back(sweep[static_cast<size_t>(queue[static_cast<size_t>(x)][k])]);
-        } else {  // a no-op entry keeps the XCD's turn (zero sums into a row of its own)
-          SweepBlock sb = sweep[0];
-          sb.n_groups = 0;
-          sb.partial_row = pad_row++;
-          launch.push_back(sb);
-        }
-      }
-    sweep.swap(launch);
-  }
   w.d_frames.reserve(kMaxFrames, 0, st);
   uploadStagedBytes(w, w.d_frames.ptr, fd.data(), (kMaxFrames) * sizeof(*w.d_frames.ptr));
   w.h_frames = fd;
@@ -853,18 +797,14 @@ void syncTopology(W &w) {
     op.p[1] = reinterpret_cast<void *>(static_cast<intptr_t>(n_all_for_groups));
     w.append_ops.push_back(op);
   };
-  const size_t n_sweep_entries = xcd_bands ? sweep.size() : static_cast<size_t>(total_sweep);
+  const size_t n_sweep_entries = static_cast<size_t>(total_sweep);
   w.n_sweep_blocks = static_cast<int>(n_sweep_entries);
   w.n_schur_blocks = static_cast<int>(schur.size());
   if (n_sweep_entries > w.d_sweep_table.capacity || (groups > 1 && static_cast<size_t>(total_fine) > w.d_fine_table.capacity))
     flushAppends(w, "flush: sweep tables grow");  // (nothing queued may still point into a table that moves)
   w.d_sweep_table.reserve(std::max<size_t>(1, n_sweep_entries), 0, st);
-  if (xcd_bands) {
-    uploadStagedBytes(w, w.d_sweep_table.ptr, sweep.data(), (sweep.size()) * sizeof(*w.d_sweep_table.ptr));
-  } else {
-    for (const PairRange &pr : ranges)
-      queuePairEntries(w.d_sweep_table.ptr, pair_tmpl[pr.pi], pr.first_sweep, pr.n_sweep, step, groups > 1 ? pair_items[pr.pi] : 0);
-  }
+  for (const PairRange &pr : ranges)
+    queuePairEntries(w.d_sweep_table.ptr, pair_tmpl[pr.pi], pr.first_sweep, pr.n_sweep, step, groups > 1 ? pair_items[pr.pi] : 0);
   if (groups > 1) {
     w.d_fine_table.reserve(std::max<size_t>(1, static_cast<size_t>(total_fine)), 0, st);
     for (const PairRange &pr : ranges) queuePairEntries(w.d_fine_table.ptr, pair_tmpl[pr.pi], pr.first_fine, pr.n_fine, 1, 0);
@@ -1218,11 +1158,10 @@ size_t solveSmemBytes(int K) {
 }
 
 /** K3 */
-void launchAssemble(W &w, double lambda, bool do_solve, bool add_priors, bool store_system, LmControl *ctrl) {
+void launchAssemble(W &w, double lambda, bool do_solve, bool add_priors, bool store_system) {
   ensureDynamicLds(reinterpret_cast<const void *>(assembleSolveKernel), w.sr.device, 150 * 1024);
   SolveArgs a = makeSolveArgs(w);
   a.lambda = lambda;
-  a.ctrl = ctrl;
   a.do_solve = do_solve ? 1 : 0;
   a.add_priors = add_priors ? 1 : 0;
   a.store_system = store_system ? 1 : 0;
@@ -1251,14 +1190,10 @@ void launchTwoStage(W &w, const LmControl *ctrl, int ublk_parity, double lambda,
   const int n_chunks = w.opt.optimize_idepths ? w.n_schur_blocks : 0;
   // two workgroups fit per compute unit (64 landmarks x K doubles of LDS each): twice as many workgroups as the chip has units,
   // each taking its share of the chunks
-  static const int chunks_override = std::getenv("DSOPP_HIP_SCHUR_CHUNKS") ? std::atoi(std::getenv("DSOPP_HIP_SCHUR_CHUNKS")) : 0;  // tuning aid
-  const int chunks_per_wg = chunks_override > 0 ? chunks_override : std::max(1, (n_chunks + 511) / 512);
   // chunks are dealt out evenly over at most 512 workgroups (n / W each, the first n mod W one more): ceil(n / 512) chunks for every
   // workgroup left e.g. 313 workgroups of 2 for 625 chunks — 12 KF / 40 000 points: 38.5 -> 31.7 us, 12 KF / 100 000: 62.9 -> 57.1 us;
-  // no change where the old split was balanced (782 chunks).  DSOPP_HIP_SCHUR_EVEN=0 / DSOPP_HIP_SCHUR_CHUNKS=n: the old split (A/B aids)
-  static const int even_env = std::getenv("DSOPP_HIP_SCHUR_EVEN") ? std::atoi(std::getenv("DSOPP_HIP_SCHUR_EVEN")) : 1;
-  const bool even = even_env != 0 && chunks_override <= 0;
-  const int n_wgs = even ? std::max(1, std::min(512, n_chunks)) : (n_chunks + chunks_per_wg - 1) / chunks_per_wg;
+  // no change where the old split was balanced (782 chunks)
+  const int n_wgs = std::max(1, std::min(512, n_chunks));
   w.d_schur_partials.reserve(std::max<size_t>(1, static_cast<size_t>(n_wgs)) * static_cast<size_t>(twoStagePartialCount(F)), 0, st);
   w.d_pair_out.reserve(static_cast<size_t>(kMaxFrames) * kMaxFrames * kPairOut, 0, st);
   TwoStageArgs a;
@@ -1274,7 +1209,6 @@ void launchTwoStage(W &w, const LmControl *ctrl, int ublk_parity, double lambda,
   a.pair_out = w.d_pair_out.ptr;
   a.F = F;
   a.n_chunks = n_chunks;
-  a.chunks_per_wg = even ? 0 : chunks_per_wg;
   a.n_schur_wgs = n_wgs;
   a.ublk_parity = ublk_parity;
   a.group_sums = group_sums;
@@ -1504,14 +1438,14 @@ void stageLinearize(W &w, bool huber = true, bool for_marg = false, bool add_pri
   if (!w.begun) fail(DSOPP_HIP_ERR_STATE, "call begin first");
   launchSweep(w, true, huber, for_marg);
   launchReduceSchur(w, for_marg, nullptr);
-  launchAssemble(w, 0.0, false, add_priors, /*store_system=*/true, nullptr);
+  launchAssemble(w, 0.0, false, add_priors, /*store_system=*/true);
   w.linearized = true;
 }
 
 void stageStep(W &w, double lambda) {
   if (!w.linearized) fail(DSOPP_HIP_ERR_STATE, "call linearize first");
   // the per-pair blocks and the Schur system are still resident: re-run the (cheap) assembly with the requested lambda
-  launchAssemble(w, lambda, true, true, false, nullptr);
+  launchAssemble(w, lambda, true, true, false);
   w.pair_valid = true;  // the solve kernel rebuilt the pair constants for eps + step
   launchBacksub(w, lambda, nullptr);
   const int K = w.K();
@@ -1548,90 +1482,6 @@ std::pair<double, double> stageAccept(W &w, bool accept) {
   if (!accept) w.pair_valid = false;  // constants were built for eps + step
   return {norms[0], norms[1]};
 }
-
-/**
- * levenberg_marquardt_algorithm::solve (levenberg_marquardt_algorithm.hpp:77-128) with the control flow ON THE DEVICE:
- * the host enqueues max_iterations loop bodies (5 launches each) plus the closing energy evaluation and reads the
- * control block back once; kernels of loop bodies after termination return immediately.
- */
-void lmSolveDevice(W &w, double &energy_out, int &iterations, int &n_valid_out) {
-  hipStream_t st = w.sr.stream;
-  const int F = w.F();
-  LmParams prm;
-  prm.function_tolerance = w.opt.function_tolerance;
-  prm.parameter_tolerance = w.opt.parameter_tolerance;
-  prm.decrease_on_accept = 1.0;  // eigen_photometric_bundle_adjustment.cpp:74-75
-  prm.increase_on_reject = 1.0;
-  prm.lambda0 = 1.0 / w.opt.initial_trust_region_radius;
-  prm.max_iterations = w.opt.max_iterations;
-  prm.min_iterations = 3;
-  prm.force_accept = w.opt.force_accept;
-  prm.use_reduced_scalars = w.allreduce ? 1 : 0;
-  LmControl *ctrl = w.d_ctrl.ptr;
-  // result = problem.calculateEnergy()
-  launchSweep(w, false, true, false);
-  HIP_CHECK(hipMemsetAsync(w.d_scalars.ptr, 0, 8 * sizeof(double), st));
-  if (w.n_schur_blocks) idepthNormKernel<<<w.n_schur_blocks, kSchurThreads, 0, st>>>(w.d_frames.ptr, w.d_schur_table.ptr, w.d_scalars.ptr + 4);
-  if (w.allreduce) {
-    sweepScalarsKernel<<<1, 256, 0, st>>>(w.d_partials.ptr, w.n_sweep_blocks, w.d_scalars.ptr, nullptr);
-    allreduceIfNeeded(w, w.d_scalars.ptr, 5);
-  }
-  {
-    LmInitArgs ia;
-    ia.sa = makeSolveArgs(w);
-    ia.partials = w.d_partials.ptr;
-    ia.scalars = w.d_scalars.ptr;
-    ia.schur_table = w.d_schur_table.ptr;
-    ia.n_sweep_blocks = w.n_sweep_blocks;
-    ia.n_schur_blocks = w.n_schur_blocks;
-    ia.ctrl = ctrl;
-    ia.prm = prm;
-    lmInitKernel<<<1, kSolveThreads, (static_cast<size_t>(w.K()) + 16) * sizeof(double), st>>>(ia);
-  }
-  HIP_CHECK(hipGetLastError());
-  for (int it = 0; it < w.opt.max_iterations; ++it) {
-    LmControl *cin = ctrl + (it & 1), *cout = ctrl + ((it + 1) & 1);
-    launchSweep(w, true, true, false, cin);          // linearize: evaluateJacobians ...
-    launchReduceSchur(w, false, cin);                //            ... pose-pose blocks + Schur complement
-    launchAssemble(w, 0.0, true, true, false, cin);  // calculateStep (lambda from the control block)
-    launchSweep(w, false, true, false, cin, /*backsub=*/true);  // calculateIdepths + calculateEnergy at the candidate state
-    if (w.allreduce) {
-      sweepScalarsKernel<<<1, 256, 0, st>>>(w.d_partials.ptr, w.n_sweep_blocks, w.d_scalars.ptr, cin);
-      allreduceIfNeeded(w, w.d_scalars.ptr, 4);
-    }
-    LmDecideArgs da;
-    da.frames = w.d_frames.ptr;
-    da.st = w.d_state.ptr;
-    da.schur_table = w.d_schur_table.ptr;
-    da.partials = w.d_partials.ptr;
-    da.scalars = w.d_scalars.ptr;
-    da.ctrl_in = cin;
-    da.ctrl_out = cout;
-    da.n_sweep_blocks = w.n_sweep_blocks;
-    da.n_schur_blocks = w.n_schur_blocks;
-    da.F = F;
-    da.prm = prm;
-    timedLaunch(w, DSOPP_HIP_KERNEL_ACCEPT,
-                [&] { lmDecideKernel<<<std::max(1, w.n_schur_blocks), kSchurThreads, 0, st>>>(da); });
-    HIP_CHECK(hipGetLastError());
-  }
-  // closing problem.calculateEnergy() at the final state (candidate statuses / energies of the accepted state); the pair
-  // constants are rebuilt unconditionally: they are stale exactly when the last step was rejected
-  const LmControl *cfin = ctrl + (w.opt.max_iterations & 1);
-  w.pair_valid = false;
-  ensurePairConstants(w);
-  launchSweep(w, false, true, false);
-  // one small read-back into pinned memory (a pageable destination makes the copy synchronous and staged); the host
-  // mirror of the frame states is refreshed lazily, by the first reader (downloadState)
-  if (!w.h_ctrl) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.h_ctrl), sizeof(LmControl), hipHostMallocDefault));
-  HIP_CHECK(hipMemcpyAsync(w.h_ctrl, cfin, sizeof(LmControl), hipMemcpyDeviceToHost, st));
-  w.host_stale = true;
-  w.sr.sync();  // the only host synchronisation of the solve
-  energy_out = w.h_ctrl->energy;
-  iterations = w.h_ctrl->iteration;
-  n_valid_out = w.h_ctrl->n_valid;
-}
-
 
 /** dsopp_hip_window_restore, host half: checks that the snapshot matches the window and puts the host-side mirror back */
 void restoreHostSide(W &w) {
@@ -1699,10 +1549,7 @@ void lmSolveFusedEnqueue(W &w) {
     ia.pair_fej = w.fej() ? 1 : 0;
     w.pair_valid = true;
     ia.sa = makeSolveArgs(w);
-    ia.partials = w.d_partials.ptr;
-    ia.scalars = nullptr;
     ia.schur_table = w.d_schur_table.ptr;
-    ia.n_sweep_blocks = w.n_sweep_blocks;
     ia.n_schur_blocks = w.n_schur_blocks;
     ia.ctrl = ctrl;
     ia.prm = prm;
@@ -2175,7 +2022,7 @@ void foldMarginalized(W &w) {
     HIP_CHECK(hipGetLastError());
   }
   launchReduceSchur(w, true, nullptr);
-  launchAssemble(w, 0.0, false, /*add_priors=*/false, /*store_system=*/true, nullptr);
+  launchAssemble(w, 0.0, false, /*add_priors=*/false, /*store_system=*/true);
   energyReduceKernel<<<1, 256, 0, w.sr.stream>>>(w.d_partials.ptr, w.n_sweep_blocks, w.d_scalars.ptr);
   HIP_CHECK(hipGetLastError());
   allreduceIfNeeded(w, w.d_scalars.ptr, 2);
@@ -2612,34 +2459,18 @@ int dsopp_hip_window_set_landmarks(dsopp_hip_window *w, int32_t frame_id, int32_
     // the new batch in the device's order: by 32 x 32-pixel tile (rows of tiles, then tiles), raster inside a tile — what a grid-cell
     // feature extractor yields, and the order in which the sweep's neighbouring items share texel granules (HostFrame::to_internal)
     const size_t add = static_cast<size_t>(n_total - old);
-    if (add && (f.permuted() || (old == 0 && sortLandmarksInternally()))) {
+    if (add && (f.permuted() || old == 0)) {
       std::vector<int> order(add);
       for (size_t k = 0; k < add; ++k) order[k] = old + static_cast<int>(k);
-      // (experiment switches, defaults = what is described above: DSOPP_HIP_LANDMARK_TILE = log2 of the tile edge, DSOPP_HIP_LANDMARK_INNER =
-      // raster | morton | snake (rows of a tile alternate direction, tile rows alternate direction))
-      static const int tb = std::getenv("DSOPP_HIP_LANDMARK_TILE") ? std::max(2, std::min(8, std::atoi(std::getenv("DSOPP_HIP_LANDMARK_TILE")))) : 5;
-      static const int inner = [] {
-        const char *e = std::getenv("DSOPP_HIP_LANDMARK_INNER");
-        return !e ? 0 : (std::string(e) == "morton" ? 1 : (std::string(e) == "snake" ? 2 : 0));
-      }();
+      constexpr int tb = 5;  // log2 of the tile edge
       auto key = [&](int c) {
         // (a coordinate that is not a number, negative or beyond any image is clamped instead of cast: the cast would be undefined behaviour,
         // and such a landmark is uploaded like any other — the sweep rejects it by its ROI test, as before the internal order existed)
         auto coord = [](double x) -> long long { return !(x >= 0.0) ? 0ll : (x > 65535.0 ? 65535ll : static_cast<long long>(x)); };
         const long long u = coord(uv[2 * c]), v = coord(uv[2 * c + 1]);
         const long long m = (1ll << tb) - 1;
-        long long tu = u >> tb, tv = v >> tb, iu = u & m, iv = v & m, in;
-        if (inner == 1) {
-          in = 0;
-          for (int b = 0; b < tb; ++b) in |= ((iu >> b) & 1) << (2 * b) | ((iv >> b) & 1) << (2 * b + 1);
-        } else {
-          if (inner == 2) {
-            if (tv & 1) tu = 65535 - tu;
-            if (iv & 1) iu = m - iu;
-          }
-          in = (iv << tb) + iu;
-        }
-        return ((tv * 65536 + tu) << (2 * tb)) + in;
+        const long long tu = u >> tb, tv = v >> tb, iu = u & m, iv = v & m;
+        return ((tv * 65536 + tu) << (2 * tb)) + (iv << tb) + iu;
       };
       // (ties — two landmarks on one pixel — are broken by their content, so that the device order, and with it every sum of the
       // deterministic build, depends on the SET of landmarks only, not on the order the caller lists them in)
@@ -2854,16 +2685,13 @@ static void runOptimize(dsopp_hip_window *w, double &e, int &it, int &nv) {
   w->sr.use();
   prepare(*w);
   HIP_CHECK(hipEventRecord(w->ev0, w->sr.stream));
-  if (w->lm_mode == 0)
+  if (w->lm_mode == 0) {
     fusedBegin(*w);
-  else
-    stageBegin(*w);
-  if (w->lm_mode == 1)
-    lmSolve(*w, e, it, nv);
-  else if (w->lm_mode == 2)
-    lmSolveDevice(*w, e, it, nv);
-  else
     lmSolveFused(*w, e, it, nv);
+  } else {
+    stageBegin(*w);
+    lmSolve(*w, e, it, nv);
+  }
   HIP_CHECK(hipEventRecord(w->ev1, w->sr.stream));
   w->solve_events_pending = true;  // the elapsed time is read when somebody asks for it (dsopp_hip_window_last_solve_ms)
   collectTimings(*w);
@@ -2974,8 +2802,7 @@ int dsopp_hip_window_solve(dsopp_hip_window *w, double *energy, int32_t *iterati
     double e = 0;
     int it = 0, nv = 0;
     const bool sharded = w->allreduce && w->world > 1;
-    static const bool serial_solve = std::getenv("DSOPP_HIP_SERIAL_SOLVE") != nullptr;  // tuning aid: the step-by-step flow
-    if (w->lm_mode == 0 && !sharded && !serial_solve && w->F() > 0) {
+    if (w->lm_mode == 0 && !sharded && w->F() > 0) {
       // One enqueue of everything, host work under it: the LM loop leaves its result in pinned memory by itself, the closing
       // evaluation after a rejected last step is gated by the device-side flag, the covariance linearisation and the transfer
       // of its systems follow, then point statuses and the packed per-frame read-back — and while the GPU is busy with those the
@@ -3610,11 +3437,12 @@ int dsopp_hip_window_time_kernel(dsopp_hip_window *w, int kernel_class, int repe
   });
 }
 
-int dsopp_hip_window_set_lm_mode(dsopp_hip_window *w, int host_driven) {
+int dsopp_hip_window_set_lm_mode(dsopp_hip_window *w, int mode) {
   return guarded([&] {
     if (w) w->export_valid = false;
     if (!w) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null window");
-    w->lm_mode = host_driven;
+    if (mode != 0 && mode != 1) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "lm_mode %d: 0 (fused device loop) or 1 (host-driven stages)", mode);
+    w->lm_mode = mode;
   });
 }
 
@@ -3690,10 +3518,9 @@ void optimizeRepeatedPipelined(dsopp_hip_window &w, int target, int &done, doubl
 
 int dsopp_hip_window_optimize_repeated(dsopp_hip_window *w, int32_t iterations_target, int32_t *iterations_done, double *last_energy) {
   if (!w || iterations_target < 0) return dsopp_hip_window_restore(nullptr);  // reports the invalid argument
-  static const bool no_pipeline = std::getenv("DSOPP_HIP_NO_PIPELINE") != nullptr;  // tuning aid: one solve at a time
   // (landmark-sharded windows too: their collectives are ordered on the stream, and every rank plans the same solves because the
   // decisions are taken from all-reduced sums)
-  if (!no_pipeline && w->lm_mode == 0 && w->opt.force_accept && w->F() > 0 && !w->async_pending) {
+  if (w->lm_mode == 0 && w->opt.force_accept && w->F() > 0 && !w->async_pending) {
     int done = 0;
     double e = 0;
     const int rc = guarded([&] {
@@ -3858,10 +3685,9 @@ int dsopp_hip_depth_maps_mean_square_optical_flow(const dsopp_hip_depth_maps *m,
     const dim3 grid(static_cast<unsigned>((a.width + 255) / 256), static_cast<unsigned>((a.height + kFlowRows - 1) / kFlowRows));
     const size_t n_blocks = static_cast<size_t>(grid.x) * grid.y;
     // the level's reference points, when the tracker has extracted them from THESE maps (estimatePose does, in front of the flows of the same
-    // frame; a refill marks them stale): the list holds exactly the pixels the dense pass keeps.  DSOPP_HIP_FLOW_DENSE=1: always the dense pass
-    static const bool dense_only = std::getenv("DSOPP_HIP_FLOW_DENSE") != nullptr;
+    // frame; a refill marks them stale): the list holds exactly the pixels the dense pass keeps
     dsopp_hip_depth_maps::LevelPoints &pts = m->points[static_cast<size_t>(level)];
-    const bool by_points = !dense_only && pts.n >= 0;
+    const bool by_points = pts.n >= 0;
     const size_t point_blocks = static_cast<size_t>(std::max(1, (pts.n + kFlowPointThreads - 1) / kFlowPointThreads));
     // scratch: [ticket of the point pass (zero-filled with the buffer, re-armed by the kernel) | 7 unused | partials per workgroup]
     m->flow_scratch.reserve(8 + std::max(n_blocks, by_points ? point_blocks : 0) * 2 * kMaxFlowTransforms, 0, st);

@@ -909,7 +909,7 @@ const FrameDev *__restrict__ frames, const PairConst *__restrict__ pc,
     }
   }
   }  // groups
-  // the last group's rows (a padding entry of the XCD-banded launch order has no group: nothing was published, its sums stay zero)
+  // the last group's rows
   SWEEP_STAMP(14);
   if (LIN && be.n_groups > 0) gramContract(gram_lds + (threadIdx.x >> 6) * 64 * kGramStride, gram);
   SWEEP_STAMP(4);

@@ -37,7 +37,7 @@ struct TwoStageArgs {
   double *schur_partials;         // [n_schur_wgs][twoStagePartialCount(F)]: tiles in MFMA layout | b
   double *pair_out;               // [kMaxFrames * kMaxFrames][kPairOut]
   int F;
-  int n_chunks, chunks_per_wg, n_schur_wgs;
+  int n_chunks, n_schur_wgs;
   int ublk_parity;
   long long *dbg;  // nullable tuning aid (-DDSOPP_HIP_STAMPS): phase stamps of workgroup 1, first chunk
   // fused loop: kScalarGroups further workgroups sum the sweep's four energy scalars into fixed groups
@@ -171,16 +171,10 @@ __global__ void __launch_bounds__(kSchurThreads, 4) schurTwoStageKernel(TwoStage
     off_b[q] = __builtin_amdgcn_readfirstlane(16 * (ti + rem));
   }
   double bs_acc = 0;  // b_schur entry threadIdx.x when the tiles have no spare column
-  // chunks are dealt out evenly: with chunks_per_wg = 0 workgroup b takes n / W chunks, the first n mod W workgroups one more
-  int first_chunk, last_chunk;
-  if (a.chunks_per_wg > 0) {
-    first_chunk = blockIdx.x * a.chunks_per_wg;
-    last_chunk = min(first_chunk + a.chunks_per_wg, a.n_chunks);
-  } else {
-    const int base = a.n_chunks / a.n_schur_wgs, rem = a.n_chunks - base * a.n_schur_wgs, b = blockIdx.x;
-    first_chunk = b * base + min(b, rem);
-    last_chunk = first_chunk + base + (b < rem ? 1 : 0);
-  }
+  // chunks are dealt out evenly: workgroup b takes n / W chunks, the first n mod W workgroups one more
+  const int base = a.n_chunks / a.n_schur_wgs, rem = a.n_chunks - base * a.n_schur_wgs, b = blockIdx.x;
+  const int first_chunk = b * base + min(b, rem);
+  const int last_chunk = first_chunk + base + (b < rem ? 1 : 0);
   int staged_r = -1;
   for (int chunk = first_chunk; chunk < last_chunk; ++chunk) {
     const SchurBlock &be = a.schur_table[chunk];

@@ -1380,11 +1380,9 @@ __global__ void acceptFramesKernel(WindowState *st, int F, int accept, double *n
 // device-side Levenberg-Marquardt control — levenberg_marquardt_algorithm.hpp:77-128
 // ---------------------------------------------------------------------------------------------------------------
 struct LmInitArgs {
-  SolveArgs sa;            // frames / st / Hm / bm / regularisers / energy_marginalized
-  const double *partials;  // sweep partials of the initial energy evaluation
-  const double *scalars;   // multi-GPU: all-reduced {energy, n_valid, -, -, idepth_sq}
+  SolveArgs sa;  // frames / st / Hm / bm / regularisers / energy_marginalized
   const SchurBlock *schur_table;
-  int n_sweep_blocks, n_schur_blocks;
+  int n_schur_blocks;
   LmControl *ctrl;  // [2]
   LmParams prm;
   // nullable: the pair constants of every ordered frame pair are set up here too (a solve that starts from a state whose constants
@@ -1397,171 +1395,6 @@ struct LmInitArgs {
   // (sa.st then IS the snapshot — this kernel only reads the states — and restore_state the live block the copy goes to)
   WindowState *restore_state = nullptr;
 };
-
-/** sum of idepth^2 over this rank's landmarks (state norm of acceptStep, problem.hpp:379); grid = schur blocks */
-__global__ void idepthNormKernel(const FrameDev *__restrict__ frames, const SchurBlock *__restrict__ table, double *out) {
-  __shared__ double lds[kSchurThreads / 64];
-  const SchurBlock be = table[blockIdx.x];
-  const FrameDev &fr = frames[be.r];
-  const int i = be.offset + threadIdx.x;
-  double v[1] = {0};
-  if (threadIdx.x < kSchurLandmarks && i < fr.n) v[0] = fr.idepth[i] * fr.idepth[i];
-  blockSum<1, kSchurThreads>(v, lds);
-  if (threadIdx.x == 0) atomicAdd(out, v[0]);
-}
-
-/** result = calculateEnergy() before the loop (levenberg_marquardt_algorithm.hpp:82); single workgroup */
-__global__ void __launch_bounds__(kSolveThreads) lmInitKernel(LmInitArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double *lds = reinterpret_cast<double *>(smem_raw);
-  __shared__ double red[(kSolveThreads / 64) * 2];
-  const int tid = threadIdx.x;
-  double v[2] = {0, 0};
-  if (a.prm.use_reduced_scalars) {
-    v[0] = tid == 0 ? a.scalars[0] : 0.0;
-    v[1] = tid == 0 ? a.scalars[1] : 0.0;
-  } else {
-    for (int b = tid; b < a.n_sweep_blocks; b += kSolveThreads) {
-      v[0] += a.partials[static_cast<size_t>(b) * kPartial + 44];
-      v[1] += a.partials[static_cast<size_t>(b) * kPartial + 45];
-    }
-  }
-  blockSum<2, kSolveThreads>(v, red);
-  const double prior = priorEnergyBlock(a.sa, false, lds, tid);
-  if (tid == 0) {
-    LmControl c;
-    c.lambda = a.prm.lambda0;
-    c.energy = v[0] + prior;
-    c.cand_prior = 0;
-    c.frame_state_sq = c.frame_step_sq = 0;
-    c.idepth_sq = a.scalars[4];
-    c.n_valid = static_cast<int>(v[1] + 0.5);
-    c.converged = 0;
-    c.iteration = 0;
-    c.linear_system_valid = 0;
-    c.need_final_setup = 0;
-    c.active = (a.prm.max_iterations > 0 && c.n_valid > 0) ? 1 : 0;
-    c.pending = 0;
-    c.relin = 0;
-    a.ctrl[0] = c;
-    a.ctrl[1] = c;
-  }
-}
-
-struct LmDecideArgs {
-  const FrameDev *frames;
-  WindowState *st;
-  const SchurBlock *schur_table;
-  const double *partials;  // energy sweep partials: [44] energy, [45] n_valid, [46] sum step^2, [47] sum idepth*step
-  const double *scalars;   // multi-GPU: the same four sums, all-reduced
-  const LmControl *ctrl_in;
-  LmControl *ctrl_out;
-  int n_sweep_blocks, n_schur_blocks;
-  int F;
-  LmParams prm;
-};
-
-/**
- * One loop body's tail (levenberg_marquardt_algorithm.hpp:93-123): compare energies, accept or reject, update lambda and
- * the convergence flags, and apply the decision to the state (acceptStep / rejectStep, problem.hpp:366-402).
- * grid = one workgroup per landmark chunk (+ at least one): every workgroup derives the same decision from the same
- * inputs (deterministic reductions), applies it to its own landmarks; workgroup 0 also moves the frame states and
- * writes the outgoing control block.
- */
-__global__ void __launch_bounds__(kSchurThreads) lmDecideKernel(LmDecideArgs a) {
-  __shared__ double red[(kSchurThreads / 64) * 4];
-  const LmControl cin = *a.ctrl_in;
-  const int tid = threadIdx.x;
-  if (!cin.active) {
-    if (blockIdx.x == 0 && tid == 0) *a.ctrl_out = cin;
-    return;
-  }
-  // energy, n_valid, step_sq(idepth), idepth.step; the frame part of the norms comes from the control block (written by the solve
-  // kernel): workgroup 0 of THIS launch moves the frame states, later workgroups must not derive their decision from them
-  double v[4] = {0, 0, 0, 0};
-  if (a.prm.use_reduced_scalars) {
-    if (tid == 0) {
-      v[0] = a.scalars[0];
-      v[1] = a.scalars[1];
-      v[2] = a.scalars[2];
-      v[3] = a.scalars[3];
-    }
-  } else {
-    for (int b = tid; b < a.n_sweep_blocks; b += kSchurThreads) {
-      const double *p = a.partials + static_cast<size_t>(b) * kPartial;
-      v[0] += p[44];
-      v[1] += p[45];
-      v[2] += p[46];
-      v[3] += p[47];
-    }
-  }
-  blockSum<4, kSchurThreads>(v, red);
-  __shared__ int s_accept;
-  __shared__ LmControl s_out;
-  if (tid == 0) {
-    LmControl c = cin;
-    const double next_energy = v[0] + cin.cand_prior;
-    const int n_valid = static_cast<int>(v[1] + 0.5);
-    int accept = 0;
-    c.iteration = cin.iteration + 1;
-    if (n_valid == 0) {
-      // problem.rejectStep(); break;
-      c.active = 0;
-      c.need_final_setup = 1;
-    } else {
-      if (fabs(cin.energy - next_energy) / cin.energy < a.prm.function_tolerance) c.converged = 1;
-      if (next_energy < cin.energy || (a.prm.force_accept && cin.iteration < a.prm.min_iterations)) {
-        accept = 1;
-        const double state_sq = cin.frame_state_sq + cin.idepth_sq, step_sq = cin.frame_step_sq + v[2];
-        if (step_sq < a.prm.parameter_tolerance * (state_sq + a.prm.parameter_tolerance)) c.converged = 1;
-        c.energy = next_energy;
-        c.n_valid = n_valid;
-        c.lambda = cin.lambda / a.prm.decrease_on_accept;
-        c.linear_system_valid = 0;
-        c.idepth_sq = cin.idepth_sq + 2.0 * v[3] + v[2];
-        c.need_final_setup = 0;
-      } else {
-        c.need_final_setup = 1;
-        if (a.prm.force_accept) {
-          c.active = 0;  // problem.calculateEnergy(); return result;
-        } else {
-          c.lambda = cin.lambda * a.prm.increase_on_reject;
-          c.linear_system_valid = 1;
-        }
-      }
-      if (c.converged || c.iteration >= a.prm.max_iterations) c.active = 0;
-    }
-    s_accept = accept;
-    s_out = c;
-  }
-  __syncthreads();
-  const int accept = s_accept;
-  // landmarks of this workgroup's chunk
-  if (static_cast<int>(blockIdx.x) < a.n_schur_blocks) {
-    const SchurBlock be = a.schur_table[blockIdx.x];
-    const FrameDev &fr = a.frames[be.r];
-    const int i = be.offset + tid;
-    if (tid < kSchurLandmarks && i < fr.n) {
-      if (accept) fr.idepth[i] += fr.idepth_step[i];
-      fr.idepth_step[i] = 0;
-      for (int t = 0; t < a.F; ++t) {
-        if (fr.status[t] == nullptr || i >= fr.n_res[t]) continue;
-        if (accept)
-          fr.status[t][i] = fr.cand[t][i];
-        else
-          fr.cand[t][i] = fr.status[t][i];
-      }
-    }
-  }
-  if (blockIdx.x == 0) {
-    if (tid < kBlk * a.F) {
-      const int f = tid >> 3, c = tid & 7;
-      if (accept) a.st->eps[f][c] += a.st->step[f][c];
-      a.st->step[f][c] = 0;
-    }
-    if (tid == 0) *a.ctrl_out = s_out;
-  }
-}
 
 /** one chunk of 64 landmarks back to the snapshot: idepths, flags and connection statuses (threads >= 64 idle) */
 __device__ __forceinline__ void restoreLandmarkChunk(const FrameDev *__restrict__ frames, const SchurBlock *__restrict__ table, int F, int chunk) {

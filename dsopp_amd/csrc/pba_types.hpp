@@ -114,12 +114,12 @@ struct SweepBlock {
   const hbm_u8 *flags, *status, *fej_valid;
   hbm_u8 *cand;
   const hbm_void *texels_t;  // Texel<S>* of the target frame's level
-  // tiled intensity plane of the target level (pyramid.hpp; nullptr: none — f32 storage or switched off): what residual-only
+  // tiled intensity plane of the target level (pyramid.hpp; nullptr: none — f32 storage): what residual-only
   // sweeps sample instead of the texels; itiles_t = 4 x 2 tiles per image row
   const hbm_void *iplane_t;
   int itiles_t;
   int partial_row;     // row of the sweep's per-workgroup sums this entry writes (= its index in the pair-contiguous numbering the pair
-                       // reductions walk; differs from the launch index only under the XCD-banded launch order, an experiment)
+                       // reductions walk)
 };
 
 /** one thread block of the Schur kernel = a chunk of landmarks of one frame.  The descriptor repeats the frame's

@@ -282,8 +282,7 @@ template <typename S>
 void buildTyped(dsopp_hip_pyramid *p, const uint8_t *img_dev, const uint8_t *vig_dev, const double *lut_dev, double vmax) {
   hipStream_t st = p->sr.stream;
   dim3 block(kTileX, kTileY);
-  static const bool no_fused = std::getenv("DSOPP_HIP_PYRAMID_CHAIN") != nullptr;  // tuning aid: always the level-by-level chain
-  if (!vig_dev && !no_fused) {
+  if (!vig_dev) {
     // no vignette: every level straight from the 8-bit image in one launch (with a vignette every level-0 value costs a division,
     // which the nested means would repeat 4^l times: the chain below stays)
     AllLevelsArgs a;
@@ -451,11 +450,10 @@ int dsopp_hip_pyramid_build_device(dsopp_hip_pyramid *p, const void *image_dev, 
 namespace {
 /** the caller's image into this pyramid's pinned buffer with non-temporal stores: the destination is read next by the DMA engine, not by
  *  the host, so the copy neither reads the old lines of the buffer first (write-allocate) nor leaves 1.3 MB of them in the caches —
- *  memcpy() takes 67 us for a 1280 x 1024 image on the tracker's per-frame path (DSOPP_HIP_IMAGE_COPY=memcpy: A/B) */
+ *  memcpy() takes 67 us for a 1280 x 1024 image on the tracker's per-frame path */
 void copyToPinned(uint8_t *dst, const uint8_t *src, size_t n) {
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-  static const bool plain = std::getenv("DSOPP_HIP_IMAGE_COPY") != nullptr && std::string(std::getenv("DSOPP_HIP_IMAGE_COPY")) == "memcpy";
-  if (!plain && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
     size_t i = 0;
     for (; i + 64 <= n; i += 64) {
       const __m128i a = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + i)), b = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + i + 16));
@@ -491,9 +489,8 @@ int dsopp_hip_pyramid_build(dsopp_hip_pyramid *p, const uint8_t *image_host, con
       HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)
     }
     // In pieces: the DMA of a piece (1.3 MB over the host link: ~50 us, as long as the memcpy itself) runs while the host copies the next
-    // one — the consumer's wait for the pyramid shrinks by three quarters of the transfer (DSOPP_HIP_IMAGE_PIECES=1: one piece, A/B)
-    static const int pieces_env = std::getenv("DSOPP_HIP_IMAGE_PIECES") ? std::atoi(std::getenv("DSOPP_HIP_IMAGE_PIECES")) : 4;
-    const size_t pieces = n >= (size_t(1) << 19) ? static_cast<size_t>(std::max(1, std::min(pieces_env, 16))) : 1;
+    // one — the consumer's wait for the pyramid shrinks by three quarters of the transfer
+    const size_t pieces = n >= (size_t(1) << 19) ? 4 : 1;
     const size_t piece = ((n + pieces - 1) / pieces + 4095) & ~static_cast<size_t>(4095);
     for (size_t off = 0; off < n; off += piece) {
       const size_t len = std::min(piece, n - off);

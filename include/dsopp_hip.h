@@ -328,9 +328,9 @@ int dsopp_hip_window_optimize(dsopp_hip_window *w, double *energy, int32_t *iter
 int dsopp_hip_window_optimize_async(dsopp_hip_window *w);
 int dsopp_hip_window_optimize_wait(dsopp_hip_window *w, double *energy, int32_t *iterations, int32_t *n_valid);
 /* 0 (default): fused device-side LM loop — 3 launches per Gauss-Newton iteration, one read-back per solve;
- * 1: control flow on the host through the stage entry points (one small read-back per energy evaluation);
- * 2: unfused device-side loop (5 launches per iteration).  Same arithmetic in all three; 1 and 2 are kept for debugging and
- * as parity cross-checks of the fused control logic */
+ * 1: control flow on the host through the stage entry points (one small read-back per energy evaluation).  Same arithmetic in
+ * both; 1 is kept for debugging and as the parity cross-check of the fused control logic.  Any other value:
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT, the mode stays as it was */
 int dsopp_hip_window_set_lm_mode(dsopp_hip_window *w, int mode);
 /* Summation order of the reduced normal equations inside the fused LM loop.  0 (default): windows of up to 192 chunks of 64
  * landmarks accumulate H_schur with fp64 atomics (fewest launches; the sum order, hence the last bits, vary from run to run — the
@@ -338,8 +338,7 @@ int dsopp_hip_window_set_lm_mode(dsopp_hip_window *w, int mode);
  * two-stage build (per-workgroup partial systems, then one ordered sum per entry: no atomics, bit-reproducible, and faster there).
  * 1: the two-stage build at every size — the fused LM loop (lm_mode 0, the default), the host-driven loop (lm_mode 1) and the stage
  * entry point dsopp_hip_window_linearize are then bit-reproducible from run to run, at the cost of two more launches per Gauss-Newton
- * iteration.  Not covered: the unfused device loop (lm_mode 2, a debugging aid) and the fold-in of marginalised landmarks inside
- * push_frame, which keep the atomic accumulation. */
+ * iteration.  Not covered: the fold-in of marginalised landmarks inside push_frame, which keeps the atomic accumulation. */
 int dsopp_hip_window_set_deterministic(dsopp_hip_window *w, int enable);
 /* TrustRegion...Options::max_iterations of an existing window */
 int dsopp_hip_window_set_max_iterations(dsopp_hip_window *w, int32_t max_iterations);

@@ -26,7 +26,7 @@ for case in range(N):
     kw = dict(first_estimate_jacobians=int(rng.integers(0, 2)), force_accept=int(rng.integers(0, 2)), max_iterations=int(rng.integers(1, 9)))
     # one time in three the single-process window group (1..4 landmark shards on this GPU, in-process reducer) instead of a window
     shards = int(rng.integers(1, 5)) if rng.integers(0, 3) == 0 else 0
-    lm_mode = int(rng.integers(0, 2 if shards else 3))   # (lm_mode 2, the unfused device loop, is a single-window debugging aid)
+    lm_mode = int(rng.integers(0, 2))
     deterministic = bool(rng.integers(0, 2))
     only = os.environ.get("STRESS_ONLY_CASE")   # re-run one case of a sequence: the random stream is consumed as in the full run
     if only is not None and case != int(only):

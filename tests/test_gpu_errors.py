@@ -49,6 +49,10 @@ def test_window_contract_violations(tiny_window):
     assert _code(e) == -6
     with pytest.raises(capi.HipError):        # depth maps need at least 1 level, at most 5
         g.create_reference_depth_maps(0)
+    for mode in (2, -1):                      # lm_mode is 0 (fused device loop) or 1 (host-driven stages)
+        with pytest.raises(capi.HipError) as e:
+            g.set_lm_mode(mode)
+        assert _code(e) == -1
     # the window is still usable after all of that: complete it and solve
     f2 = win.frames[2]
     g.push_frame(f2.frame_id, f2.timestamp, f2.pixelinfo, None, intr, syn.mat_to_params(f2.T_w_c_init), 1.0, np.zeros(2), False, False)

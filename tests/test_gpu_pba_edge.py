@@ -196,7 +196,7 @@ def test_snapshot_restore_is_idempotent(small_window):
     g.close()
 
 
-@pytest.mark.parametrize("lm_mode", [0, 1, 2])
+@pytest.mark.parametrize("lm_mode", [0, 1])
 @pytest.mark.parametrize("fej", [1, 0])
 def test_reject_path_without_force_accept(lm_mode, fej):
     """force_accept = false with enough iterations that LM steps get rejected near the optimum: the device-driven loops must
