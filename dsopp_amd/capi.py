@@ -44,6 +44,9 @@ SYMBOLS = [
     "dsopp_hip_comm_allreduce", "dsopp_hip_window_set_comm",
     "dsopp_hip_window_optimize_async", "dsopp_hip_window_optimize_wait",
     "dsopp_hip_immature_sets_estimate",
+    "dsopp_hip_feature_extractor_create", "dsopp_hip_feature_extractor_destroy", "dsopp_hip_feature_extractor_set_mask",
+    "dsopp_hip_feature_extractor_extract", "dsopp_hip_feature_extractor_get_state", "dsopp_hip_features_shuffle_order",
+    "dsopp_hip_immature_set_create_from_features", "dsopp_hip_immature_set_download_inputs",
     "dsopp_hip_aligner_set_rotation_prior",
     "dsopp_hip_window_refill_reference_depth_maps",
     "dsopp_hip_initialization_poses",
@@ -914,6 +917,88 @@ class ImmatureSet:
         _chk(lib().dsopp_hip_immature_set_download_state(self._h, _p(out["idepth_min"]), _p(out["idepth_max"]), _p(out["uniqueness"]),
                                                          _p(out["search_pixel_interval"]), _p(out["status"], np.uint8), _p(out["traced"], np.uint8)))
         return out
+
+    @classmethod
+    def from_features(cls, extractor: "FeatureExtractor", pyramid: Pyramid, intrinsics, device=0, stream=None) -> "ImmatureSet":
+        """buildFeatures + pushImmatureLandmarks on the device: the landmarks of the extractor's last list inside the camera ROI, with
+        patch and gradient read from level 0 of `pyramid` (dsopp_hip_immature_set_create_from_features)"""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        n = C.c_int32()
+        _chk(lib().dsopp_hip_immature_set_create_from_features(int(device), C.c_void_p(stream or 0), extractor._h, pyramid._h, _p(_f64(intrinsics)),
+                                                               C.byref(self._h), C.byref(n)))
+        self.n = n.value
+        return self
+
+    def inputs(self):
+        """the input planes: projection (n, 2), direction (n, 3), patch (n, 8), gradient (n, 2)"""
+        n = self.n
+        out = dict(projection=np.zeros((n, 2)), direction=np.zeros((n, 3)), patch=np.zeros((n, 8)), gradient=np.zeros((n, 2)))
+        _chk(lib().dsopp_hip_immature_set_download_inputs(self._h, _p(out["projection"]), _p(out["direction"]), _p(out["patch"]), _p(out["gradient"])))
+        return out
+
+
+def features_shuffle_order(n):
+    """the permutation std::shuffle with a fresh std::default_random_engine applies to n elements (no device needed)"""
+    perm = np.zeros(int(n), dtype=np.int32)
+    _chk(lib().dsopp_hip_features_shuffle_order(int(n), _p(perm, np.int32)))
+    return perm
+
+
+class FeatureExtractor:
+    """features::SobelTrackingFeaturesExtractor on the device (dsopp_hip_feature_extractor): stateful across extract() calls."""
+
+    def __init__(self, width, height, point_density_for_detector=1500.0, quantile_level=0.6, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.device = int(width), int(height), device
+        self._mask = None
+        self._capacity = 4096
+        _chk(lib().dsopp_hip_feature_extractor_create(int(device), C.c_void_p(stream or 0), self.width, self.height,
+                                                      C.c_double(point_density_for_detector), C.c_double(quantile_level), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_feature_extractor_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_mask(self, mask):
+        m = _u8(mask)
+        assert m is None or m.shape == (self.height, self.width)
+        _chk(lib().dsopp_hip_feature_extractor_set_mask(self._h, _p(m, np.uint8)))
+        self._mask = None if m is None else m.copy()
+
+    def extract_raw(self, image, capacity):
+        """one dsopp_hip_feature_extractor_extract call: (return code, xy (n, 2) or None, n)"""
+        img = _u8(image)
+        assert img.shape == (self.height, self.width)
+        xy = np.zeros((max(int(capacity), 1), 2))
+        n = C.c_int32()
+        rc = lib().dsopp_hip_feature_extractor_extract(self._h, _p(img, np.uint8), int(capacity), _p(xy), C.byref(n))
+        return rc, (xy[:n.value].copy() if rc == 0 else None), n.value
+
+    def extract(self, image, mask=None):
+        """TrackingFeaturesExtractor::extract(image, mask) -> (n, 2) float64 (x, y); mask None = all pixels valid"""
+        if (mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask)):
+            self.set_mask(mask)
+        rc, xy, n = self.extract_raw(image, self._capacity)
+        if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: the state is unchanged, run again with the room reported
+            self._capacity = n
+            rc, xy, n = self.extract_raw(image, self._capacity)
+        _chk(rc)
+        return xy
+
+    def state(self):
+        init, thr, ws, found = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        dens = C.c_double()
+        _chk(lib().dsopp_hip_feature_extractor_get_state(self._h, C.byref(init), C.byref(thr), C.byref(ws), C.byref(dens), C.byref(found)))
+        return dict(initialized=bool(init.value), grad_norm_threshold=thr.value, window_size=ws.value, point_density=dens.value,
+                    found_last=found.value)
 
 
 class HipAligner:

@@ -704,43 +704,48 @@ DepthLandmarks landmarkPointers(dsopp_hip_immature_set *s) {
 
 }  // namespace
 
+ImmatureSetPtr dsopp_hip::newImmatureSet(int device, void *stream, int32_t n, const double *projection, const double *direction, const double *patch,
+                                         const double *gradient) {
+  ImmatureSetPtr s(new dsopp_hip_immature_set());
+  s->sr.init(device, stream);
+  s->n = n;
+  hipStream_t st = s->sr.stream;
+  const size_t N = static_cast<size_t>(n);
+  s->d_in.reserve(std::max<size_t>(1, N * 15), 0, st);
+  s->d_io.reserve(std::max<size_t>(1, N * 4), 0, st);
+  s->d_flags.reserve(std::max<size_t>(1, N * 2), 0, st);
+  if (projection) s->d_in.upload(projection, 2 * N, 0, st);
+  if (direction) s->d_in.upload(direction, 3 * N, 2 * N, st);
+  if (patch) s->d_in.upload(patch, 8 * N, 5 * N, st);
+  if (gradient) s->d_in.upload(gradient, 2 * N, 13 * N, st);
+  // constructor defaults of ImmatureTrackingLandmark (immature_tracking_landmark.hpp:93-106)
+  std::vector<double> io(4 * N);
+  std::vector<uint8_t> fl(2 * N, 0);
+  for (size_t i = 0; i < N; ++i) {
+    io[i] = 0;
+    io[N + i] = 1. / 0.001;
+    io[2 * N + i] = io[3 * N + i] = std::numeric_limits<double>::max();
+    fl[i] = kImUninitialized;
+  }
+  s->d_io.upload(io.data(), 4 * N, 0, st);
+  s->d_flags.upload(fl.data(), 2 * N, 0, st);
+  // the launch tables of the batched per-frame estimate (this set may be the one that leads a batch): allocated here, at
+  // keyframe time, so that the per-frame call allocates nothing (a pinned allocation in its first call cost 0.1 ms)
+  HIP_CHECK(hipHostMalloc(&s->h_tables, sizeof(Tables), hipHostMallocDefault));
+  HIP_CHECK(hipEventCreateWithFlags(&s->tables_copied, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(s->tables_copied, st));
+  s->d_tables.reserve(sizeof(Tables), 0, st);
+  s->sr.sync();
+  return s;
+}
+
 extern "C" {
 
 int dsopp_hip_immature_set_create(int device, void *stream, int32_t n, const double *projection, const double *direction, const double *patch,
                                   const double *gradient, dsopp_hip_immature_set **out) {
   return guarded([&] {
     if (!out || n < 0 || (n && (!projection || !direction || !patch || !gradient))) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    auto s = std::make_unique<dsopp_hip_immature_set>();
-    s->sr.init(device, stream);
-    s->n = n;
-    hipStream_t st = s->sr.stream;
-    const size_t N = static_cast<size_t>(n);
-    s->d_in.reserve(std::max<size_t>(1, N * 15), 0, st);
-    s->d_io.reserve(std::max<size_t>(1, N * 4), 0, st);
-    s->d_flags.reserve(std::max<size_t>(1, N * 2), 0, st);
-    s->d_in.upload(projection, 2 * N, 0, st);
-    s->d_in.upload(direction, 3 * N, 2 * N, st);
-    s->d_in.upload(patch, 8 * N, 5 * N, st);
-    s->d_in.upload(gradient, 2 * N, 13 * N, st);
-    // constructor defaults of ImmatureTrackingLandmark (immature_tracking_landmark.hpp:93-106)
-    std::vector<double> io(4 * N);
-    std::vector<uint8_t> fl(2 * N, 0);
-    for (size_t i = 0; i < N; ++i) {
-      io[i] = 0;
-      io[N + i] = 1. / 0.001;
-      io[2 * N + i] = io[3 * N + i] = std::numeric_limits<double>::max();
-      fl[i] = kImUninitialized;
-    }
-    s->d_io.upload(io.data(), 4 * N, 0, st);
-    s->d_flags.upload(fl.data(), 2 * N, 0, st);
-    // the launch tables of the batched per-frame estimate (this set may be the one that leads a batch): allocated here, at
-    // keyframe time, so that the per-frame call allocates nothing (a pinned allocation in its first call cost 0.1 ms)
-    HIP_CHECK(hipHostMalloc(&s->h_tables, sizeof(Tables), hipHostMallocDefault));
-    HIP_CHECK(hipEventCreateWithFlags(&s->tables_copied, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(s->tables_copied, st));
-    s->d_tables.reserve(sizeof(Tables), 0, st);
-    s->sr.sync();
-    *out = s.release();
+    *out = newImmatureSet(device, stream, n, projection, direction, patch, gradient).release();
   });
 }
 
@@ -805,6 +810,20 @@ int dsopp_hip_immature_set_download_state(dsopp_hip_immature_set *s, double *ide
     if (search_pixel_interval) std::memcpy(search_pixel_interval, hd + 3 * N, N * sizeof(double));
     if (status) std::memcpy(status, hf, N);
     if (traced) std::memcpy(traced, hf + N, N);
+  });
+}
+
+int dsopp_hip_immature_set_download_inputs(const dsopp_hip_immature_set *s, double *projection, double *direction, double *patch, double *gradient) {
+  return guarded([&] {
+    if (!s) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null set");
+    s->sr.use();
+    hipStream_t st = s->sr.stream;
+    const size_t N = static_cast<size_t>(s->n);
+    if (projection) s->d_in.download(projection, 2 * N, 0, st);
+    if (direction) s->d_in.download(direction, 3 * N, 2 * N, st);
+    if (patch) s->d_in.download(patch, 8 * N, 5 * N, st);
+    if (gradient) s->d_in.download(gradient, 2 * N, 13 * N, st);
+    s->sr.sync();
   });
 }
 

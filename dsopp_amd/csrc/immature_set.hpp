@@ -5,6 +5,8 @@
 #pragma once
 #include "common.hpp"
 
+#include <memory>
+
 struct dsopp_hip_immature_set {
   dsopp_hip::StreamRef sr;
   int n = 0;
@@ -17,3 +19,15 @@ struct dsopp_hip_immature_set {
   dsopp_hip::DeviceBuffer<char> d_tables;
   hipEvent_t tables_copied = nullptr;        // the previous batch's table upload has left the pinned buffer
 };
+
+namespace dsopp_hip {
+struct ImmatureSetDeleter {
+  void operator()(dsopp_hip_immature_set *s) const { dsopp_hip_immature_set_destroy(s); }
+};
+using ImmatureSetPtr = std::unique_ptr<dsopp_hip_immature_set, ImmatureSetDeleter>;
+/** A set of n landmarks in the ImmatureTrackingLandmark constructor state (depth_estimation.hip), synchronised on return.  The input
+ *  planes (projection 2n | direction 3n | patch 8n | gradient 2n of d_in) are uploaded from the host arrays that are not NULL; the
+ *  others are left for the caller to write on the set's stream (dsopp_hip_immature_set_create_from_features, features.hip). */
+ImmatureSetPtr newImmatureSet(int device, void *stream, int32_t n, const double *projection, const double *direction, const double *patch,
+                              const double *gradient);
+}  // namespace dsopp_hip

@@ -526,6 +526,48 @@ class HipPoseAlignment {
   time_point target_time_ = 0;
 };
 
+/** features::SobelTrackingFeaturesExtractor (src/features/src/sobel_tracking_features_extractor.cpp:70-134) on the device: the candidate
+ *  pixels of a new keyframe.  Stateful as the reference: the first extract fixes the gradient-norm threshold and the window size, every
+ *  later call adapts the threshold.  extract() mirrors TrackingFeaturesExtractor::extract(image, mask) and returns the features'
+ *  coordinates (TrackingFeaturesFrame); the list also stays on the device for DeviceImmatureSet's constructor from an extractor. */
+class HipSobelTrackingFeaturesExtractor {
+ public:
+  using Feature = std::array<double, 2>;
+  HipSobelTrackingFeaturesExtractor(int width, int height, double point_density_for_detector = 1500, double quantile_level = 0.6,
+                                    int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_feature_extractor_create(device, stream, width, height, point_density_for_detector, quantile_level, &ex_));
+  }
+  ~HipSobelTrackingFeaturesExtractor() { dsopp_hip_feature_extractor_destroy(ex_); }
+  HipSobelTrackingFeaturesExtractor(const HipSobelTrackingFeaturesExtractor &) = delete;
+  HipSobelTrackingFeaturesExtractor &operator=(const HipSobelTrackingFeaturesExtractor &) = delete;
+  /** image: W x H 8-bit grey (CameraFeatures::frame_data_); mask: the camera's level-0 CameraMask bytes, nullptr = all valid.  The mask
+   *  is a per-camera constant (CameraFeatures::pyramidOfMasks()[0]): it is eroded again only when a different array is passed. */
+  std::vector<Feature> extract(const uint8_t *image, const uint8_t *mask) {
+    if (!mask_set_ || mask != mask_) {
+      check(dsopp_hip_feature_extractor_set_mask(ex_, mask));
+      mask_ = mask;
+      mask_set_ = true;
+    }
+    int32_t n = 0;
+    int rc = dsopp_hip_feature_extractor_extract(ex_, image, static_cast<int32_t>(xy_.size() / 2), xy_.data(), &n);
+    if (rc == DSOPP_HIP_ERR_CAPACITY) {  // the state is unchanged: run again with the room reported
+      xy_.resize(2 * static_cast<size_t>(n));
+      rc = dsopp_hip_feature_extractor_extract(ex_, image, n, xy_.data(), &n);
+    }
+    check(rc);
+    std::vector<Feature> out(static_cast<size_t>(n));
+    for (size_t i = 0; i < out.size(); ++i) out[i] = {xy_[2 * i], xy_[2 * i + 1]};
+    return out;
+  }
+  const dsopp_hip_feature_extractor *handle() const { return ex_; }
+
+ private:
+  dsopp_hip_feature_extractor *ex_ = nullptr;
+  const uint8_t *mask_ = nullptr;
+  bool mask_set_ = false;
+  std::vector<double> xy_ = std::vector<double>(2 * 4096);
+};
+
 /** The immature landmarks of one keyframe kept on the device for their lifetime (ActiveKeyframe::immature_landmarks_:
  *  created by pushImmatureLandmarks, traced every frame by the depth estimator, consumed by the activator). */
 class DeviceImmatureSet {
@@ -544,6 +586,28 @@ class DeviceImmatureSet {
     }
     check(dsopp_hip_immature_set_create(device, stream, static_cast<int32_t>(n_), proj.data(), dir.data(), patch.data(), grad.data(), &s_));
     upload(landmarks);
+  }
+  /** buildFeatures + pushImmatureLandmarks (build_features.hpp:20-32, active_keyframe.cpp:95-112) on the device for the extractor's last
+   *  list over level 0 of the keyframe's pyramid: features outside insideCameraROI are dropped.  `landmarks` receives the host copy
+   *  (projection, direction, patch, gradient; the estimator state at the constructor defaults) that the activator keeps. */
+  DeviceImmatureSet(const HipSobelTrackingFeaturesExtractor &extractor, const DevicePyramid &keyframe_pyramid, const PinholeModel &model,
+                    std::vector<ImmatureLandmarkView> &landmarks, int device = 0, void *stream = nullptr) {
+    const double intr[4] = {model.fx, model.fy, model.cx, model.cy};
+    int32_t n = 0;
+    check(dsopp_hip_immature_set_create_from_features(device, stream, extractor.handle(), keyframe_pyramid.handle(), intr, &s_, &n));
+    n_ = static_cast<size_t>(n);
+    std::vector<double> proj(2 * n_), dir(3 * n_), patch(8 * n_), grad(2 * n_);
+    check(dsopp_hip_immature_set_download_inputs(s_, proj.data(), dir.data(), patch.data(), grad.data()));
+    landmarks.assign(n_, ImmatureLandmarkView{});
+    for (size_t i = 0; i < n_; ++i) {
+      ImmatureLandmarkView &l = landmarks[i];
+      for (size_t k = 0; k < 2; ++k) {
+        l.projection[k] = proj[2 * i + k];
+        l.gradient[k] = grad[2 * i + k];
+      }
+      for (size_t k = 0; k < 3; ++k) l.direction[k] = dir[3 * i + k];
+      for (size_t k = 0; k < 8; ++k) l.patch[k] = patch[8 * i + k];
+    }
   }
   ~DeviceImmatureSet() { dsopp_hip_immature_set_destroy(s_); }
   DeviceImmatureSet(const DeviceImmatureSet &) = delete;
@@ -589,7 +653,7 @@ class DeviceImmatureSet {
   }
 
  private:
-  size_t n_;
+  size_t n_ = 0;
   dsopp_hip_immature_set *s_ = nullptr;
 };
 

@@ -443,6 +443,54 @@ int dsopp_hip_estimate_depths(const dsopp_hip_pyramid *target_pyramid, int level
                               const double *gradient /* 2n */, double *idepth_min, double *idepth_max, double *uniqueness,
                               double *search_pixel_interval, uint8_t *status, uint8_t *traced);
 
+/* the input planes of a set as create() took them (projection 2n, direction 3n, patch 8n, gradient 2n); any pointer may be NULL.
+ * What fills the host copy of a set built on the device by dsopp_hip_immature_set_create_from_features: the keyframe keeps its
+ * ImmatureTrackingLandmark objects on the host (immature_tracking_landmark.hpp:26-106), and the host mirror's activator reads
+ * their projection and patch (ImmatureLandmarkView, dsopp_amd/host/dsopp_hip_solvers.hpp). */
+int dsopp_hip_immature_set_download_inputs(const dsopp_hip_immature_set *s, double *projection, double *direction, double *patch,
+                                           double *gradient);
+
+/* ---- tracking-feature extraction (the candidate pixels of a new keyframe) ----
+ * features::SobelTrackingFeaturesExtractor (src/features/src/sobel_tracking_features_extractor.cpp:70-134), the extractor
+ * camera_fabric.cpp:103-123 builds when nothing else is configured, run once per keyframe on the 8-bit grey image
+ * (camera_features.cpp:36-41).  Stateful as the reference: the first extract() fixes the gradient-norm threshold (the
+ * quantile_level quantile of |Sx| + |Sy|) and the window size sqrt(W * H * (1 - q) / density); every later call adapts the
+ * threshold.  The `eigen` extractor (DSO's pixel selector) is not provided.
+ * width, height >= 16; point_density_for_detector > 0; quantile_level in (0, 1), else DSOPP_HIP_ERR_INVALID_ARGUMENT.
+ * Before the first extract the state reads initialized 0, threshold 0, window size 15 (tracking_features_extractor.hpp:51). */
+typedef struct dsopp_hip_feature_extractor dsopp_hip_feature_extractor;
+int dsopp_hip_feature_extractor_create(int device, void *stream, int width, int height, double point_density_for_detector, double quantile_level,
+                                       dsopp_hip_feature_extractor **out);
+void dsopp_hip_feature_extractor_destroy(dsopp_hip_feature_extractor *ex);
+/* the camera mask the extractor erodes (CameraMask::getEroded(4).getEroded(3), camera_mask.cpp:20-29: a 15 x 15 erosion whose
+ * image edge never erodes) and uses for every later extract; NULL = all pixels valid (CameraMask(rows, cols)).  W x H bytes,
+ * non-zero = valid. */
+int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const uint8_t *mask_host);
+/* SobelTrackingFeaturesExtractor::extract(image, mask): the first pixel (raster order) with |Sx| + |Sy| above the threshold and
+ * inside the eroded mask of every window, in window order, shuffled by std::shuffle with a fresh std::default_random_engine and cut
+ * to (long)point_density_for_detector.  xy = (x, y) per feature (2 * capacity doubles), *n = their number.  A capacity below the
+ * result returns DSOPP_HIP_ERR_CAPACITY with *n = the number needed and the extractor state unchanged.  One deliberate deviation:
+ * where the reference's threshold update is undefined (no feature found: an integer division by zero; a non-finite or
+ * out-of-range quotient) the threshold is kept.  The list stays on the device for dsopp_hip_immature_set_create_from_features. */
+int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n);
+/* the extractor's state after the last extract (any pointer may be NULL): initialized_, grad_norm_threshold_, current_potential_
+ * (the window size), point_density_for_detector_ (lowered by the first call when the window would be below one pixel), and the
+ * number of windows with a hit before the truncation */
+int dsopp_hip_feature_extractor_get_state(const dsopp_hip_feature_extractor *ex, int32_t *initialized, int32_t *grad_norm_threshold,
+                                          int32_t *window_size, double *point_density, int32_t *found_last);
+/* The permutation std::shuffle(first, first + n, std::default_random_engine{}) applies (libstdc++), written as perm[i] = the
+ * original index at position i: the reference's shuffle of step :127.  It states the reference's ordering for tests and
+ * callers and computes nothing the device would; the one entry point of this section that needs no device. */
+int dsopp_hip_features_shuffle_order(int32_t n, int32_t *perm);
+/* buildFeatures (src/tracker/tracker/internal/tracker/build_features.hpp:20-32: features outside insideCameraROI dropped, order
+ * kept; direction = ((x - cx) / fx, (y - cy) / fy, 1) with the inverse focal lengths precomputed) + pushImmatureLandmarks
+ * (src/track/frames/src/active_keyframe.cpp:95-112: patch = level-0 intensities at the 8 pattern pixels, gradient = the sum of their
+ * (dI/dx, dI/dy) in the image scalar) for the last extract of `ex`, read from level 0 of `pyramid` (f64 or f32, the extractor's size,
+ * same device) after its build: a new set in the ImmatureTrackingLandmark constructor state, *n landmarks, no host round trip of
+ * the patches.  intrinsics = (fx, fy, cx, cy). */
+int dsopp_hip_immature_set_create_from_features(int device, void *stream, const dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *pyramid,
+                                                const double intrinsics[4], dsopp_hip_immature_set **out, int32_t *n);
+
 /* ---- activation of immature landmarks (row f-3) ----
  * LandmarksActivator<SE3, PinholeCamera, PixelMap, 1, REFINE>::activate (src/tracker/landmarks_activator/src/landmarks_activator.cpp:351-391),
  * called once per new keyframe after pushNewKeyframe and before the keyframe enters the bundle adjustment
