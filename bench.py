@@ -14,15 +14,19 @@ run with the same arguments can be compared output for output.
               [combined system | energy scalars], enqueued by the library itself (dsopp_hip_comm: ncclAllReduce on the
               window's stream; --comm torch routes it through a torch.distributed callback instead).
               Headline at N > 1 = STRONG scaling on BASELINE.json configs[3] (C3: 7 KF, 20 000 points in TOTAL, sharded): value =
-              GN iterations of the whole window / wall time, "scaling": "strong"; rank 0 first times the SAME window alone on its
-              GPU ("same_workload_1gpu") and the line carries speedup = value / same_workload_1gpu.  C1 weak scaling (2000 points
-              PER GPU) and C4 strong scaling (12 KF / 50 000) ride along as extras ("weak_scaling_c1", "strong_scaling"), and so
-              does "window_group": the same C3 window driven by ONE process over all N devices through dsopp_hip_window_group
+              GN iterations of the whole window / wall time, "scaling": "strong".  With --full, rank 0 first times the SAME window
+              alone on its GPU ("same_workload_1gpu") and the line carries speedup = value / same_workload_1gpu; C1 weak scaling
+              (2000 points PER GPU) and C4 strong scaling (12 KF / 50 000) ride along as extras ("weak_scaling_c1", "strong_scaling"),
+              and so does "window_group": the same C3 window driven by ONE process over all N devices through dsopp_hip_window_group
               (scripts/group_bench.py, started by rank 0 after the timed part) — the form the reference's single solver object takes.
               `--workload c1|c3|c4` / `--scaling` select another headline explicitly.  Without a launcher `--gpus N` spawns its own
               ranks (torch.distributed.run) and refuses to run when the node has fewer than N GPUs.
-Extra objects on the same line: roofline (linearisation sweep kernel, measured live with HIP events on the library's
-stream) and cpu_baseline (the oracle = CPU port of the reference algorithm, timed on the host cores of this box).
+A plain run does what the headline needs and nothing more: set up, warm up, time --steps, dump the outputs when asked, print the line.
+`--full` measures everything else after the timed steps, on the same process and window: roofline (linearisation sweep kernel,
+measured live with HIP events on the library's stream) and per-kernel times, cpu_baseline (the oracle = CPU port of the reference
+algorithm, timed on the host cores of this box), the other workloads, the tracker and the other extras; the full result goes to
+bench_extras.json and stderr, the compact headline (with roofline and cpu_baseline) to stdout.  --no-cpu / --no-extras / --no-group
+trim a --full run.
 """
 import argparse
 import json
@@ -256,7 +260,7 @@ def run_sharded_workload(job, torch, capi, syn, distributed, name, args, dtype, 
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=140)
@@ -272,15 +276,24 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--comm", default="native", choices=["native", "torch"],
                     help="N > 1 exchange: native = the library's own ncclAllReduce (dsopp_hip_comm), torch = torch.distributed callback")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the large-window roofline, the tracker (C2) timing and the other extras")
-    ap.add_argument("--no-group", action="store_true", help="N > 1: skip the single-process window-group measurement (row g-1)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: live roofline and per-kernel times, the same window on one GPU "
+                         "(N > 1), the other workloads and extras, the CPU baseline, the window group; the full result goes to "
+                         "bench_extras.json.  Without it a run sets up, warms up, times --steps and prints the headline only")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds of CPU-baseline solves")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the CPU-port columns of the extras")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the large-window roofline, the tracker (C2) timing and the other extras")
+    ap.add_argument("--no-group", action="store_true", help="--full, N > 1: skip the single-process window-group measurement (row g-1)")
     ap.add_argument("--group-timeout", type=int, default=150, help="seconds the window-group process may take")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (energy, poses, affine brightness, inverse depths "
                          "of rank 0's window) to DIR/<name>.npy, for output-for-output comparison of two builds")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -320,7 +333,7 @@ def main():
     full_win = syn.make_window(num_frames=F, num_points=total_points, width=args.width, height=args.height, seed=0)
     dtype = capi.F64 if args.dtype == "f64" else capi.F32
     same_workload_1gpu = None
-    if world > 1 and scaling == "strong":
+    if args.full and world > 1 and scaling == "strong":
         # rank 0 alone, the whole window on its one GPU, no collective: the rate the sharded run is compared with (same process,
         # same box, same build); the other ranks wait at the barrier
         if rank == 0:
@@ -364,9 +377,65 @@ def main():
     block_s, block_times = timed_blocks(job, torch, run_iterations, args.steps, max_blocks=1)
     steps_done = args.steps
     if args.dump_outputs and rank == 0:
-        # the window as the last timed step left it (the profiling passes below run further iterations on it)
+        # the window as the last timed step left it (the --full passes below run further iterations on it)
         dump_outputs(args.dump_outputs, window_outputs(g, win, last_energy[0]))
 
+    ms_per_step = block_s / steps_done * 1e3
+    per_job = world if scaling == "weak" else 1   # weak: every rank advances its own 2000-point share of the window
+    line = {
+        "metric": "Gauss-Newton iters/sec (7-KF window, 2k active pts)",
+        "value": per_job * steps_done / block_s,
+        "unit": "GN iterations/s",
+        "n_gpus": world,
+        "steps": steps_done,
+        "warmup": args.warmup,  # as given; a warm-up shorter than one LM solve (7 iterations) is rounded up to one:
+        "warmup_effective": warmup,
+        "ms_per_step": ms_per_step,
+        "timed_region_s": block_s,   # the timed block: `steps` iterations between two barrier + synchronize pairs
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic",
+        "timing": {"what": f"one timed block of exactly {steps_done} GN iterations (= --steps; barrier + synchronize on both sides, "
+                           "max over ranks); inside the block the LM solves (7 iterations each, the "
+                           "window restored in front of every solve) are enqueued back to back, their results fetched with one copy at the "
+                           "end of the block: no host synchronisation between solves",
+                   "blocks": len(block_times), "block_ms_min": min(block_times) * 1e3, "block_ms_median": block_s * 1e3,
+                   "block_ms_max": max(block_times) * 1e3},
+        "config": {"workload": f"{desc} ({total_points} total, {P_local} on rank 0), {args.width}x{args.height}, full clique, "
+                               "production LM settings", "name": args.workload,
+                   "frames": F, "points_per_gpu": P, "total_points": total_points,
+                   "parallelism": f"landmark-sharded x{world}" if world > 1 else "single GPU",
+                   "exchange": job.transport, "ranks": world,
+                   # the launcher's world size above; what the communicator itself counts (ncclCommCount) when the native one is in use
+                   "ranks_comm": job.comm.size() if job.comm is not None else None},
+    }
+
+    if args.full:
+        same = None
+        if same_workload_1gpu is not None:
+            # strong scaling: the same window on ONE GPU of this node (rank 0 alone, before the sharded run) and the ratio
+            same = {"value": same_workload_1gpu, "unit": "GN iterations/s",
+                    "what": f"{desc}: the whole window ({total_points} points) on rank 0's GPU alone, no collective, "
+                            f"median of 15 blocks of {steps_done} iterations"}
+        measure_beside_headline(job, torch, capi, syn, distributed, g, win, args, run_iterations, line, same)
+    if rank == 0:
+        headline = emit(line)[0] if args.full else make_headline(line)
+        os.write(json_fd, (json.dumps(headline, separators=(",", ":")) + "\n").encode())
+    g.close()
+    job.close()
+
+
+def measure_beside_headline(job, torch, capi, syn, distributed, g, win, args, run_iterations, line, same):
+    """--full: everything the run measures beside the headline, after the timed steps, into `line` (rank 0's; the other ranks take part
+    in the collective legs).  Live per-kernel timing and the roofline of the dominant kernel, the committed counter and profile figures,
+    the same window on one GPU (N > 1), the other workloads and extras, the window group, the CPU baseline."""
+    world, rank = job.world, job.rank
+    dtype = capi.F64 if args.dtype == "f64" else capi.F32
+    cfg = line["config"]
+    F, P, P_local, scaling = cfg["frames"], cfg["points_per_gpu"], win.num_points, line["scaling"]
+    ms_per_step = line["ms_per_step"]
     # ---- live per-kernel timing (HIP events on the library's stream) -> roofline of the dominant kernel
     g.set_profiling(True)
     run_iterations(35)
@@ -441,86 +510,49 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu:
         cpu_baseline = run_cpu_baseline(args, F, P, win, syn)
 
-    if rank == 0:
-        # the committed rocprofv3 figure of the kernel AS THE LOOP RUNS IT (kernel_stats csv of the same command under profiles/) rides
-        # along as `frac_profile`; `roofline.frac` itself is the event-bracketed measurement of this run
-        prof_roof = profile_roofline(b_lin) if (F, P_local, args.dtype) == (7, 2000, "f64") else None
-        in_loop = (prof_roof or {}).get("in_loop")
-        frac_events = achieved / HBM_PEAK_GBS
-        ms_per_step = block_s / steps_done * 1e3
-        per_job = world if scaling == "weak" else 1   # weak: every rank advances its own 2000-point share of the window
-        line = {
-            "metric": "Gauss-Newton iters/sec (7-KF window, 2k active pts)",
-            "value": per_job * steps_done / block_s,
-            "unit": "GN iterations/s",
-            "n_gpus": world,
-            "steps": steps_done,
-            "warmup": args.warmup,  # as given; a warm-up shorter than one LM solve (7 iterations) is rounded up to one:
-            "warmup_effective": warmup,
-            "ms_per_step": ms_per_step,
-            "timed_region_s": block_s,   # the timed block: `steps` iterations between two barrier + synchronize pairs
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "timing": {"what": f"one timed block of exactly {steps_done} GN iterations (= --steps; barrier + synchronize on both sides, "
-                               "max over ranks); inside the block the LM solves (7 iterations each, the "
-                               "window restored in front of every solve) are enqueued back to back, their results fetched with one copy at the "
-                               "end of the block: no host synchronisation between solves",
-                       "blocks": len(block_times), "block_ms_min": min(block_times) * 1e3, "block_ms_median": block_s * 1e3,
-                       "block_ms_max": max(block_times) * 1e3},
-            "config": {"workload": f"{desc} ({total_points} total, {P_local} on rank 0), {args.width}x{args.height}, full clique, "
-                                   "production LM settings", "name": args.workload,
-                       "frames": F, "points_per_gpu": P, "total_points": total_points,
-                       "parallelism": f"landmark-sharded x{world}" if world > 1 else "single GPU",
-                       "exchange": job.transport, "ranks": world,
-                       # the launcher's world size above; what the communicator itself counts (ncclCommCount) when the native one is in use
-                       "ranks_comm": job.comm.size() if job.comm is not None else None},
-            # `frac` / `achieved` / `avg_launch_us` are THIS run's measurement: HIP events on the library's stream around 200 back-to-back
-            # launches of the kernel as the loop configures it.  `frac_profile` is the committed rocprofv3 --kernel-trace --stats average of
-            # the kernel inside the bench loop (profiles/, file and commit named) — the cross-check, never the headline figure.
-            "roofline": {"bound": "hbm", "kernel": "sweepKernel<double,LIN,FEJ,HUBER> (linearisation sweep as the LM loop launches it)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac_events,
-                         "frac_source": "HIP events of this run on the library's stream, 200 back-to-back launches",
-                         "frac_profile": in_loop["frac"] if in_loop else None,
-                         "profile_source": in_loop["source"] if in_loop else None,
-                         "profile_commit": in_loop["committed_at"] if in_loop else None,
-                         "traffic": traffic, "traffic_detail": traffic_detail,
-                         "algorithmic_bytes_per_launch": b_lin, "avg_launch_us": lin_avg_s * 1e6,
-                         "mfma": load_mfma_utilisation(),
-                         # whole Gauss-Newton iteration against the same roof: SURVEY.md §8d's B_gn = B_lin + B_en over the
-                         # driver-timed time per iteration (launch gaps, reduction and dense solve included)
-                         "iteration_frac": (b_lin + b_en) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "iteration_algorithmic_bytes": b_lin + b_en,
-                         # the same 200 isolated launches under `rocprofv3 --kernel-trace --stats` (scripts/profile_target.py c1_isolated,
-                         # committed csv): rocprof's per-dispatch duration of back-to-back launches includes each launch's ramp, which
-                         # overlaps the previous kernel's tail, so its average sits ~10 % above the event-bracketed wall time per launch
-                         "profile": prof_roof,
-                         "what_the_fraction_is": "algorithmic bytes (no texel reuse counted) over kernel time against the 8 TB/s HBM3E peak; "
-                                                 "the C1 working set (69 MB of texels) fits the 256 MB Infinity Cache, whose hits the TCC_EA "
-                                                 "counters behind `traffic` include: a latency-bound gather, not DRAM streaming",
-                         "opening_linearisation": {"avg_launch_us": isolated["sweep_linearize"],
-                                                   "frac": b_lin / (isolated["sweep_linearize"] * 1e-6) / 1e9 / HBM_PEAK_GBS},
-                         "energy_sweep": {"algorithmic_bytes_per_launch": b_en, "avg_launch_us": isolated["sweep_energy"]}},
-            "kernels": kernels,
-            "kernels_isolated_avg_us": isolated,
-            "dominant_kernel_by_total_time": dominant,
-        }
-        if same_workload_1gpu is not None:
-            # strong scaling: the same window on ONE GPU of this node (rank 0 alone, before the sharded run) and the ratio
-            line["same_workload_1gpu"] = {"value": same_workload_1gpu, "unit": "GN iterations/s",
-                                          "what": f"{desc}: the whole window ({total_points} points) on rank 0's GPU alone, no collective, "
-                                                  f"median of 15 blocks of {steps_done} iterations"}
-            line["speedup"] = line["value"] / same_workload_1gpu
-        line.update(extras)
-        if cpu_baseline is not None:
-            line["cpu_baseline"] = cpu_baseline
-            line["speedup_vs_cpu_port"] = line["value"] / cpu_baseline["value"]
-        headline, extras_path = emit(line)
-        os.write(json_fd, (json.dumps(headline, separators=(",", ":")) + "\n").encode())
-    g.close()
-    job.close()
+    if rank != 0:
+        return
+    # the committed rocprofv3 figure of the kernel AS THE LOOP RUNS IT (kernel_stats csv of the same command under profiles/) rides
+    # along as `frac_profile`; `roofline.frac` itself is the event-bracketed measurement of this run
+    prof_roof = profile_roofline(b_lin) if (F, P_local, args.dtype) == (7, 2000, "f64") else None
+    in_loop = (prof_roof or {}).get("in_loop")
+    frac_events = achieved / HBM_PEAK_GBS
+    # `frac` / `achieved` / `avg_launch_us` are THIS run's measurement: HIP events on the library's stream around 200 back-to-back
+    # launches of the kernel as the loop configures it.  `frac_profile` is the committed rocprofv3 --kernel-trace --stats average of
+    # the kernel inside the bench loop (profiles/, file and commit named) — the cross-check, never the headline figure.
+    line["roofline"] = {"bound": "hbm", "kernel": "sweepKernel<double,LIN,FEJ,HUBER> (linearisation sweep as the LM loop launches it)",
+                        "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac_events,
+                        "frac_source": "HIP events of this run on the library's stream, 200 back-to-back launches",
+                        "frac_profile": in_loop["frac"] if in_loop else None,
+                        "profile_source": in_loop["source"] if in_loop else None,
+                        "profile_commit": in_loop["committed_at"] if in_loop else None,
+                        "traffic": traffic, "traffic_detail": traffic_detail,
+                        "algorithmic_bytes_per_launch": b_lin, "avg_launch_us": lin_avg_s * 1e6,
+                        "mfma": load_mfma_utilisation(),
+                        # whole Gauss-Newton iteration against the same roof: SURVEY.md §8d's B_gn = B_lin + B_en over the
+                        # driver-timed time per iteration (launch gaps, reduction and dense solve included)
+                        "iteration_frac": (b_lin + b_en) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "iteration_algorithmic_bytes": b_lin + b_en,
+                        # the same 200 isolated launches under `rocprofv3 --kernel-trace --stats` (scripts/profile_target.py c1_isolated,
+                        # committed csv): rocprof's per-dispatch duration of back-to-back launches includes each launch's ramp, which
+                        # overlaps the previous kernel's tail, so its average sits ~10 % above the event-bracketed wall time per launch
+                        "profile": prof_roof,
+                        "what_the_fraction_is": "algorithmic bytes (no texel reuse counted) over kernel time against the 8 TB/s HBM3E peak; "
+                                                "the C1 working set (69 MB of texels) fits the 256 MB Infinity Cache, whose hits the TCC_EA "
+                                                "counters behind `traffic` include: a latency-bound gather, not DRAM streaming",
+                        "opening_linearisation": {"avg_launch_us": isolated["sweep_linearize"],
+                                                  "frac": b_lin / (isolated["sweep_linearize"] * 1e-6) / 1e9 / HBM_PEAK_GBS},
+                        "energy_sweep": {"algorithmic_bytes_per_launch": b_en, "avg_launch_us": isolated["sweep_energy"]}}
+    line["kernels"] = kernels
+    line["kernels_isolated_avg_us"] = isolated
+    line["dominant_kernel_by_total_time"] = dominant
+    if same is not None:
+        line["same_workload_1gpu"] = same
+        line["speedup"] = line["value"] / same["value"]
+    line.update(extras)
+    if cpu_baseline is not None:
+        line["cpu_baseline"] = cpu_baseline
+        line["speedup_vs_cpu_port"] = line["value"] / cpu_baseline["value"]
 
 
 HEADLINE_MAX_BYTES = 4096   # the driver keeps an 8 KB tail of stdout: the ONE stdout line must fit it with room to spare
@@ -534,12 +566,14 @@ ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic
 def make_headline(line):
     """The compact form of the result that goes to stdout: the driver's contract keys + roofline + cpu_baseline and nothing else.  Everything
     the run measured beside the headline (stage table, tracker, tick sequences, large windows, ...) stays in `line`, which emit() writes to
-    bench_extras.json.  Raises when the result would not fit HEADLINE_MAX_BYTES: a line the driver cannot parse is worth nothing."""
+    bench_extras.json.  A run without --full has no roofline or cpu_baseline, and its headline none either.  Raises when the result would not
+    fit HEADLINE_MAX_BYTES: a line the driver cannot parse is worth nothing."""
     head = {k: line[k] for k in HEADLINE_KEYS if k in line}
     cfg = line.get("config") or {}
     head["config"] = {k: cfg[k] for k in ("workload", "name", "frames", "points_per_gpu", "total_points", "parallelism", "exchange", "ranks") if k in cfg}
-    roof = line.get("roofline") or {}
-    head["roofline"] = {k: roof[k] for k in ROOFLINE_KEYS if k in roof}
+    if "roofline" in line:
+        roof = line["roofline"] or {}
+        head["roofline"] = {k: roof[k] for k in ROOFLINE_KEYS if k in roof}
     tm = line.get("timing") or {}
     if tm:
         head["timing"] = {k: tm[k] for k in ("blocks", "block_ms_min", "block_ms_median", "block_ms_max") if k in tm}

@@ -13,8 +13,8 @@ timeout 900 python scripts/pmc_traffic.py c1 > $O/pmc_c1.log 2>&1; cp gpurun_out
 timeout 900 python scripts/pmc_traffic.py large > $O/pmc_large.log 2>&1; cp gpurun_out/pmc_traffic_large.json $O/pmc_traffic_large.json 2>/dev/null
 python scripts/group_bench.py --devices 0,0 --workload c3 --blocks 7 2>/dev/null | grep "^{" > $O/group_bench_c3_two_shards_one_gpu.json
 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu 2>$O/bench_steps20.err | grep "^{" > $O/bench_steps20.json
-DSOPP_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --no-cpu 2>$O/bench_2rank.err | grep "^{" > $O/bench_2rank_one_gpu.json
-python bench.py 2>$O/bench.err | grep "^{" > $O/bench.json
+DSOPP_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --full --no-cpu 2>$O/bench_2rank.err | grep "^{" > $O/bench_2rank_one_gpu.json
+python bench.py --full 2>$O/bench.err | grep "^{" > $O/bench.json
 python - <<'PY'
 import json
 for f in ("bench", "bench_steps20", "bench_2rank_one_gpu"):

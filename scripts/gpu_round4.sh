@@ -36,7 +36,7 @@ timeout 600 python scripts/pmc_traffic.py c1 > $O/pmc_c1.log 2>&1; cp gpurun_out
 timeout 600 python scripts/pmc_traffic.py large > $O/pmc_large.log 2>&1; cp gpurun_out/pmc_traffic_large.json $O/pmc_traffic_large.json 2>/dev/null
 # bench lines
 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu 2>$O/bench_steps20.err | grep "^{" > $O/bench_steps20.json
-python bench.py 2>$O/bench.err | grep "^{" > $O/bench.json
+python bench.py --full 2>$O/bench.err | grep "^{" > $O/bench.json
 python - <<'PY'
 import json
 for f in ("bench", "bench_steps20"):

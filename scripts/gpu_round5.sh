@@ -27,9 +27,9 @@ done
 timeout 600 python scripts/pmc_traffic.py c1 > $O/pmc_c1.log 2>&1; cp gpurun_out/pmc_traffic.json $O/pmc_traffic_c1.json 2>/dev/null
 # ... and of the 12 KF / 50 k window (the library's internal landmark order is what runs)
 timeout 900 python scripts/pmc_traffic.py large > $O/pmc_large.log 2>&1; cp gpurun_out/pmc_traffic_large.json $O/pmc_traffic_large.json 2>/dev/null
-# bench lines: the driver's form, then the default
+# bench lines: the driver's form, then --full
 python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/bench_steps20.err | grep "^{" > $O/bench_steps20.json
-python bench.py 2>$O/bench.err | grep "^{" > $O/bench.json
+python bench.py --full 2>$O/bench.err | grep "^{" > $O/bench.json
 python - <<'PY'
 import json
 for f in ("bench", "bench_steps20"):

@@ -42,9 +42,9 @@ fi
 python scripts/stress_tracker.py 1000 2>/dev/null | grep distinct > $O/stress_tracker.txt
 # native tick driver (200 frames, both sizes)
 python scripts/time_tick_native.py 1280x1024 640x480 2>/dev/null | grep "^{" > $O/tick_native.jsonl
-# bench lines: the driver's form, then the default (full result -> bench_extras.json)
-python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/bench_steps20.err | grep "^{" > $O/bench_steps20.json; cp bench_extras.json $O/bench_steps20_extras.json
-python bench.py 2>$O/bench.err | grep "^{" > $O/bench.json; cp bench_extras.json $O/bench_extras.json
+# bench lines: the driver's form, then --full (full result -> bench_extras.json)
+python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/bench_steps20.err | grep "^{" > $O/bench_steps20.json
+python bench.py --full 2>$O/bench.err | grep "^{" > $O/bench.json; cp bench_extras.json $O/bench_extras.json
 rm -f $O/bench.err $O/bench_steps20.err
 python - <<'PY'
 import json

@@ -62,6 +62,29 @@ def test_emit_writes_extras_file(tmp_path, monkeypatch, capsys):
     assert "tick_sequence" in out.err
 
 
+def _plain_line():
+    # what a run without --full puts in its line: the contract keys, config and timing, none of the measurements beside them
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "warmup_effective", "ms_per_step", "timed_region_s", "higher_is_better",
+            "scaling", "vs_baseline", "dtype", "data", "timing", "config")
+    return {k: v for k, v in _full_line().items() if k in keep}
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (args.full, args.steps, args.warmup, args.dump_outputs) == (False, 20, 5, None)
+    assert bench.parse_args(["--full"]).full is True
+
+
+def test_plain_headline_carries_the_contract_keys_only():
+    line = _plain_line()
+    head = bench.make_headline(line)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert head[k] == line[k], k
+    assert set(head) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "timed_region_s", "higher_is_better",
+                         "scaling", "vs_baseline", "dtype", "data", "config", "timing"}
+
+
 def test_dump_outputs_writes_npy_within_budget(tmp_path):
     """--dump-outputs: one float64 .npy per array; an oversized landmark array becomes the same seeded sample every time"""
     import numpy as np
@@ -84,15 +107,22 @@ def test_dump_outputs_writes_npy_within_budget(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_steps_and_dump_outputs(tmp_path):
-    """--steps K times exactly K GN iterations, ms_per_step is that region / K, and --dump-outputs leaves the C1 window's results"""
+    """--steps K times exactly K GN iterations, ms_per_step is that region / K, and --dump-outputs leaves the C1 window's results; a run
+    without --full measures nothing beside the headline"""
     import subprocess
     import numpy as np
     out = tmp_path / "dump"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "7", "--no-extras",
-                        "--no-cpu", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "7",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
     assert d["steps"] == 10 and d["timing"]["blocks"] == 1
+    assert d["metric"].startswith("Gauss-Newton") and d["unit"] == "GN iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 10 / d["timed_region_s"]) <= 1e-9 * d["value"]
+    for k in ("roofline", "cpu_baseline", "speedup_vs_cpu_port", "frame_tracking_ms_per_frame_1280x1024", "extras_file"):
+        assert k not in d, k
     assert abs(d["ms_per_step"] * 10 - d["timed_region_s"] * 1e3) <= 1e-9 * d["ms_per_step"] * 10
     e, T, ab, idp = (np.load(out / f"{n}.npy") for n in ("energy", "poses", "affine_brightness", "idepth"))
     assert e.shape == (1,) and T.shape == (7, 7) and ab.shape == (7, 2) and idp.shape == (2000,)

@@ -85,7 +85,7 @@ def _run_bench(extra, env_extra=None, timeout=900):
 
 
 def _full_result():
-    """everything the run measured beside the compact stdout headline: bench.py writes it to bench_extras.json at the repo root"""
+    """everything the run measured beside the compact stdout headline: bench.py --full writes it to bench_extras.json at the repo root"""
     import json
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,9 +99,9 @@ def test_bench_script_runs_with_two_ranks():
     block timing, rank-0 JSON line.  Two ranks share this one GPU over gloo (DSOPP_BENCH_SINGLE_DEVICE=1); on a multi-GPU node the
     same script runs one rank per GPU with the library's native ncclAllReduce.
     The N > 1 headline is STRONG scaling on BASELINE.json configs[3] (7 KF / 20 000 points in total, sharded) with the same window's
-    single-GPU rate measured by rank 0 alone beside it."""
+    single-GPU rate measured by rank 0 alone beside it (--full)."""
     import json
-    out = _run_bench(["--gpus", "2", "--steps", "28", "--warmup", "7", "--no-extras", "--no-cpu"], {"DSOPP_BENCH_SINGLE_DEVICE": "1"})
+    out = _run_bench(["--gpus", "2", "--steps", "28", "--warmup", "7", "--full", "--no-extras", "--no-cpu"], {"DSOPP_BENCH_SINGLE_DEVICE": "1"})
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -136,9 +136,10 @@ def test_bench_weak_scaling_workload_two_ranks():
 
 
 def test_bench_strong_scaling_workload_two_ranks():
-    """--workload c4: the dense configuration (12 KF / 50 000 points in total) sharded; value counts whole-window iterations"""
+    """--workload c4: the dense configuration (12 KF / 50 000 points in total) sharded; value counts whole-window iterations; --full adds
+    the same window's single-GPU rate and the speedup"""
     import json
-    out = _run_bench(["--gpus", "2", "--steps", "14", "--warmup", "7", "--workload", "c4", "--no-extras", "--no-cpu", "--no-group"],
+    out = _run_bench(["--gpus", "2", "--steps", "14", "--warmup", "7", "--workload", "c4", "--full", "--no-extras", "--no-cpu", "--no-group"],
                      {"DSOPP_BENCH_SINGLE_DEVICE": "1"})
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
