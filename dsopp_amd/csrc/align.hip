@@ -1357,7 +1357,7 @@ struct dsopp_hip_aligner {
   DeviceBuffer<double> d_u, d_v, d_id, d_int, d_partials[2];
   // the reference points the solve reads: the aligner's own buffers above or the per-level cache of a dsopp_hip_depth_maps
   const double *p_u = nullptr, *p_v = nullptr, *p_id = nullptr, *p_int = nullptr;
-  AlignControl *h_ctrl = nullptr;  // pinned staging of the control block (upload + read-back)
+  PinnedMem<AlignControl> h_ctrl;  // staging of the control block (upload + read-back)
   int lm_path = 0;                 // 0: automatic (single-workgroup loop for small point sets), 1: always one launch per iteration
   bool skip_covariance = false;    // estimate_pose: the per-level covariance is not read by the tracker loop
   bool pyramids_ordered = false;   // estimate_pose already ordered this stream behind both pyramids' builds (one wait per frame, not per level)
@@ -1365,7 +1365,7 @@ struct dsopp_hip_aligner {
   DeviceBuffer<double> d_pyr_partials;
 
   DeviceBuffer<AlignPyramidResult> d_pyr_out;
-  AlignPyramidResult *h_pyr_out = nullptr;     // pinned
+  PinnedMem<AlignPyramidResult> h_pyr_out;
   int pyr_phase[kPyramidHypotheses] = {-1, -1, -1, -1, -1, -1, -1, -1};  // per hypothesis slot: buffer phase the next persistent launch starts
                                                                           // with; -1: the slot's exchange buffers have to be (re)armed by a fill
   int hypothesis_width = 0;  // initialisations per launch: 0 automatic (1 while tracking holds, 8 once a first try has failed), 1 .. 8 fixed
@@ -1378,9 +1378,10 @@ struct dsopp_hip_aligner {
   // the loop are no-ops, but each still costs a dispatch)
   std::map<int, int> launches_needed;
   DeviceBuffer<int> d_rows;  // row counts / offsets of the device-side depth-map scan
-  int *h_level_totals = nullptr;  // pinned: point counts of the levels scanned by one ensureAllLevelPoints
+  PinnedMem<int> h_level_totals;  // point counts of the levels scanned by one ensureAllLevelPoints
   DeviceBuffer<AlignControl> d_ctrl;
   std::map<int64_t, Rigid> known_poses;
+  DeviceMem<double> dbg_dev;  // DSOPP_HIP_STAMPS builds: the partial sums of every pass (DSOPP_HIP_CHECK_SUMS)
 };
 
 namespace dsopp_hip {
@@ -1565,20 +1566,20 @@ void ensureAllLevelPoints(dsopp_hip_aligner *a, const dsopp_hip_depth_maps *maps
   }
   if (n_stale < 2) return;  // (one level: ensureLevelPoints does it as before)
   a->d_rows.reserve(rows_total, 0, st);
-  if (!a->h_level_totals) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&a->h_level_totals), DSOPP_HIP_MAX_LEVELS * sizeof(int), hipHostMallocDefault));
+  a->h_level_totals.reserve(DSOPP_HIP_MAX_LEVELS * sizeof(int));
   for (int i = 0; i < n_stale; ++i) {
     const int lvl = stale[i], W = pyramid->w(lvl), H = pyramid->h(lvl);
     int *row_count = a->d_rows.ptr + first_row[lvl], *row_offset = row_count + H;
     countDepthMapRowsKernel<<<H, 256, 0, st>>>(maps->idepth_sum[static_cast<size_t>(lvl)].ptr, maps->weight[static_cast<size_t>(lvl)].ptr, W, H, row_count);
     scanDepthMapRowsKernel<<<1, 256, 0, st>>>(row_count, H, row_offset);
-    HIP_CHECK(hipMemcpyAsync(a->h_level_totals + i, row_offset + H, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(a->h_level_totals.get() + i, row_offset + H, sizeof(int), hipMemcpyDeviceToHost, st));
   }
   HIP_CHECK(hipGetLastError());
   a->sr.sync();
   for (int i = 0; i < n_stale; ++i) {
     const int lvl = stale[i], W = pyramid->w(lvl), H = pyramid->h(lvl);
     dsopp_hip_depth_maps::LevelPoints &pts = maps->points[static_cast<size_t>(lvl)];
-    const int total = a->h_level_totals[i];
+    const int total = a->h_level_totals.get()[i];
     const size_t n = static_cast<size_t>(total);
     pts.u.reserve(std::max<size_t>(n, 1), 0, st);
     pts.v.reserve(std::max<size_t>(n, 1), 0, st);
@@ -1629,12 +1630,7 @@ void dsopp_hip_aligner_destroy(dsopp_hip_aligner *a) {
   if (!a) return;
   (void)hipSetDevice(a->sr.device);
   if (a->sr.stream) (void)hipStreamSynchronize(a->sr.stream);
-  if (a->h_ctrl) (void)hipHostFree(a->h_ctrl);
-  if (a->h_pyr_out) (void)hipHostFree(a->h_pyr_out);
-  if (a->h_level_totals) (void)hipHostFree(a->h_level_totals);
-  StreamRef sr = a->sr;
   delete a;
-  sr.destroy();
 }
 
 int dsopp_hip_aligner_reset(dsopp_hip_aligner *a) {
@@ -1844,8 +1840,8 @@ int dsopp_hip_aligner_solve(dsopp_hip_aligner *a, dsopp_hip_align_result *result
     prm.max_iterations = a->opt.max_iterations;
     prm.n_points = n;
     prm.n_blocks = n_blocks;
-    if (!a->h_ctrl) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&a->h_ctrl), 2 * sizeof(AlignControl), hipHostMallocDefault));
-    AlignControl &c = a->h_ctrl[0];
+    a->h_ctrl.reserve(2 * sizeof(AlignControl));
+    AlignControl &c = a->h_ctrl.get()[0];
     std::memset(&c, 0, sizeof(c));
     Rigid T_tr = rigidMul(rigidInverse(a->T_w_tgt), a->T_w_ref);  // eigen_pose_alignment.cpp:307-308
     if (a->have_rotation_prior)
@@ -1860,7 +1856,7 @@ int dsopp_hip_aligner_solve(dsopp_hip_aligner *a, dsopp_hip_align_result *result
     a->d_ctrl.upload(&c, 1, 0, st);  // pinned source: stream-ordered, no host wait
     const int total_launches = a->opt.max_iterations + 2;  // initial evaluation + one per iteration + final control pass
     int launch = 0;
-    AlignControl &h = a->h_ctrl[1];
+    AlignControl &h = a->h_ctrl.get()[1];
     const bool single_workgroup = n <= kAlignLoopMaxPoints && a->lm_path != 1;
     if (single_workgroup) {
       // the whole LM loop in one launch of one workgroup (alignLoopKernel): one enqueue, one read-back, one synchronisation
@@ -2049,10 +2045,9 @@ int dsopp_hip_aligner_estimate_pose(dsopp_hip_aligner *a, int64_t reference_time
         args.ab0[1] = affine_init[1];
         static_assert(kAlignPartial == 48, "kPyramidSetDoubles");
         a->d_pyr_partials.reserve(kPyramidHypotheses * kPyramidSetDoubles, 0, st);
-        if (!a->h_pyr_out)
-          HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&a->h_pyr_out), kPyramidHypotheses * sizeof(AlignPyramidResult), hipHostMallocDefault));
+        a->h_pyr_out.reserve(kPyramidHypotheses * sizeof(AlignPyramidResult));
         args.partials = a->d_pyr_partials.ptr;
-        args.out = a->h_pyr_out;  // pinned host memory: the kernel leaves its results there itself (no copy kernel behind it)
+        args.out = a->h_pyr_out.get();  // pinned host memory: the kernel leaves its results there itself (no copy kernel behind it)
         // every slot armed with the sentinel, the failed flag with the same (!= kPyramidFailed) pattern: one fill per hypothesis slot —
         // before its first launch and after a failed one only; a launch leaves the buffers armed for its successor (the pass counter
         // continues, the kernel re-arms by its rotation rule), which saves two fill kernels (10 us) per tracked frame
@@ -2067,12 +2062,11 @@ int dsopp_hip_aligner_estimate_pose(dsopp_hip_aligner *a, int64_t reference_time
         }
 #ifdef DSOPP_HIP_STAMPS
         static const bool check_sums = std::getenv("DSOPP_HIP_CHECK_SUMS") != nullptr;
-        static double *dbg_dev = nullptr;
         constexpr size_t kDbgDoubles = 256 * kPyramidMaxWorkgroups * 4;
         if (check_sums) {
-          if (!dbg_dev) HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg_dev), kDbgDoubles * sizeof(double)));
-          HIP_CHECK(hipMemsetAsync(dbg_dev, 0, kDbgDoubles * sizeof(double), st));
-          args.debug_sums = dbg_dev;
+          if (!a->dbg_dev) a->dbg_dev.alloc(kDbgDoubles * sizeof(double));
+          HIP_CHECK(hipMemsetAsync(a->dbg_dev.get(), 0, kDbgDoubles * sizeof(double), st));
+          args.debug_sums = a->dbg_dev.get();
         }
         static const bool poison = std::getenv("DSOPP_HIP_POISON_LDS") != nullptr;
         args.debug_poison_lds = poison ? 1 : 0;
@@ -2087,7 +2081,7 @@ int dsopp_hip_aligner_estimate_pose(dsopp_hip_aligner *a, int64_t reference_time
         a->sr.sync();
 #ifdef DSOPP_HIP_STAMPS
         if (std::getenv("DSOPP_HIP_TRACE")) {
-          const AlignPyramidResult &o = a->h_pyr_out[0];
+          const AlignPyramidResult &o = a->h_pyr_out.get()[0];
           auto us = [&](int i, int j) { return (o.stamps[j] - o.stamps[i]) / 100.0; };
           std::fprintf(stderr, "alignPyramid pass (level 0, wave 0 of workgroup 0): set-up %.2f  gather + point %.2f  rows + matrix cores %.2f  wave sums + barrier %.2f  "
                                "workgroup sum + publish %.2f  poll + quarter sums %.2f  barrier + total %.2f  control step %.2f  drain + barrier %.2f  = %.2f us (G = %d, one XCD: %d)\n",
@@ -2099,7 +2093,7 @@ int dsopp_hip_aligner_estimate_pose(dsopp_hip_aligner *a, int64_t reference_time
           // every workgroup has to derive the same totals in every pass (a difference is a stale or missed value in the exchange), and a
           // repeated call on the same inputs has to reproduce the first call's partial sums and totals bit for bit
           std::vector<double> dbg(kDbgDoubles);
-          HIP_CHECK(hipMemcpy(dbg.data(), dbg_dev, kDbgDoubles * sizeof(double), hipMemcpyDeviceToHost));
+          HIP_CHECK(hipMemcpy(dbg.data(), a->dbg_dev.get(), kDbgDoubles * sizeof(double), hipMemcpyDeviceToHost));
           static std::map<int, std::vector<double>> reference;  // by level count x participants
           for (int pass = 0; pass < 256; ++pass) {
             const double *row = dbg.data() + static_cast<size_t>(pass) * kPyramidMaxWorkgroups * 4;
@@ -2133,24 +2127,24 @@ int dsopp_hip_aligner_estimate_pose(dsopp_hip_aligner *a, int64_t reference_time
 #endif
         static const bool trace_levels = std::getenv("DSOPP_HIP_TRACE") != nullptr;  // debugging aid: what every level of hypothesis 0 did
         if (trace_levels) {
-          const AlignPyramidResult &o = a->h_pyr_out[0];
+          const AlignPyramidResult &o = a->h_pyr_out.get()[0];
           for (int lvl = levels - 1; lvl >= 0; --lvl)
             std::fprintf(stderr, "  level %d: %d points, %d iterations, n_valid %d, rmse %.12g (G = %d)\n", lvl, args.level[lvl].n_points, o.iterations[lvl],
                          o.n_valid[lvl], o.rmse[lvl], G);
         }
         for (int h = 0; h < nb; ++h)
-          if (a->h_pyr_out[h].failed) {
+          if (a->h_pyr_out.get()[h].failed) {
             a->pyramid_kernel_disabled = true;  // not all workgroups were resident in time: this GPU is busy with something else
             return;
           }
-        for (int h = 0; h < nb; ++h) a->pyr_phase[h] = a->h_pyr_out[h].end_phase;  // armed for a launch that continues the pass counter
+        for (int h = 0; h < nb; ++h) a->pyr_phase[h] = a->h_pyr_out.get()[h].end_phase;  // armed for a launch that continues the pass counter
         fast = true;
       });
       if (rc != DSOPP_HIP_OK) return rc;
       if (fast) {
         // the batch in the order of the sequential loop: the first success ends it
         for (int h = 0; h < nb && !success; ++h) {
-          const AlignPyramidResult &o = a->h_pyr_out[h];
+          const AlignPyramidResult &o = a->h_pyr_out.get()[h];
           ++tries;
           lm_iterations += o.lm_iterations;
           std::memcpy(T, T_world_target_init + 7 * (try_number + h), sizeof(T));

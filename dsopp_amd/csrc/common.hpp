@@ -1,4 +1,4 @@
-// Common host-side helpers of the HIP library: error reporting, RAII device buffers.
+// Common host-side helpers of the HIP library: error reporting, owners of device / pinned memory, events and streams.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,11 +170,76 @@ struct DeviceBuffer {
   }
 };
 
-/** owns (or borrows) a stream on a device */
+/** Owner of one HIP handle `h` (an allocation or an event), released with `Release` when the owner is destroyed or reset(); move-only */
+template <typename T, auto Release>
+struct Owned {
+  T h = nullptr;
+  Owned() = default;
+  Owned(const Owned &) = delete;
+  Owned &operator=(const Owned &) = delete;
+  Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+  Owned &operator=(Owned &&o) noexcept {
+    if (this != &o) {
+      reset();
+      h = o.h;
+      o.h = nullptr;
+    }
+    return *this;
+  }
+  ~Owned() { reset(); }
+  void reset() {
+    if (h) (void)Release(h);
+    h = nullptr;
+  }
+  explicit operator bool() const { return h != nullptr; }
+};
+
+/** pinned host memory (hipHostMallocDefault) that grows to what reserve() asks for and never shrinks; a growth does not keep the contents */
+template <typename T>
+struct PinnedMem : Owned<T *, hipHostFree> {
+  size_t bytes = 0;
+  void reset() {
+    Owned<T *, hipHostFree>::reset();
+    bytes = 0;
+  }
+  void reserve(size_t need) {
+    if (need <= bytes) return;
+    reset();
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&this->h), need, hipHostMallocDefault));
+    bytes = need;
+  }
+  T *get() const { return this->h; }
+};
+
+/** device memory of exactly the size asked for: none of DeviceBuffer's rounding, zero-fill or growth */
+template <typename T>
+struct DeviceMem : Owned<T *, hipFree> {
+  void alloc(size_t bytes) {
+    this->reset();
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&this->h), bytes));
+  }
+  T *get() const { return this->h; }
+};
+
+/** a HIP event, created by its first get() with the flags of that call site (hipEventDisableTiming unless it is timed) */
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+  hipEvent_t get(unsigned flags) {
+    if (!h) HIP_CHECK(hipEventCreateWithFlags(&h, flags));
+    return h;
+  }
+};
+
+/** a stream on a device: the caller's, borrowed, or one of its own that init() creates and the destructor destroys */
 struct StreamRef {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owned = false;
+  StreamRef() = default;
+  StreamRef(const StreamRef &) = delete;
+  StreamRef &operator=(const StreamRef &) = delete;
+  ~StreamRef() {
+    if (owned && stream) (void)hipStreamDestroy(stream);
+  }
   void init(int dev, void *user_stream) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
@@ -184,15 +249,15 @@ struct StreamRef {
     HIP_CHECK(hipSetDevice(dev));
     if (user_stream) {
       stream = static_cast<hipStream_t>(user_stream);
-      owned = false;
     } else {
       HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
       owned = true;
     }
   }
-  void destroy() {
-    if (owned && stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
+  /** the device and stream of `o`, which keeps owning the stream (a fresh StreamRef only) */
+  void borrow(const StreamRef &o) {
+    device = o.device;
+    stream = o.stream;
   }
   void use() const { HIP_CHECK(hipSetDevice(device)); }
   void sync() const { HIP_CHECK(hipStreamSynchronize(stream)); }

@@ -731,9 +731,8 @@ ImmatureSetPtr dsopp_hip::newImmatureSet(int device, void *stream, int32_t n, co
   s->d_flags.upload(fl.data(), 2 * N, 0, st);
   // the launch tables of the batched per-frame estimate (this set may be the one that leads a batch): allocated here, at
   // keyframe time, so that the per-frame call allocates nothing (a pinned allocation in its first call cost 0.1 ms)
-  HIP_CHECK(hipHostMalloc(&s->h_tables, sizeof(Tables), hipHostMallocDefault));
-  HIP_CHECK(hipEventCreateWithFlags(&s->tables_copied, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(s->tables_copied, st));
+  s->h_tables.reserve(sizeof(Tables));
+  HIP_CHECK(hipEventRecord(s->tables_copied.get(hipEventDisableTiming), st));
   s->d_tables.reserve(sizeof(Tables), 0, st);
   s->sr.sync();
   return s;
@@ -753,12 +752,7 @@ void dsopp_hip_immature_set_destroy(dsopp_hip_immature_set *s) {
   if (!s) return;
   (void)hipSetDevice(s->sr.device);
   if (s->sr.stream) (void)hipStreamSynchronize(s->sr.stream);
-  if (s->h_stage) (void)hipHostFree(s->h_stage);
-  if (s->h_tables) (void)hipHostFree(s->h_tables);
-  if (s->tables_copied) (void)hipEventDestroy(s->tables_copied);
-  StreamRef sr = s->sr;
   delete s;
-  sr.destroy();
 }
 
 int dsopp_hip_immature_set_upload_state(dsopp_hip_immature_set *s, const double *idepth_min, const double *idepth_max, const double *uniqueness,
@@ -793,13 +787,8 @@ int dsopp_hip_immature_set_download_state(dsopp_hip_immature_set *s, double *ide
     // two contiguous copies into pinned staging (the state planes are adjacent on the device), then a host-side scatter:
     // six pageable copies cost six staged transfers
     const size_t bytes = 4 * N * sizeof(double) + 2 * N;
-    if (s->h_stage_bytes < bytes) {
-      if (s->h_stage) (void)hipHostFree(s->h_stage);
-      s->h_stage = nullptr;
-      HIP_CHECK(hipHostMalloc(&s->h_stage, bytes, hipHostMallocDefault));
-      s->h_stage_bytes = bytes;
-    }
-    double *hd = static_cast<double *>(s->h_stage);
+    s->h_stage.reserve(bytes);
+    double *hd = static_cast<double *>(s->h_stage.get());
     uint8_t *hf = reinterpret_cast<uint8_t *>(hd + 4 * N);
     s->d_io.download(hd, 4 * N, 0, st);
     s->d_flags.download(hf, 2 * N, 0, st);
@@ -889,14 +878,9 @@ int dsopp_hip_immature_sets_estimate(int32_t n_sets, dsopp_hip_immature_set *con
       else
         estimateDepthsBatchArgKernel<float><<<grid, 64, smem, st>>>(t);
     } else {
-      if (!lead->h_tables) {  // (sets created before the tables moved into dsopp_hip_immature_set_create)
-        HIP_CHECK(hipHostMalloc(&lead->h_tables, sizeof(Tables), hipHostMallocDefault));
-        HIP_CHECK(hipEventCreateWithFlags(&lead->tables_copied, hipEventDisableTiming));
-      } else {
-        HIP_CHECK(hipEventSynchronize(lead->tables_copied));  // the pinned table is about to be rewritten
-      }
+      HIP_CHECK(hipEventSynchronize(lead->tables_copied.h));  // the pinned table is about to be rewritten
       lead->d_tables.reserve(sizeof(Tables), 0, st);
-      Tables &t = *static_cast<Tables *>(lead->h_tables);
+      Tables &t = *static_cast<Tables *>(lead->h_tables.get());
       for (int k = 0; k < n_sets; ++k) {
         dsopp_hip_immature_set *s = sets[k];
         if (s->sr.stream != st) HIP_CHECK(hipStreamSynchronize(s->sr.stream));  // earlier work on that set's own stream
@@ -905,7 +889,7 @@ int dsopp_hip_immature_sets_estimate(int32_t n_sets, dsopp_hip_immature_set *con
         t.l[k] = landmarkPointers(s);
       }
       HIP_CHECK(hipMemcpyAsync(lead->d_tables.ptr, &t, sizeof(Tables), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipEventRecord(lead->tables_copied, st));
+      HIP_CHECK(hipEventRecord(lead->tables_copied.h, st));
       const DepthFrame *df = reinterpret_cast<const DepthFrame *>(lead->d_tables.ptr);
       const DepthLandmarks *dl = reinterpret_cast<const DepthLandmarks *>(lead->d_tables.ptr + offsetof(Tables, l));
       const size_t smem = static_cast<size_t>(t.f[0].max_line) * sizeof(double);

@@ -23,27 +23,15 @@ struct dsopp_hip_depth_maps {
     dsopp_hip::DeviceBuffer<double> u, v, idepth, intensity;
     // recorded by the extracting stream behind the compaction: a consumer on ANOTHER stream (the optical-flow measure runs on the maps' own)
     // orders itself behind it
-    hipEvent_t ready = nullptr;
+    dsopp_hip::Event ready;
     hipStream_t ordered = nullptr;  // the consumer stream that has already been ordered behind `ready` (one wait per extraction, not per frame)
-    LevelPoints() = default;
-    LevelPoints(const LevelPoints &) = delete;
-    LevelPoints &operator=(const LevelPoints &) = delete;
-    LevelPoints(LevelPoints &&o) noexcept
-        : n(o.n), pyramid(o.pyramid), u(std::move(o.u)), v(std::move(o.v)), idepth(std::move(o.idepth)), intensity(std::move(o.intensity)), ready(o.ready), ordered(o.ordered) {
-      o.ready = nullptr;
-      o.n = -1;
-    }
-    ~LevelPoints() {
-      if (ready) (void)hipEventDestroy(ready);
-    }
     void markReady(hipStream_t producer) {
-      if (!ready) HIP_CHECK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(ready, producer));
+      HIP_CHECK(hipEventRecord(ready.get(hipEventDisableTiming), producer));
       ordered = producer;
     }
     void orderBehind(hipStream_t consumer) {
       if (!ready || ordered == consumer) return;
-      HIP_CHECK(hipStreamWaitEvent(consumer, ready, 0));
+      HIP_CHECK(hipStreamWaitEvent(consumer, ready.h, 0));
       ordered = consumer;
     }
   };
@@ -51,11 +39,5 @@ struct dsopp_hip_depth_maps {
   mutable dsopp_hip::DeviceBuffer<double> flow_scratch;  // per-workgroup partials of the optical-flow measure
   // its result, in pinned host memory the closing workgroup writes itself (the tracker asks for the flow on every frame: a 16-byte copy into
   // the caller's pageable array was a staged transfer — a copy kernel, 20 us inside hipMemcpyAsync and a second wait)
-  mutable double *h_flow = nullptr;
-  dsopp_hip_depth_maps() = default;
-  dsopp_hip_depth_maps(const dsopp_hip_depth_maps &) = delete;
-  dsopp_hip_depth_maps &operator=(const dsopp_hip_depth_maps &) = delete;
-  ~dsopp_hip_depth_maps() {
-    if (h_flow) (void)hipHostFree(h_flow);
-  }
+  mutable dsopp_hip::PinnedMem<double> h_flow;
 };

@@ -159,26 +159,6 @@ __global__ void __launch_bounds__(kBlock) buildImmatureKernel(const int *__restr
 
 inline unsigned gridFor(long n) { return static_cast<unsigned>(std::max<long>(1, (n + kBlock - 1) / kBlock)); }
 
-/** a pinned host buffer that grows (never shrinks) */
-struct Pinned {
-  void *ptr = nullptr;
-  size_t bytes = 0;
-  void reserve(size_t b) {
-    if (b <= bytes) return;
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    HIP_CHECK(hipHostMalloc(&ptr, b, hipHostMallocDefault));
-    bytes = b;
-  }
-  ~Pinned() {
-    if (ptr) (void)hipHostFree(ptr);
-  }
-  template <typename T>
-  T *as() const {
-    return static_cast<T *>(ptr);
-  }
-};
-
 /** The threshold update of the reference (calculateThreshold, sobel_tracking_features_extractor.cpp:26-29), int / int
  *  divisions included.  Where the reference is undefined (a zero divisor: SIGFPE on x86; a non-finite or out-of-range quotient)
  *  the threshold is kept: the one deliberate deviation. */
@@ -209,9 +189,11 @@ struct dsopp_hip_feature_extractor {
   DeviceBuffer<unsigned> d_hist;
   DeviceBuffer<int> d_hit, d_list, d_count, d_final;  // per-window hit | hits in window order | their count | the returned list
   DeviceBuffer<char> d_temp;                          // device select scratch
-  Pinned h_image, h_count, h_list, h_hist, h_final;
+  PinnedMem<uint8_t> h_image;
+  PinnedMem<int> h_count, h_list, h_final;
+  PinnedMem<unsigned> h_hist;
   std::vector<int> final_list;  // the returned list as pixel indices y * W + x (host copy)
-  hipEvent_t final_ready = nullptr;  // d_final written (recorded behind its upload)
+  Event final_ready;            // d_final written (recorded behind its upload)
 };
 
 extern "C" {
@@ -249,7 +231,7 @@ int dsopp_hip_feature_extractor_create(int device, void *stream, int width, int 
     ex->d_count.reserve(1, 0, st);
     ex->h_image.reserve(n);
     ex->h_count.reserve(sizeof(int));
-    HIP_CHECK(hipEventCreateWithFlags(&ex->final_ready, hipEventDisableTiming));
+    (void)ex->final_ready.get(hipEventDisableTiming);
     ex->sr.sync();
     *out = ex.release();
   });
@@ -259,10 +241,7 @@ void dsopp_hip_feature_extractor_destroy(dsopp_hip_feature_extractor *ex) {
   if (!ex) return;
   (void)hipSetDevice(ex->sr.device);
   if (ex->sr.stream) (void)hipStreamSynchronize(ex->sr.stream);
-  if (ex->final_ready) (void)hipEventDestroy(ex->final_ready);
-  StreamRef sr = ex->sr;
   delete ex;
-  sr.destroy();
 }
 
 int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const uint8_t *mask_host) {
@@ -295,8 +274,8 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
     hipStream_t st = ex->sr.stream;
     const int W = ex->width, H = ex->height, N = W * H;
     // the caller's image leaves from pinned memory (the stream is idle here: every call ends with a synchronisation)
-    std::memcpy(ex->h_image.ptr, image_host, static_cast<size_t>(N));
-    HIP_CHECK(hipMemcpyAsync(ex->d_image.ptr, ex->h_image.ptr, static_cast<size_t>(N), hipMemcpyHostToDevice, st));
+    std::memcpy(ex->h_image.get(), image_host, static_cast<size_t>(N));
+    HIP_CHECK(hipMemcpyAsync(ex->d_image.ptr, ex->h_image.get(), static_cast<size_t>(N), hipMemcpyHostToDevice, st));
 
     // everything below is computed into locals and committed at the end: a failed call leaves the state as it was
     bool initialized = ex->initialized;
@@ -307,11 +286,11 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
       sobelKernel<true><<<std::min(gridFor(N), 256u), kBlock, 0, st>>>(ex->d_image.ptr, W, H, ex->d_grad.ptr, ex->d_hist.ptr);
       HIP_CHECK(hipGetLastError());
       ex->h_hist.reserve(kGradBins * sizeof(unsigned));
-      HIP_CHECK(hipMemcpyAsync(ex->h_hist.ptr, ex->d_hist.ptr, kGradBins * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(ex->h_hist.get(), ex->d_hist.ptr, kGradBins * sizeof(unsigned), hipMemcpyDeviceToHost, st));
       ex->sr.sync();
       // quantile(): nth_element at k = (long)(size * q) — the k-th smallest norm, read off the cumulative histogram
       const long k = static_cast<long>(static_cast<double>(N) * ex->quantile);
-      const unsigned *h = ex->h_hist.as<unsigned>();
+      const unsigned *h = ex->h_hist.get();
       long cum = 0;
       thr = kGradBins - 1;
       for (int b = 0; b < kGradBins; ++b) {
@@ -344,9 +323,9 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
       HIP_CHECK(hipcub::DeviceSelect::If(nullptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
       ex->d_temp.reserve(std::max<size_t>(1, temp_bytes), 0, st);
       HIP_CHECK(hipcub::DeviceSelect::If(ex->d_temp.ptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
-      HIP_CHECK(hipMemcpyAsync(ex->h_count.ptr, ex->d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(ex->h_count.get(), ex->d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
       ex->sr.sync();
-      found = *ex->h_count.as<int>();
+      found = *ex->h_count.get();
     }
 
     // truncation to (long)density after the shuffle (:128-131)
@@ -362,9 +341,9 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
     std::vector<int> final_list(static_cast<size_t>(needed));
     if (needed > 0) {
       ex->h_list.reserve(static_cast<size_t>(found) * sizeof(int));
-      HIP_CHECK(hipMemcpyAsync(ex->h_list.ptr, ex->d_list.ptr, static_cast<size_t>(found) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(ex->h_list.get(), ex->d_list.ptr, static_cast<size_t>(found) * sizeof(int), hipMemcpyDeviceToHost, st));
       ex->sr.sync();
-      const int *list = ex->h_list.as<int>();
+      const int *list = ex->h_list.get();
       for (long i = 0; i < needed; ++i) {
         const int idx = list[perm[static_cast<size_t>(i)]];
         final_list[static_cast<size_t>(i)] = idx;
@@ -374,10 +353,10 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
       // the list stays on the device for the immature-landmark build (the stream is idle: the pinned buffer's last upload is done)
       ex->d_final.reserve(static_cast<size_t>(needed), 0, st);
       ex->h_final.reserve(static_cast<size_t>(needed) * sizeof(int));
-      std::memcpy(ex->h_final.ptr, final_list.data(), static_cast<size_t>(needed) * sizeof(int));
-      HIP_CHECK(hipMemcpyAsync(ex->d_final.ptr, ex->h_final.ptr, static_cast<size_t>(needed) * sizeof(int), hipMemcpyHostToDevice, st));
+      std::memcpy(ex->h_final.get(), final_list.data(), static_cast<size_t>(needed) * sizeof(int));
+      HIP_CHECK(hipMemcpyAsync(ex->d_final.ptr, ex->h_final.get(), static_cast<size_t>(needed) * sizeof(int), hipMemcpyHostToDevice, st));
     }
-    HIP_CHECK(hipEventRecord(ex->final_ready, st));
+    HIP_CHECK(hipEventRecord(ex->final_ready.h, st));
 
     ex->initialized = initialized;
     ex->threshold = thr;
@@ -416,7 +395,7 @@ int dsopp_hip_immature_set_create_from_features(int device, void *stream, const 
     hipStream_t st = s->sr.stream;
     if (kept > 0) {
       pyramid->waitReady(st);
-      if (st != ex->sr.stream) HIP_CHECK(hipStreamWaitEvent(st, ex->final_ready, 0));
+      if (st != ex->sr.stream) HIP_CHECK(hipStreamWaitEvent(st, ex->final_ready.h, 0));
       DeviceBuffer<int> pos;
       DeviceBuffer<char> temp;
       pos.reserve(static_cast<size_t>(n_list), 0, st);
@@ -428,11 +407,11 @@ int dsopp_hip_immature_set_create_from_features(int device, void *stream, const 
       const double cx = intrinsics[2], cy = intrinsics[3], ifx = 1.0 / intrinsics[0], ify = 1.0 / intrinsics[1];
       if (pyramid->dtype == DSOPP_HIP_F64)
         buildImmatureKernel<double><<<gridFor(n_list), kBlock, 0, st>>>(ex->d_final.ptr, pos.ptr, n_list, W, H,
-                                                                        static_cast<const Texel<double> *>(pyramid->texels[0]), cx, cy, ifx, ify, kept,
+                                                                        static_cast<const Texel<double> *>(pyramid->texels[0].get()), cx, cy, ifx, ify, kept,
                                                                         s->d_in.ptr);
       else
         buildImmatureKernel<float><<<gridFor(n_list), kBlock, 0, st>>>(ex->d_final.ptr, pos.ptr, n_list, W, H,
-                                                                       static_cast<const Texel<float> *>(pyramid->texels[0]), cx, cy, ifx, ify, kept,
+                                                                       static_cast<const Texel<float> *>(pyramid->texels[0].get()), cx, cy, ifx, ify, kept,
                                                                        s->d_in.ptr);
       HIP_CHECK(hipGetLastError());
       s->sr.sync();  // (the scratch above is freed on return)

@@ -13,11 +13,10 @@ struct dsopp_hip_immature_set {
   dsopp_hip::DeviceBuffer<double> d_in;      // projection 2n | direction 3n | patch 8n | gradient 2n
   dsopp_hip::DeviceBuffer<double> d_io;      // idepth_min | idepth_max | uniqueness | search_pixel_interval
   dsopp_hip::DeviceBuffer<uint8_t> d_flags;  // status | traced
-  void *h_stage = nullptr;                   // pinned read-back staging
-  size_t h_stage_bytes = 0;
-  void *h_tables = nullptr;                  // pinned descriptor tables of a batched estimate led by this set
+  dsopp_hip::PinnedMem<void> h_stage;       // read-back staging
+  dsopp_hip::PinnedMem<void> h_tables;      // descriptor tables of a batched estimate led by this set
   dsopp_hip::DeviceBuffer<char> d_tables;
-  hipEvent_t tables_copied = nullptr;        // the previous batch's table upload has left the pinned buffer
+  dsopp_hip::Event tables_copied;            // the previous batch's table upload has left the pinned buffer
 };
 
 namespace dsopp_hip {

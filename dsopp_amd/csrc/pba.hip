@@ -112,11 +112,11 @@ struct dsopp_hip_window {
     static const int override_chunks = std::getenv("DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS") ? std::atoi(std::getenv("DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS")) : 0;  // tuning aid
     return override_chunks > 0 ? override_chunks : twoStageMinChunks();
   }
-  unsigned *d_bs_flag = nullptr;  // ticket counter + hand-over buffers of the back-substitution inside the solve launch (pba_solve_combined.hpp)
+  DeviceMem<unsigned> d_bs_flag;  // ticket counter + hand-over buffers of the back-substitution inside the solve launch (pba_solve_combined.hpp)
   unsigned bs_seq = 0, bs_ticket_base = 0;
-  int *h_bs_fault = nullptr;  // pinned: raised by a landmark workgroup of the solve launch whose bounded wait for the step ran out (checkSolveLaunchFault)
-  long long *dbg_stamps = nullptr;
-  long long *dbg_sweep = nullptr;
+  PinnedMem<int> h_bs_fault;  // raised by a landmark workgroup of the solve launch whose bounded wait for the step ran out (checkSolveLaunchFault)
+  DeviceMem<long long> dbg_stamps;
+  DeviceMem<long long> dbg_sweep;
   bool dbg_sweep_lin = true;
   DeviceBuffer<LmControl> d_ctrl;
   const LmControl *fused_final_ctrl = nullptr;  // control block the enqueued fused loop ends in
@@ -147,25 +147,23 @@ struct dsopp_hip_window {
   std::vector<FrameDev> h_frames;     // the frame table as last uploaded (what such a patch starts from)
   bool state_dirty = true;   // host mirror newer than device
   bool host_stale = false;   // device state newer than the host mirror (after a device-driven solve): see downloadState
-  LmControl *h_ctrl = nullptr;  // pinned read-back buffer of the solve result
-  void *h_uncertainty = nullptr;          // pinned destination of estimateUncertainty's systems (+ frame states)
-  size_t h_uncertainty_bytes = 0;
-  hipEvent_t uncertainty_ready = nullptr; // recorded behind that transfer
+  PinnedMem<LmControl> h_ctrl;   // read-back buffer of the solve result
+  PinnedMem<void> h_uncertainty;  // destination of estimateUncertainty's systems (+ frame states)
+  Event uncertainty_ready;        // recorded behind that transfer
   bool restore_in_begin = false;      // optimize_repeated: the restore to the snapshot rides in the next solve's opening kernel
   DeviceBuffer<LmControl> d_results;  // optimize_repeated: one result slot per solve of a batch ...
-  LmControl *h_results = nullptr;     // ... fetched together into pinned memory
+  PinnedMem<LmControl> h_results;     // ... fetched together into pinned memory
   LmControl *result_device = nullptr; // set while such a solve is enqueued: where its closing kernel leaves the control block
   DeviceBuffer<SelectState> d_select;   // radix-select state of updatePointStatuses
   DeviceBuffer<double> d_pair_dist;     // camera-centre distances of all frame pairs
   DeviceBuffer<double> d_export;        // packed per-frame read-back (get_frame_update): 4 n doubles, then (1 + targets) n bytes
-  void *h_export = nullptr;             // its pinned host staging
-  size_t h_export_bytes = 0;
+  PinnedMem<void> h_export;             // its pinned host staging
   // Pinned bump allocator for the per-keyframe uploads (landmarks, connection statuses, flags): the caller's arrays are
   // copied here and leave with asynchronous transfers, so set_landmarks / set_connection need no synchronisation of their own.
   // When the ring wraps the stream is synchronised once (every transfer that read the old contents has finished then).
   struct StageRing {
-    char *base = nullptr;
-    size_t capacity = 0, offset = 0;
+    PinnedMem<char> mem;
+    size_t offset = 0;
   } stage;
   // Appends of a keyframe step (dsopp_hip_window_set_landmarks / _set_connection: ~120 calls per keyframe from the tracker, each of which used
   // to cost one or more pinned-ring copies and a small kernel — 0.6 ms of host time per keyframe in the native driver, rocprofv3 --hip-trace,
@@ -193,8 +191,7 @@ struct dsopp_hip_window {
   };
   std::vector<ExportEntry> export_entries;
   DeviceBuffer<double> d_update;
-  void *h_update = nullptr;
-  size_t h_update_bytes = 0;
+  PinnedMem<void> h_update;
   bool export_valid = false;
   // device buffers of keyframes / connections that left the window, kept for the next keyframe: a new keyframe needs ~12
   // landmark arrays and 12 connection tables of 5 arrays each — about 70 hipMallocs (0.5 ms) when allocated afresh
@@ -222,7 +219,7 @@ struct dsopp_hip_window {
   std::vector<double> last_step;
   float last_solve_ms = 0;
   bool solve_events_pending = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Event ev0, ev1;
   dsopp_hip_allreduce_fn allreduce = nullptr;
   void *allreduce_user = nullptr;
   int rank = 0, world = 1;
@@ -230,10 +227,10 @@ struct dsopp_hip_window {
   bool profiling = false;
   struct TimedLaunch {
     int cls;
-    hipEvent_t a, b;
+    Event a, b;
   };
   std::vector<TimedLaunch> timed;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<Event> event_pool;
   double prof_ms[DSOPP_HIP_NUM_KERNEL_CLASSES] = {0};
   int64_t prof_count[DSOPP_HIP_NUM_KERNEL_CLASSES] = {0};
   // device-side snapshot of the mutable solver state (bench loops / tracker retries): see dsopp_hip_window_snapshot
@@ -265,14 +262,14 @@ using W = dsopp_hip_window;
 int nativeAllreduce(void *user, void *device_buffer, size_t count, void *stream);  // comm.hip
 namespace {
 
-hipEvent_t takeEvent(W &w) {
+Event takeEvent(W &w) {
+  Event e;
   if (!w.event_pool.empty()) {
-    hipEvent_t e = w.event_pool.back();
+    e = std::move(w.event_pool.back());
     w.event_pool.pop_back();
-    return e;
+  } else {
+    (void)e.get(hipEventDefault);
   }
-  hipEvent_t e;
-  HIP_CHECK(hipEventCreate(&e));
   return e;
 }
 
@@ -283,11 +280,11 @@ void timedLaunch(W &w, int cls, Body &&body) {
     body();
     return;
   }
-  hipEvent_t a = takeEvent(w), b = takeEvent(w);
-  HIP_CHECK(hipEventRecord(a, w.sr.stream));
+  Event a = takeEvent(w), b = takeEvent(w);
+  HIP_CHECK(hipEventRecord(a.h, w.sr.stream));
   body();
-  HIP_CHECK(hipEventRecord(b, w.sr.stream));
-  w.timed.push_back({cls, a, b});
+  HIP_CHECK(hipEventRecord(b.h, w.sr.stream));
+  w.timed.push_back({cls, std::move(a), std::move(b)});
 }
 
 void collectTimings(W &w) {
@@ -295,11 +292,11 @@ void collectTimings(W &w) {
   w.sr.sync();
   for (auto &t : w.timed) {
     float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t.a, t.b));
+    HIP_CHECK(hipEventElapsedTime(&ms, t.a.h, t.b.h));
     w.prof_ms[t.cls] += ms;
     w.prof_count[t.cls] += 1;
-    w.event_pool.push_back(t.a);
-    w.event_pool.push_back(t.b);
+    w.event_pool.push_back(std::move(t.a));
+    w.event_pool.push_back(std::move(t.b));
   }
   w.timed.clear();
 }
@@ -428,36 +425,30 @@ void ensureLandmarkCapacity(W &w, HostFrame &f, int n) {
 }
 
 /** pinned read-back buffers grow geometrically (a window gains landmarks with every keyframe: sized exactly, the per-keyframe read-backs
- *  paid a hipHostFree + hipHostMalloc — 0.17 ms — at every keyframe of the native driver; rocprofv3 --hip-trace, profiles/r06) */
-void growPinned(void *&ptr, size_t &have, size_t need) {
-  if (have >= need) return;
-  if (ptr) (void)hipHostFree(ptr);
-  ptr = nullptr;
-  size_t cap = std::max<size_t>(have, size_t(1) << 16);
+ *  paid a pinned free and allocation — 0.17 ms — at every keyframe of the native driver; rocprofv3 --hip-trace, profiles/r06) */
+void reserveGeometric(PinnedMem<void> &buf, size_t need) {
+  if (need <= buf.bytes) return;
+  size_t cap = std::max<size_t>(buf.bytes, size_t(1) << 16);
   while (cap < need) cap *= 2;
-  HIP_CHECK(hipHostMalloc(&ptr, cap, hipHostMallocDefault));
-  have = cap;
+  buf.reserve(cap);
 }
 
 /** `bytes` of pinned staging whose previous contents are no longer in flight */
 void *stageAcquire(W &w, size_t bytes) {
   bytes = (bytes + 63) & ~static_cast<size_t>(63);
-  if (bytes > w.stage.capacity) {
-    if (w.stage.base) {
+  if (bytes > w.stage.mem.bytes) {
+    if (w.stage.mem) {
       w.sr.sync();
-      (void)hipHostFree(w.stage.base);
-      w.stage.base = nullptr;
+      w.stage.mem.reset();
     }
-    const size_t cap = std::max<size_t>(bytes * 2, size_t(1) << 21);
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.stage.base), cap, hipHostMallocDefault));
-    w.stage.capacity = cap;
+    w.stage.mem.reserve(std::max<size_t>(bytes * 2, size_t(1) << 21));
     w.stage.offset = 0;
   }
-  if (w.stage.offset + bytes > w.stage.capacity) {
+  if (w.stage.offset + bytes > w.stage.mem.bytes) {
     w.sr.sync();
     w.stage.offset = 0;
   }
-  void *p = w.stage.base + w.stage.offset;
+  void *p = w.stage.mem.get() + w.stage.offset;
   w.stage.offset += bytes;
   return p;
 }
@@ -970,7 +961,7 @@ void launchSweepTyped(W &w, bool lin, bool huber, bool for_marg, const LmControl
   prm.gate_on_pending = ex.gate_on_pending ? 1 : 0;
   prm.run_flag = ex.run_flag;
   prm.external_backsub = ex.external_backsub ? 1 : 0;
-  prm.dbg = (w.dbg_sweep && lin == w.dbg_sweep_lin) ? w.dbg_sweep : nullptr;
+  prm.dbg = (w.dbg_sweep && lin == w.dbg_sweep_lin) ? w.dbg_sweep.get() : nullptr;
   dim3 grid(static_cast<unsigned>(w.n_sweep_blocks)), block(kSweepThreads);
   hipStream_t st = w.sr.stream;
   const FrameDev *fr = w.d_frames.ptr;
@@ -1101,7 +1092,7 @@ void launchReduceSchur(W &w, bool for_marg, const LmControl *ctrl, const FusedRe
   if (fused) a.prm = fused->prm;
   if (fused && fused->scalars) a.scalars = fused->scalars;
   a.ctrl_host = fused ? fused->ctrl_host : nullptr;
-  a.dbg = w.dbg_stamps ? w.dbg_stamps + 24 : nullptr;
+  a.dbg = w.dbg_stamps ? w.dbg_stamps.get() + 24 : nullptr;
   const size_t decide_smem = kDecideSmemBytes;
   if (mode == ReduceMode::kDecideOnly) {
     timedLaunch(w, DSOPP_HIP_KERNEL_ACCEPT,
@@ -1134,7 +1125,7 @@ SolveArgs makeSolveArgs(W &w) {
   a.Hsc = w.dHsc();
   a.bsc = w.dbsc();
   a.use_marginal = w.marg_nonzero ? 1 : 0;
-  a.dbg_stamps = w.dbg_stamps;
+  a.dbg_stamps = w.dbg_stamps.get();
   a.Hm = w.d_Hm.ptr;
   a.bm = w.d_bm.ptr;
   a.step = w.d_step.ptr;
@@ -1201,7 +1192,7 @@ void launchTwoStage(W &w, const LmControl *ctrl, int ublk_parity, double lambda,
   a.pc = w.d_pc.ptr;
   a.schur_table = w.d_schur_table.ptr;
   a.partials = w.d_partials.ptr;
-  a.dbg = w.dbg_stamps ? w.dbg_stamps + 32 : nullptr;
+  a.dbg = w.dbg_stamps ? w.dbg_stamps.get() + 32 : nullptr;
   a.pair_first_block = w.d_pair_first.ptr;
   a.pair_num_blocks = w.d_pair_count.ptr;
   a.ctrl = ctrl;
@@ -1273,25 +1264,25 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
       if (!w.d_bs_flag) {
         // [ticket counter | pad] + two hand-over buffers of kBlk * kMaxFrames doubles, both armed
         constexpr size_t kHand = static_cast<size_t>(kBlk) * kMaxFrames;
-        HIP_CHECK(hipMalloc(&w.d_bs_flag, 16 + 2 * kHand * sizeof(double)));
+        w.d_bs_flag.alloc(16 + 2 * kHand * sizeof(double));
         std::vector<double> arm(2 * kHand, kHandOverSentinel());
-        HIP_CHECK(hipMemsetAsync(w.d_bs_flag, 0, 16, w.sr.stream));
-        HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
+        HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, 16, w.sr.stream));
+        HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag.get()) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
         HIP_CHECK(hipStreamSynchronize(w.sr.stream));  // (`arm` is a pageable host buffer)
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.h_bs_fault), sizeof(int), hipHostMallocDefault));
-        *w.h_bs_fault = 0;
+        w.h_bs_fault.reserve(sizeof(int));
+        *w.h_bs_fault.get() = 0;
       }
       {
         constexpr size_t kHand = static_cast<size_t>(kBlk) * kMaxFrames;
-        double *hand = reinterpret_cast<double *>(reinterpret_cast<char *>(w.d_bs_flag) + 16);
+        double *hand = reinterpret_cast<double *>(reinterpret_cast<char *>(w.d_bs_flag.get()) + 16);
         const unsigned n = w.bs_seq;
-        a.bs_ticket = w.d_bs_flag;
+        a.bs_ticket = w.d_bs_flag.get();
         a.bs_hand = hand + (n & 1u) * kHand;
         a.bs_hand_next = hand + ((n + 1) & 1u) * kHand;
       }
       a.bs_parity = ublk_parity;
       a.bs_ticket_base = w.bs_ticket_base;  // (both mirrors advance behind the launch, once it is known to have been accepted)
-      a.bs_fault = w.h_bs_fault;
+      a.bs_fault = w.h_bs_fault.get();
     }
   }
   a.frames = w.d_frames.ptr;
@@ -1316,7 +1307,7 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
   a.F = w.F();
   a.fej = w.fej() ? 1 : 0;
   a.use_marginal = w.marg_nonzero ? 1 : 0;
-  a.dbg_stamps = w.dbg_stamps;
+  a.dbg_stamps = w.dbg_stamps.get();
   timedLaunch(w, DSOPP_HIP_KERNEL_ASSEMBLE_SOLVE,
               [&] {
                 if (w.F() > 8)
@@ -1348,12 +1339,12 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
  *  depths of that round were not back-substituted and the solve's result is not the algorithm's: the hand-over state is rebuilt and the
  *  call fails (the window stays usable). */
 void checkSolveLaunchFault(W &w) {
-  if (!w.h_bs_fault || !*w.h_bs_fault) return;
-  *w.h_bs_fault = 0;
+  if (!w.h_bs_fault || !*w.h_bs_fault.get()) return;
+  *w.h_bs_fault.get() = 0;
   constexpr size_t kHand = static_cast<size_t>(kBlk) * kMaxFrames;
   std::vector<double> arm(2 * kHand, kHandOverSentinel());
-  HIP_CHECK(hipMemsetAsync(w.d_bs_flag, 0, 16, w.sr.stream));
-  HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
+  HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, 16, w.sr.stream));
+  HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag.get()) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
   HIP_CHECK(hipStreamSynchronize(w.sr.stream));
   w.bs_seq = 0;
   w.bs_ticket_base = 0;
@@ -1652,8 +1643,8 @@ void lmSolveFusedEnqueue(W &w) {
     } else if (r + 1 == rounds) {
       // the closing round only takes the decision for the last candidate (its sweep was residual-only: no system to build) and
       // leaves the solve's result in pinned host memory itself (a copy kernel behind it cost 4 us per solve)
-      if (!w.h_ctrl) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.h_ctrl), sizeof(LmControl), hipHostMallocDefault));
-      fr.ctrl_host = w.result_device ? w.result_device : w.h_ctrl;  // (batched solves: a device slot, fetched with the batch)
+      w.h_ctrl.reserve(sizeof(LmControl));
+      fr.ctrl_host = w.result_device ? w.result_device : w.h_ctrl.get();  // (batched solves: a device slot, fetched with the batch)
       result_written_by_kernel = true;
       if (large) {
         // tens of thousands of sweep blocks: their scalars in 64 fixed groups first (every workgroup of the decision adds 64 x 4
@@ -1679,12 +1670,12 @@ void lmSolveFusedEnqueue(W &w) {
   w.pair_valid = false;
   // one small read-back into pinned memory (a pageable destination makes the copy synchronous and staged); the host
   // mirror of the frame states is refreshed lazily, by the first reader (downloadState)
-  if (!w.h_ctrl) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.h_ctrl), sizeof(LmControl), hipHostMallocDefault));
+  w.h_ctrl.reserve(sizeof(LmControl));
   if (!result_written_by_kernel) {
     if (w.result_device)  // batched solves of a sharded window: the slot is filled by a copy behind the closing round
       HIP_CHECK(hipMemcpyAsync(w.result_device, cfin, sizeof(LmControl), hipMemcpyDeviceToDevice, st));
     else
-      HIP_CHECK(hipMemcpyAsync(w.h_ctrl, cfin, sizeof(LmControl), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(w.h_ctrl.get(), cfin, sizeof(LmControl), hipMemcpyDeviceToHost, st));
   }
   w.host_stale = true;
   w.fused_final_ctrl = cfin;
@@ -1696,7 +1687,7 @@ void lmSolveFusedFinish(W &w, double &energy_out, int &iterations, int &n_valid_
   const LmControl *cfin = w.fused_final_ctrl;
   w.sr.sync();  // the only host synchronisation of the solve (unless the last step was rejected, below)
   checkSolveLaunchFault(w);
-  if (w.h_ctrl->need_final_setup) {
+  if (w.h_ctrl.get()->need_final_setup) {
     // closing problem.calculateEnergy() at the final state: the last sweep already evaluated it unless the last step was
     // rejected — then the pair constants are rebuilt and a residual sweep re-evaluates energies / candidate statuses
     ensurePairConstants(w);
@@ -1706,9 +1697,9 @@ void lmSolveFusedFinish(W &w, double &energy_out, int &iterations, int &n_valid_
   }
   (void)st;
   (void)cfin;
-  energy_out = w.h_ctrl->energy;
-  iterations = w.h_ctrl->iteration;
-  n_valid_out = w.h_ctrl->n_valid;
+  energy_out = w.h_ctrl.get()->energy;
+  iterations = w.h_ctrl.get()->iteration;
+  n_valid_out = w.h_ctrl.get()->n_valid;
 }
 
 void lmSolveFused(W &w, double &energy_out, int &iterations, int &n_valid_out) {
@@ -1918,12 +1909,12 @@ bool estimateUncertaintyEnqueue(W &w, bool force_state) {
   const bool want_state = force_state || (w.host_stale && !w.state_dirty);
   const size_t bytes = 2 * kk * sizeof(double) + sizeof(WindowState);
   // (a buffer of its own: the packed per-frame read-back of solve() uses h_export while the host is still working on this one)
-  growPinned(w.h_uncertainty, w.h_uncertainty_bytes, bytes);
-  if (!w.uncertainty_ready) HIP_CHECK(hipEventCreateWithFlags(&w.uncertainty_ready, hipEventDisableTiming));
-  double *Hpp = static_cast<double *>(w.h_uncertainty), *Hsc = Hpp + kk;
+  reserveGeometric(w.h_uncertainty, bytes);
+  const hipEvent_t ready = w.uncertainty_ready.get(hipEventDisableTiming);
+  double *Hpp = static_cast<double *>(w.h_uncertainty.get()), *Hsc = Hpp + kk;
   w.d_Hpp.download(Hpp, 2 * kk, 0, w.sr.stream);  // [H_pp | symmetric H_schur], stored back to back by the assemble kernel
   if (want_state) HIP_CHECK(hipMemcpyAsync(Hsc + kk, w.d_state.ptr, sizeof(WindowState), hipMemcpyDeviceToHost, w.sr.stream));
-  HIP_CHECK(hipEventRecord(w.uncertainty_ready, w.sr.stream));
+  HIP_CHECK(hipEventRecord(ready, w.sr.stream));
   return want_state;
 }
 
@@ -1939,8 +1930,8 @@ void estimateUncertainty(W &w) {
 void estimateUncertaintyHost(W &w, bool want_state) {
   const int K = w.K(), F = w.F();
   const size_t kk = static_cast<size_t>(K) * K;
-  double *Hpp = static_cast<double *>(w.h_uncertainty), *Hsc = Hpp + kk;
-  HIP_CHECK(hipEventSynchronize(w.uncertainty_ready));
+  double *Hpp = static_cast<double *>(w.h_uncertainty.get()), *Hsc = Hpp + kk;
+  HIP_CHECK(hipEventSynchronize(w.uncertainty_ready.h));
   if (want_state) {
     std::memcpy(&w.hst, Hsc + kk, sizeof(WindowState));
     w.host_stale = false;
@@ -2321,8 +2312,8 @@ int dsopp_hip_window_create(const dsopp_hip_options *options, int device, void *
     if (w->opt.dtype != DSOPP_HIP_F64 && w->opt.dtype != DSOPP_HIP_F32) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "bad dtype");
     w->sr.init(device, stream);
     std::memset(&w->hst, 0, sizeof(w->hst));
-    HIP_CHECK(hipEventCreate(&w->ev0));
-    HIP_CHECK(hipEventCreate(&w->ev1));
+    (void)w->ev0.get(hipEventDefault);
+    (void)w->ev1.get(hipEventDefault);
     *out = w.release();
   });
 }
@@ -2331,25 +2322,11 @@ void dsopp_hip_window_destroy(dsopp_hip_window *w) {
   if (!w) return;
   (void)hipSetDevice(w->sr.device);
   if (w->sr.stream) (void)hipStreamSynchronize(w->sr.stream);
-  if (w->ev0) (void)hipEventDestroy(w->ev0);
-  if (w->ev1) (void)hipEventDestroy(w->ev1);
-  if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  if (w->h_results) (void)hipHostFree(w->h_results);
-  if (w->h_uncertainty) (void)hipHostFree(w->h_uncertainty);
-  if (w->uncertainty_ready) (void)hipEventDestroy(w->uncertainty_ready);
-  if (w->h_export) (void)hipHostFree(w->h_export);
-  if (w->stage.base) (void)hipHostFree(w->stage.base);
-  if (w->h_update) (void)hipHostFree(w->h_update);
-  if (w->d_bs_flag) (void)hipFree(w->d_bs_flag);
-  if (w->h_bs_fault) (void)hipHostFree(w->h_bs_fault);
-  w->frames.clear();
   for (dsopp_hip_depth_maps *m : w->live_maps) {  // maps may outlive the window (the tracker holds them): they lose the borrowed stream
     m->sr.stream = nullptr;
     m->owner = nullptr;
   }
-  StreamRef sr = w->sr;
   delete w;
-  sr.destroy();
 }
 
 int dsopp_hip_window_push_frame(dsopp_hip_window *w, int32_t frame_id, int64_t timestamp, const dsopp_hip_pyramid *pyramid, int level,
@@ -2684,7 +2661,7 @@ static void runOptimize(dsopp_hip_window *w, double &e, int &it, int &nv) {
   if (w->F() == 0) fail(DSOPP_HIP_ERR_STATE, "window is empty");
   w->sr.use();
   prepare(*w);
-  HIP_CHECK(hipEventRecord(w->ev0, w->sr.stream));
+  HIP_CHECK(hipEventRecord(w->ev0.h, w->sr.stream));
   if (w->lm_mode == 0) {
     fusedBegin(*w);
     lmSolveFused(*w, e, it, nv);
@@ -2692,7 +2669,7 @@ static void runOptimize(dsopp_hip_window *w, double &e, int &it, int &nv) {
     stageBegin(*w);
     lmSolve(*w, e, it, nv);
   }
-  HIP_CHECK(hipEventRecord(w->ev1, w->sr.stream));
+  HIP_CHECK(hipEventRecord(w->ev1.h, w->sr.stream));
   w->solve_events_pending = true;  // the elapsed time is read when somebody asks for it (dsopp_hip_window_last_solve_ms)
   collectTimings(*w);
 }
@@ -2756,8 +2733,8 @@ void prefetchFrameUpdates(dsopp_hip_window &w) {
   }
   exportFramesKernel<<<dim3(static_cast<unsigned>((max_n + 255) / 256), static_cast<unsigned>(batch.n_frames)), 256, 0, st>>>(batch);
   HIP_CHECK(hipGetLastError());
-  growPinned(w.h_update, w.h_update_bytes, words * 8);
-  HIP_CHECK(hipMemcpyAsync(w.h_update, w.d_update.ptr, words * 8, hipMemcpyDeviceToHost, st));
+  reserveGeometric(w.h_update, words * 8);
+  HIP_CHECK(hipMemcpyAsync(w.h_update.get(), w.d_update.ptr, words * 8, hipMemcpyDeviceToHost, st));
 }
 }  // namespace
 
@@ -2814,7 +2791,7 @@ int dsopp_hip_window_solve(dsopp_hip_window *w, double *energy, int32_t *iterati
         HostTimes ht2_("solve: prepare");
         prepare(*w);  // (flushes the queued appends first)
       }
-      HIP_CHECK(hipEventRecord(w->ev0, w->sr.stream));
+      HIP_CHECK(hipEventRecord(w->ev0.h, w->sr.stream));
       {
         HostTimes ht2_("solve: enqueue of the LM loop");
         fusedBegin(*w);
@@ -2830,7 +2807,7 @@ int dsopp_hip_window_solve(dsopp_hip_window *w, double *energy, int32_t *iterati
         launchSweep(*w, false, true, false, nullptr, false, 0.0, ex);
         w->pair_valid = false;
       }
-      HIP_CHECK(hipEventRecord(w->ev1, w->sr.stream));
+      HIP_CHECK(hipEventRecord(w->ev1.h, w->sr.stream));
       w->solve_events_pending = true;
       {
         HostTimes ht2_("solve: enqueue of the re-linearisation");
@@ -2855,9 +2832,9 @@ int dsopp_hip_window_solve(dsopp_hip_window *w, double *energy, int32_t *iterati
         w->sr.sync();  // solve() is a blocking call: every result is in place when it returns
       }
       checkSolveLaunchFault(*w);
-      e = w->h_ctrl->energy;
-      it = w->h_ctrl->iteration;
-      nv = w->h_ctrl->n_valid;
+      e = w->h_ctrl.get()->energy;
+      it = w->h_ctrl.get()->iteration;
+      nv = w->h_ctrl.get()->n_valid;
       w->export_valid = true;
       collectTimings(*w);
       w->begun = false;
@@ -3026,7 +3003,7 @@ int dsopp_hip_window_get_frame_update(dsopp_hip_window *w, int32_t frame_id, dou
           if (all) row[static_cast<size_t>(t)] = static_cast<int>(it - e.target_ids.begin());
         }
         if (!all) break;
-        const double *hd = static_cast<const double *>(w->h_update) + e.word_offset;
+        const double *hd = static_cast<const double *>(w->h_update.get()) + e.word_offset;
         const uint8_t *hb = reinterpret_cast<const uint8_t *>(hd + 4 * n);
         if (idepth) std::memcpy(idepth, hd, n * sizeof(double));
         if (inv_hessian_idepth) std::memcpy(inv_hessian_idepth, hd + n, n * sizeof(double));
@@ -3061,10 +3038,10 @@ int dsopp_hip_window_get_frame_update(dsopp_hip_window *w, int32_t frame_id, dou
     a.out_b = reinterpret_cast<uint8_t *>(w->d_export.ptr + 4 * n);
     exportFrameKernel<<<static_cast<unsigned>((n + 255) / 256), 256, 0, st>>>(a);
     HIP_CHECK(hipGetLastError());
-    growPinned(w->h_export, w->h_export_bytes, words * 8);
-    HIP_CHECK(hipMemcpyAsync(w->h_export, w->d_export.ptr, words * 8, hipMemcpyDeviceToHost, st));
+    reserveGeometric(w->h_export, words * 8);
+    HIP_CHECK(hipMemcpyAsync(w->h_export.get(), w->d_export.ptr, words * 8, hipMemcpyDeviceToHost, st));
     w->sr.sync();
-    const double *hd = static_cast<const double *>(w->h_export);
+    const double *hd = static_cast<const double *>(w->h_export.get());
     const uint8_t *hb = reinterpret_cast<const uint8_t *>(hd + 4 * n);
     if (idepth) std::memcpy(idepth, hd, n * sizeof(double));
     if (inv_hessian_idepth) std::memcpy(inv_hessian_idepth, hd + n, n * sizeof(double));
@@ -3236,8 +3213,7 @@ int dsopp_hip_window_create_reference_depth_maps(dsopp_hip_window *w, int32_t le
     const HostFrame &fn = *w->frames.back();
     const LevelView lv = fn.pyramid->view(fn.level);
     auto maps = std::make_unique<dsopp_hip_depth_maps>();
-    maps->sr = w->sr;
-    maps->sr.owned = false;
+    maps->sr.borrow(w->sr);
     maps->levels = levels;
     maps->points.resize(static_cast<size_t>(levels));
     // initDepthMaps — create_depth_maps.cpp:62-68: one map per pyramid level of the newest keyframe
@@ -3340,13 +3316,13 @@ int dsopp_hip_debug_sweep_stamps(dsopp_hip_window *w, int lin, long long *out16)
   return guarded([&] {
     if (!kStamps) fail(DSOPP_HIP_ERR_STATE, "phase stamps are not compiled in (build with -DDSOPP_HIP_STAMPS)");
     if (!w->dbg_sweep) {
-      HIP_CHECK(hipMalloc(&w->dbg_sweep, 16 * sizeof(long long)));
+      w->dbg_sweep.alloc(16 * sizeof(long long));
     } else {
-      HIP_CHECK(hipMemcpy(out16, w->dbg_sweep, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(out16, w->dbg_sweep.get(), 16 * sizeof(long long), hipMemcpyDeviceToHost));
     }
-    HIP_CHECK(hipMemset(w->dbg_sweep, 0, 16 * sizeof(long long)));
+    HIP_CHECK(hipMemset(w->dbg_sweep.get(), 0, 16 * sizeof(long long)));
     const long long big = 0x7fffffffffffffffLL;
-    HIP_CHECK(hipMemcpy(w->dbg_sweep + 8, &big, sizeof(long long), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(w->dbg_sweep.get() + 8, &big, sizeof(long long), hipMemcpyHostToDevice));
     w->dbg_sweep_lin = lin != 0;
   });
 }
@@ -3356,10 +3332,10 @@ int dsopp_hip_debug_solve_stamps(dsopp_hip_window *w, long long *out8) {
   return guarded([&] {
     if (!kStamps) fail(DSOPP_HIP_ERR_STATE, "phase stamps are not compiled in (build with -DDSOPP_HIP_STAMPS)");
     if (!w->dbg_stamps) {
-      HIP_CHECK(hipMalloc(&w->dbg_stamps, 64 * sizeof(long long)));
-      HIP_CHECK(hipMemset(w->dbg_stamps, 0, 64 * sizeof(long long)));
+      w->dbg_stamps.alloc(64 * sizeof(long long));
+      HIP_CHECK(hipMemset(w->dbg_stamps.get(), 0, 64 * sizeof(long long)));
     }
-    HIP_CHECK(hipMemcpy(out8, w->dbg_stamps, 64 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out8, w->dbg_stamps.get(), 64 * sizeof(long long), hipMemcpyDeviceToHost));
   });
 }
 
@@ -3420,12 +3396,12 @@ int dsopp_hip_window_time_kernel(dsopp_hip_window *w, int kernel_class, int repe
     }
     if (kernel_class == DSOPP_HIP_KERNEL_SWEEP_LINEARIZE_LOOP) launchSolveCombined(*w, 1e-5, nullptr);  // a pose step to back-substitute
     once();  // warm
-    HIP_CHECK(hipEventRecord(w->ev0, w->sr.stream));
+    HIP_CHECK(hipEventRecord(w->ev0.h, w->sr.stream));
     for (int i = 0; i < repeats; ++i) once();
-    HIP_CHECK(hipEventRecord(w->ev1, w->sr.stream));
-    HIP_CHECK(hipEventSynchronize(w->ev1));
+    HIP_CHECK(hipEventRecord(w->ev1.h, w->sr.stream));
+    HIP_CHECK(hipEventSynchronize(w->ev1.h));
     float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, w->ev0, w->ev1));
+    HIP_CHECK(hipEventElapsedTime(&ms, w->ev0.h, w->ev1.h));
     *avg_us = static_cast<double>(ms) * 1e3 / repeats;
     w->profiling = saved;
     // the repeated solve launches moved the candidate step: drop it so the window state is unchanged
@@ -3460,7 +3436,7 @@ void optimizeRepeatedPipelined(dsopp_hip_window &w, int target, int &done, doubl
   const int configured = w.opt.max_iterations;
   constexpr int kSlots = 32;  // solves per batch: their results are fetched with ONE copy and ONE synchronisation
   w.d_results.reserve(kSlots, 0, st);
-  if (!w.h_results) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&w.h_results), kSlots * sizeof(LmControl), hipHostMallocDefault));
+  w.h_results.reserve(kSlots * sizeof(LmControl));
   done = 0;
   bool stalled = false, last_needs_closing = false;
   auto cleanUp = [&] {
@@ -3488,11 +3464,11 @@ void optimizeRepeatedPipelined(dsopp_hip_window &w, int target, int &done, doubl
         ++n;
       }
       w.result_device = nullptr;
-      HIP_CHECK(hipMemcpyAsync(w.h_results, w.d_results.ptr, static_cast<size_t>(n) * sizeof(LmControl), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(w.h_results.get(), w.d_results.ptr, static_cast<size_t>(n) * sizeof(LmControl), hipMemcpyDeviceToHost, st));
       w.sr.sync();
       checkSolveLaunchFault(w);
       for (int k = 0; k < n; ++k) {
-        const LmControl &r = w.h_results[k];
+        const LmControl &r = w.h_results.get()[k];
         if (r.iteration <= 0) stalled = true;  // no progress: leave (iterations_done < target)
         done += r.iteration;
         energy = r.energy;
@@ -3638,8 +3614,8 @@ int dsopp_hip_window_last_solve_ms(dsopp_hip_window *w, float *ms) {
     if (w->solve_events_pending) {
       w->sr.use();
     flushAppends(*w);
-      HIP_CHECK(hipEventSynchronize(w->ev1));
-      HIP_CHECK(hipEventElapsedTime(&w->last_solve_ms, w->ev0, w->ev1));
+      HIP_CHECK(hipEventSynchronize(w->ev1.h));
+      HIP_CHECK(hipEventElapsedTime(&w->last_solve_ms, w->ev0.h, w->ev1.h));
       w->solve_events_pending = false;
     }
     *ms = w->last_solve_ms;
@@ -3691,8 +3667,8 @@ int dsopp_hip_depth_maps_mean_square_optical_flow(const dsopp_hip_depth_maps *m,
     const size_t point_blocks = static_cast<size_t>(std::max(1, (pts.n + kFlowPointThreads - 1) / kFlowPointThreads));
     // scratch: [ticket of the point pass (zero-filled with the buffer, re-armed by the kernel) | 7 unused | partials per workgroup]
     m->flow_scratch.reserve(8 + std::max(n_blocks, by_points ? point_blocks : 0) * 2 * kMaxFlowTransforms, 0, st);
-    if (!m->h_flow) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&m->h_flow), 8 * sizeof(double), hipHostMallocDefault));
-    double *out = m->h_flow, *partials = m->flow_scratch.ptr + 8;
+    m->h_flow.reserve(8 * sizeof(double));
+    double *out = m->h_flow.get(), *partials = m->flow_scratch.ptr + 8;
     if (by_points) {
       pts.orderBehind(st);
       opticalFlowPointsKernel<<<static_cast<unsigned>(point_blocks), kFlowPointThreads, 0, st>>>(pts.u.ptr, pts.v.ptr, pts.idepth.ptr, pts.n, a, partials,
@@ -3810,9 +3786,9 @@ int dsopp_hip_window_activate_landmarks(dsopp_hip_window *w, int32_t n_keyframes
       n_immature += a.n_immature;
       n_active_cap += a.n_active;
       max_items = std::max(max_items, std::max(a.n_active, a.n_immature));
-      tex[static_cast<size_t>(k)] = fr.pyramid->texels[0];
+      tex[static_cast<size_t>(k)] = fr.pyramid->texels[0].get();
     }
-    tex[static_cast<size_t>(F - 1)] = newest_pyramid->texels[0];
+    tex[static_cast<size_t>(F - 1)] = newest_pyramid->texels[0].get();
     for (int r = 0; r < F; ++r)
       for (int t = 0; t < F; ++t) {
         ActPair &pc = pairs[static_cast<size_t>(r) * F + t];
@@ -3860,7 +3836,7 @@ int dsopp_hip_window_activate_landmarks(dsopp_hip_window *w, int32_t n_keyframes
     a.keyframes = S.keyframes.ptr;
     a.pairs = S.pairs.ptr;
     a.texels0 = S.texels0.ptr;
-    a.newest_sparsity = newest_pyramid->texels[1];
+    a.newest_sparsity = newest_pyramid->texels[1].get();
     a.n_keyframes = n_keyframes;
     a.n_frames = F;
     a.n_immature = n_immature;
@@ -3915,8 +3891,8 @@ int dsopp_hip_window_activate_landmarks(dsopp_hip_window *w, int32_t n_keyframes
     HIP_CHECK(hipGetLastError());
     // ---- one read-back of the contiguous results: idepth (nI doubles) | distance | statuses (nI bytes, padded to words) | counters (8 ints)
     const size_t bytes = (nI + 1 + status_words + 4) * sizeof(double);
-    growPinned(w->h_export, w->h_export_bytes, bytes);
-    char *h = static_cast<char *>(w->h_export);
+    reserveGeometric(w->h_export, bytes);
+    char *h = static_cast<char *>(w->h_export.get());
     HIP_CHECK(hipMemcpyAsync(h, S.pack.ptr, bytes, hipMemcpyDeviceToHost, st));
     w->sr.sync();
     const double *h_id = reinterpret_cast<const double *>(h);

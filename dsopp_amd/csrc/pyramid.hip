@@ -9,6 +9,8 @@
 // each thread regenerates from the parent plane (u8 + LUT at level 0, 2x2 means above) — reads are coalesced rows that
 // hit L2, writes are one full 16/32-byte texel per lane.  HBM-bound by construction: ~(1 + 4*sizeof(S)) bytes per pixel.
 #include "pyramid.hpp"
+
+#include <memory>
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
 #include <emmintrin.h>
 #endif
@@ -293,8 +295,8 @@ void buildTyped(dsopp_hip_pyramid *p, const uint8_t *img_dev, const uint8_t *vig
     for (int l = 0; l < p->levels; ++l) {
       a.width[l] = p->w(l);
       a.height[l] = p->h(l);
-      a.tex[l] = p->texels[l];
-      a.plane[l] = p->planes[l];
+      a.tex[l] = p->texels[l].get();
+      a.plane[l] = p->planes[l].get();
     }
     a.tiles0_x = (p->w(0) + kTileX - 1) / kTileX;
     const int tiles0 = a.tiles0_x * ((p->h(0) + kTileY - 1) / kTileY);
@@ -310,13 +312,13 @@ void buildTyped(dsopp_hip_pyramid *p, const uint8_t *img_dev, const uint8_t *vig
   }
   {
     dim3 grid((p->w(0) + kTileX - 1) / kTileX, (p->h(0) + kTileY - 1) / kTileY);
-    pyramidLevel0Kernel<S><<<grid, block, 0, st>>>(img_dev, vig_dev, lut_dev, vmax, p->w(0), p->h(0), static_cast<S *>(p->planes[0]),
-                                                   static_cast<Texel<S> *>(p->texels[0]));
+    pyramidLevel0Kernel<S><<<grid, block, 0, st>>>(img_dev, vig_dev, lut_dev, vmax, p->w(0), p->h(0), static_cast<S *>(p->planes[0].get()),
+                                                   static_cast<Texel<S> *>(p->texels[0].get()));
   }
   for (int l = 1; l < p->levels; ++l) {
     dim3 grid((p->w(l) + kTileX - 1) / kTileX, (p->h(l) + kTileY - 1) / kTileY);
-    pyramidLevelKernel<S><<<grid, block, 0, st>>>(static_cast<const S *>(p->planes[l - 1]), p->w(l - 1), p->w(l), p->h(l),
-                                                  static_cast<S *>(p->planes[l]), static_cast<Texel<S> *>(p->texels[l]));
+    pyramidLevelKernel<S><<<grid, block, 0, st>>>(static_cast<const S *>(p->planes[l - 1].get()), p->w(l - 1), p->w(l), p->h(l),
+                                                  static_cast<S *>(p->planes[l].get()), static_cast<Texel<S> *>(p->texels[l].get()));
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -324,7 +326,7 @@ void buildTyped(dsopp_hip_pyramid *p, const uint8_t *img_dev, const uint8_t *vig
 template <typename S>
 void fillMask(dsopp_hip_pyramid *p, int level, const uint8_t *mask_dev) {
   const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
-  fillMaskKernel<S><<<static_cast<unsigned>((n + 255) / 256), 256, 0, p->sr.stream>>>(static_cast<Texel<S> *>(p->texels[level]), mask_dev, n);
+  fillMaskKernel<S><<<static_cast<unsigned>((n + 255) / 256), 256, 0, p->sr.stream>>>(static_cast<Texel<S> *>(p->texels[level].get()), mask_dev, n);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -343,24 +345,24 @@ const void *dsopp_hip_pyramid::intensityPlane(int level, hipStream_t consumer) c
   std::lock_guard<std::mutex> lock(iplane_mutex);
   const int tx = itilesX(level), ty = itilesY(level);
   if (!iplane_valid[level]) {
-    if (!iplane[level]) HIP_CHECK(hipMalloc(&iplane[level], static_cast<size_t>(tx) * ty * 64));  // one 64-byte tile per (tx, ty)
-    if (!iplane_ready[level]) HIP_CHECK(hipEventCreateWithFlags(&iplane_ready[level], hipEventDisableTiming));
+    if (!iplane[level]) iplane[level].alloc(static_cast<size_t>(tx) * ty * 64);  // one 64-byte tile per (tx, ty)
+    const hipEvent_t built = iplane_ready[level].get(hipEventDisableTiming);
     waitReady(consumer);  // the texels' last build
     dim3 block(kTileX, kTileY), grid((4 * tx + kTileX - 1) / kTileX, ((dtype == DSOPP_HIP_F64 ? 2 : 4) * ty + kTileY - 1) / kTileY);
     if (dtype == DSOPP_HIP_F64)
-      buildIntensityPlaneKernel<<<grid, block, 0, consumer>>>(static_cast<const Texel<double> *>(texels[level]), w(level), h(level), tx, ty,
-                                                              static_cast<unsigned long long *>(iplane[level]));
+      buildIntensityPlaneKernel<<<grid, block, 0, consumer>>>(static_cast<const Texel<double> *>(texels[level].get()), w(level), h(level), tx, ty,
+                                                              static_cast<unsigned long long *>(iplane[level].get()));
     else
-      buildIntensityPlaneKernel<<<grid, block, 0, consumer>>>(static_cast<const Texel<float> *>(texels[level]), w(level), h(level), tx, ty,
-                                                              static_cast<unsigned *>(iplane[level]));
+      buildIntensityPlaneKernel<<<grid, block, 0, consumer>>>(static_cast<const Texel<float> *>(texels[level].get()), w(level), h(level), tx, ty,
+                                                              static_cast<unsigned *>(iplane[level].get()));
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(iplane_ready[level], consumer));
+    HIP_CHECK(hipEventRecord(built, consumer));
     iplane_stream[level] = consumer;
     iplane_valid[level] = true;
   } else if (consumer != iplane_stream[level]) {
-    HIP_CHECK(hipStreamWaitEvent(consumer, iplane_ready[level], 0));
+    HIP_CHECK(hipStreamWaitEvent(consumer, iplane_ready[level].h, 0));
   }
-  return iplane[level];
+  return iplane[level].get();
 }
 
 extern "C" {
@@ -381,32 +383,27 @@ int dsopp_hip_pyramid_create(int device, void *stream, int width, int height, in
     if (!out || width <= 0 || height <= 0 || levels <= 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "bad pyramid dimensions");
     if (dtype != DSOPP_HIP_F64 && dtype != DSOPP_HIP_F32) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "bad dtype %d", dtype);
     levels = levels > DSOPP_HIP_MAX_LEVELS ? DSOPP_HIP_MAX_LEVELS : levels;  // pixel_data_frame.cpp:14
-    auto *p = new dsopp_hip_pyramid();
-    try {
-      p->sr.init(device, stream);
-      p->width = width;
-      p->height = height;
-      p->levels = levels;
-      p->dtype = dtype;
-      for (int l = 0; l < levels; ++l) {
-        const size_t n = static_cast<size_t>(p->w(l)) * p->h(l);
-        if (n == 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "level %d is empty", l);
-        HIP_CHECK(hipMalloc(&p->texels[l], n * 4 * p->elemSize()));
-        HIP_CHECK(hipMalloc(&p->planes[l], n * p->elemSize()));
-        if (dtype == DSOPP_HIP_F64)
-          fillMask<double>(p, l, nullptr);
-        else
-          fillMask<float>(p, l, nullptr);
-      }
-      HIP_CHECK(hipMalloc(&p->staging_u8, static_cast<size_t>(width) * height));
-      HIP_CHECK(hipMalloc(&p->staging_vig, static_cast<size_t>(width) * height));
-      HIP_CHECK(hipMalloc(&p->lut_dev, 256 * sizeof(double)));
-      p->sr.sync();
-    } catch (...) {
-      dsopp_hip_pyramid_destroy(p);
-      throw;
+    auto p = std::make_unique<dsopp_hip_pyramid>();
+    p->sr.init(device, stream);
+    p->width = width;
+    p->height = height;
+    p->levels = levels;
+    p->dtype = dtype;
+    for (int l = 0; l < levels; ++l) {
+      const size_t n = static_cast<size_t>(p->w(l)) * p->h(l);
+      if (n == 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "level %d is empty", l);
+      p->texels[l].alloc(n * 4 * p->elemSize());
+      p->planes[l].alloc(n * p->elemSize());
+      if (dtype == DSOPP_HIP_F64)
+        fillMask<double>(p.get(), l, nullptr);
+      else
+        fillMask<float>(p.get(), l, nullptr);
     }
-    *out = p;
+    p->staging_u8.alloc(static_cast<size_t>(width) * height);
+    p->staging_vig.alloc(static_cast<size_t>(width) * height);
+    p->lut_dev.alloc(256 * sizeof(double));
+    p->sr.sync();
+    *out = p.release();
   });
 }
 
@@ -414,18 +411,6 @@ void dsopp_hip_pyramid_destroy(dsopp_hip_pyramid *p) {
   if (!p) return;
   (void)hipSetDevice(p->sr.device);
   if (p->sr.stream) (void)hipStreamSynchronize(p->sr.stream);
-  for (int l = 0; l < DSOPP_HIP_MAX_LEVELS; ++l) {
-    if (p->texels[l]) (void)hipFree(p->texels[l]);
-    if (p->planes[l]) (void)hipFree(p->planes[l]);
-    if (p->iplane[l]) (void)hipFree(p->iplane[l]);
-    if (p->iplane_ready[l]) (void)hipEventDestroy(p->iplane_ready[l]);
-  }
-  if (p->staging_u8) (void)hipFree(p->staging_u8);
-  if (p->staging_vig) (void)hipFree(p->staging_vig);
-  if (p->h_image) (void)hipHostFree(p->h_image);
-  if (p->lut_dev) (void)hipFree(p->lut_dev);
-  if (p->ready) (void)hipEventDestroy(p->ready);
-  p->sr.destroy();
   delete p;
 }
 
@@ -436,8 +421,8 @@ int dsopp_hip_pyramid_build_device(dsopp_hip_pyramid *p, const void *image_dev, 
     p->sr.use();
     const double *lut_dev = nullptr;
     if (lut256) {
-      HIP_CHECK(hipMemcpyAsync(p->lut_dev, lut256, 256 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
-      lut_dev = p->lut_dev;
+      HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
+      lut_dev = p->lut_dev.get();
     }
     if (p->dtype == DSOPP_HIP_F64)
       buildTyped<double>(p, static_cast<const uint8_t *>(image_dev), static_cast<const uint8_t *>(vignetting_dev), lut_dev, vignetting_max);
@@ -482,28 +467,24 @@ int dsopp_hip_pyramid_build(dsopp_hip_pyramid *p, const uint8_t *image_host, con
     // instead (a memcpy of 1.3 MB) and leaves from there as a DMA the call does not wait for: consumers order themselves behind the build
     // with waitReady(), as they do behind build_device.  (The buffer's previous upload has long completed: a pyramid is rebuilt once per
     // frame, and the synchronisation below covers the paths that keep it.)
-    if (!p->h_image) {
-      HIP_CHECK(hipStreamSynchronize(p->sr.stream));
-      HIP_CHECK(hipHostMalloc(&p->h_image, n, hipHostMallocDefault));
-    } else {
-      HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)
-    }
+    HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)
+    p->h_image.reserve(n);
     // In pieces: the DMA of a piece (1.3 MB over the host link: ~50 us, as long as the memcpy itself) runs while the host copies the next
     // one — the consumer's wait for the pyramid shrinks by three quarters of the transfer
     const size_t pieces = n >= (size_t(1) << 19) ? 4 : 1;
     const size_t piece = ((n + pieces - 1) / pieces + 4095) & ~static_cast<size_t>(4095);
     for (size_t off = 0; off < n; off += piece) {
       const size_t len = std::min(piece, n - off);
-      copyToPinned(static_cast<uint8_t *>(p->h_image) + off, image_host + off, len);
-      HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t *>(p->staging_u8) + off, static_cast<uint8_t *>(p->h_image) + off, len, hipMemcpyHostToDevice, p->sr.stream));
+      copyToPinned(p->h_image.get() + off, image_host + off, len);
+      HIP_CHECK(hipMemcpyAsync(p->staging_u8.get() + off, p->h_image.get() + off, len, hipMemcpyHostToDevice, p->sr.stream));
     }
     double vmax = 0;
     if (vignetting_host) {
       // cv::minMaxLoc(vignetting, nullptr, &max) — photometrically_corrected_image.cpp:11-13
       for (size_t i = 0; i < n; ++i) vmax = vignetting_host[i] > vmax ? vignetting_host[i] : vmax;
-      HIP_CHECK(hipMemcpyAsync(p->staging_vig, vignetting_host, n, hipMemcpyHostToDevice, p->sr.stream));
+      HIP_CHECK(hipMemcpyAsync(p->staging_vig.get(), vignetting_host, n, hipMemcpyHostToDevice, p->sr.stream));
     }
-    int rc = dsopp_hip_pyramid_build_device(p, p->staging_u8, lut256, vignetting_host ? p->staging_vig : nullptr, vmax);
+    int rc = dsopp_hip_pyramid_build_device(p, p->staging_u8.get(), lut256, vignetting_host ? p->staging_vig.get() : nullptr, vmax);
     if (rc != DSOPP_HIP_OK) throw Error(rc, lastError());
     // the LUT and the vignette are read straight from the caller's (pageable) arrays: those paths wait; the plain image path does not
     if (lut256 || vignetting_host) p->sr.sync();
@@ -516,18 +497,17 @@ int dsopp_hip_pyramid_set_level(dsopp_hip_pyramid *p, int level, const double *p
     if (!pixelinfo_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null pixelinfo");
     p->sr.use();
     const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
-    double *tmp = nullptr;
-    HIP_CHECK(hipMalloc(&tmp, n * 3 * sizeof(double)));
-    HIP_CHECK(hipMemcpyAsync(tmp, pixelinfo_host, n * 3 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
+    DeviceMem<double> tmp;
+    tmp.alloc(n * 3 * sizeof(double));
+    HIP_CHECK(hipMemcpyAsync(tmp.get(), pixelinfo_host, n * 3 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
     const unsigned grid = static_cast<unsigned>((n + 255) / 256);
     if (p->dtype == DSOPP_HIP_F64)
-      setLevelKernel<double><<<grid, 256, 0, p->sr.stream>>>(static_cast<Texel<double> *>(p->texels[level]), static_cast<double *>(p->planes[level]), tmp, n);
+      setLevelKernel<double><<<grid, 256, 0, p->sr.stream>>>(static_cast<Texel<double> *>(p->texels[level].get()), static_cast<double *>(p->planes[level].get()), tmp.get(), n);
     else
-      setLevelKernel<float><<<grid, 256, 0, p->sr.stream>>>(static_cast<Texel<float> *>(p->texels[level]), static_cast<float *>(p->planes[level]), tmp, n);
+      setLevelKernel<float><<<grid, 256, 0, p->sr.stream>>>(static_cast<Texel<float> *>(p->texels[level].get()), static_cast<float *>(p->planes[level].get()), tmp.get(), n);
     HIP_CHECK(hipGetLastError());
     p->markReady();
     p->sr.sync();
-    (void)hipFree(tmp);
   });
 }
 
@@ -538,8 +518,8 @@ int dsopp_hip_pyramid_set_mask(dsopp_hip_pyramid *p, int level, const uint8_t *m
     const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
     const uint8_t *mask_dev = nullptr;
     if (mask_host) {
-      HIP_CHECK(hipMemcpyAsync(p->staging_u8, mask_host, n, hipMemcpyHostToDevice, p->sr.stream));
-      mask_dev = static_cast<const uint8_t *>(p->staging_u8);
+      HIP_CHECK(hipMemcpyAsync(p->staging_u8.get(), mask_host, n, hipMemcpyHostToDevice, p->sr.stream));
+      mask_dev = p->staging_u8.get();
     }
     if (p->dtype == DSOPP_HIP_F64)
       fillMask<double>(p, level, mask_dev);
@@ -556,17 +536,16 @@ int dsopp_hip_pyramid_get_level(dsopp_hip_pyramid *p, int level, double *pixelin
     if (!pixelinfo_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null output");
     p->sr.use();
     const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
-    double *tmp = nullptr;
-    HIP_CHECK(hipMalloc(&tmp, n * 3 * sizeof(double)));
+    DeviceMem<double> tmp;
+    tmp.alloc(n * 3 * sizeof(double));
     const unsigned grid = static_cast<unsigned>((n + 255) / 256);
     if (p->dtype == DSOPP_HIP_F64)
-      getLevelKernel<double><<<grid, 256, 0, p->sr.stream>>>(static_cast<const Texel<double> *>(p->texels[level]), tmp, n);
+      getLevelKernel<double><<<grid, 256, 0, p->sr.stream>>>(static_cast<const Texel<double> *>(p->texels[level].get()), tmp.get(), n);
     else
-      getLevelKernel<float><<<grid, 256, 0, p->sr.stream>>>(static_cast<const Texel<float> *>(p->texels[level]), tmp, n);
+      getLevelKernel<float><<<grid, 256, 0, p->sr.stream>>>(static_cast<const Texel<float> *>(p->texels[level].get()), tmp.get(), n);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(pixelinfo_host, tmp, n * 3 * sizeof(double), hipMemcpyDeviceToHost, p->sr.stream));
+    HIP_CHECK(hipMemcpyAsync(pixelinfo_host, tmp.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, p->sr.stream));
     p->sr.sync();
-    (void)hipFree(tmp);
   });
 }
 

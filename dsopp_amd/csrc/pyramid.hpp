@@ -85,19 +85,18 @@ struct LevelView {
 struct dsopp_hip_pyramid {
   dsopp_hip::StreamRef sr;
   int width = 0, height = 0, levels = 0, dtype = DSOPP_HIP_F64;
-  void *texels[DSOPP_HIP_MAX_LEVELS] = {nullptr};  // Texel<S>[h_l * w_l]
-  void *planes[DSOPP_HIP_MAX_LEVELS] = {nullptr};  // S[h_l * w_l] scalar plane (downscale source)
-  void *staging_u8 = nullptr;                       // level-0 u8 image / vignette / mask staging
-  void *staging_vig = nullptr;
-  void *h_image = nullptr;                          // pinned copy of the caller's 8-bit image (dsopp_hip_pyramid_build): the upload is a true DMA, the call does not wait for it
-  double *lut_dev = nullptr;                        // 256 doubles
+  dsopp_hip::DeviceMem<void> texels[DSOPP_HIP_MAX_LEVELS];  // Texel<S>[h_l * w_l]
+  dsopp_hip::DeviceMem<void> planes[DSOPP_HIP_MAX_LEVELS];  // S[h_l * w_l] scalar plane (downscale source)
+  dsopp_hip::DeviceMem<uint8_t> staging_u8;                 // level-0 u8 image / vignette / mask staging
+  dsopp_hip::DeviceMem<uint8_t> staging_vig;
+  dsopp_hip::PinnedMem<uint8_t> h_image;  // copy of the caller's 8-bit image (dsopp_hip_pyramid_build): the upload is a true DMA, the call does not wait for it
+  dsopp_hip::DeviceMem<double> lut_dev;   // 256 doubles
   // Recorded on the pyramid's stream behind every write of the texels (build / build_device / set_level / set_mask).  A
   // consumer that reads the texels on another stream orders itself behind it with waitReady(): build_device only ENQUEUES
   // work, so without this a solve on the aligner's or the window's own stream could sample a half-built image.
-  hipEvent_t ready = nullptr;
+  dsopp_hip::Event ready;
   void markReady() {
-    if (!ready) HIP_CHECK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(ready, sr.stream));
+    HIP_CHECK(hipEventRecord(ready.get(hipEventDisableTiming), sr.stream));
     std::lock_guard<std::mutex> lock(iplane_mutex);
     for (bool &v : iplane_valid) v = false;  // the texels changed: the intensity planes derived from them are stale
     ++generation;  // (a window that borrowed this pyramid compares it before its next sweep and rebuilds the plane it samples)
@@ -107,10 +106,10 @@ struct dsopp_hip_pyramid {
   // 4-byte words, 4 x 4 pixels (f32 pyramids, the reference's -DUSE_FLOAT build; round 6).  What the residual-only sweeps read
   // instead of the 32- / 16-byte texels: a bilinear footprint then lies in 1.9 (f32: 1.6) segments on average instead of 3, and
   // a pattern's 8 footprints share them.
-  mutable void *iplane[DSOPP_HIP_MAX_LEVELS] = {nullptr};
+  mutable dsopp_hip::DeviceMem<void> iplane[DSOPP_HIP_MAX_LEVELS];
   mutable bool iplane_valid[DSOPP_HIP_MAX_LEVELS] = {false};
   unsigned generation = 0;  // number of rewrites of the texels (markReady)
-  mutable hipEvent_t iplane_ready[DSOPP_HIP_MAX_LEVELS] = {nullptr};
+  mutable dsopp_hip::Event iplane_ready[DSOPP_HIP_MAX_LEVELS];
   mutable hipStream_t iplane_stream[DSOPP_HIP_MAX_LEVELS] = {nullptr};
   mutable std::mutex iplane_mutex;
   int itilesX(int l) const { return (w(l) + 3) / 4; }
@@ -119,10 +118,10 @@ struct dsopp_hip_pyramid {
   const void *intensityPlane(int level, hipStream_t consumer) const;
   /** everything enqueued on `consumer` after this call sees the texels of the last build (no host synchronisation) */
   void waitReady(hipStream_t consumer) const {
-    if (ready && consumer != sr.stream) HIP_CHECK(hipStreamWaitEvent(consumer, ready, 0));
+    if (ready && consumer != sr.stream) HIP_CHECK(hipStreamWaitEvent(consumer, ready.h, 0));
   }
   int w(int l) const { return width >> l; }
   int h(int l) const { return height >> l; }
   size_t elemSize() const { return dtype == DSOPP_HIP_F64 ? sizeof(double) : sizeof(float); }
-  dsopp_hip::LevelView view(int l) const { return dsopp_hip::LevelView{texels[l], w(l), h(l)}; }
+  dsopp_hip::LevelView view(int l) const { return dsopp_hip::LevelView{texels[l].get(), w(l), h(l)}; }
 };

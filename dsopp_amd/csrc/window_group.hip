@@ -88,8 +88,8 @@ struct AbortableBarrier {
 struct LocalReducer {
   int n = 0;
   std::vector<int> device;
-  std::vector<hipEvent_t> ev_in;
-  hipEvent_t ev_out = nullptr;
+  std::vector<Event> ev_in;
+  Event ev_out;
   struct Slot {
     double *buf = nullptr;
     size_t count = 0;
@@ -112,7 +112,7 @@ int localAllreduce(void *user, void *device_buffer, size_t count, void *stream) 
   const int i = u->shard;
   hipStream_t st = static_cast<hipStream_t>(stream);
   r.slot[static_cast<size_t>(i)] = {static_cast<double *>(device_buffer), count, st};
-  if (hipEventRecord(r.ev_in[static_cast<size_t>(i)], st) != hipSuccess) r.failed.store(1);
+  if (hipEventRecord(r.ev_in[static_cast<size_t>(i)].h, st) != hipSuccess) r.failed.store(1);
   if (!r.bar.wait()) return -2;
   if (i == 0) {
     ShardBuffers b{};
@@ -121,18 +121,18 @@ int localAllreduce(void *user, void *device_buffer, size_t count, void *stream) 
       const LocalReducer::Slot &s = r.slot[static_cast<size_t>(j)];
       ok = ok && s.count == count && s.buf != nullptr;
       b.p[j] = s.buf;
-      if (j > 0 && hipStreamWaitEvent(st, r.ev_in[static_cast<size_t>(j)], 0) != hipSuccess) ok = false;
+      if (j > 0 && hipStreamWaitEvent(st, r.ev_in[static_cast<size_t>(j)].h, 0) != hipSuccess) ok = false;
     }
     if (ok && count) {
       const unsigned grid = static_cast<unsigned>(std::min<size_t>((count + 255) / 256, 1024));
       sumShardBuffersKernel<<<grid, 256, 0, st>>>(b, r.n, count);
       ok = hipGetLastError() == hipSuccess;
     }
-    if (hipEventRecord(r.ev_out, st) != hipSuccess) ok = false;
+    if (hipEventRecord(r.ev_out.h, st) != hipSuccess) ok = false;
     if (!ok) r.failed.store(1);
   }
   if (!r.bar.wait()) return -2;
-  if (i != 0 && hipStreamWaitEvent(st, r.ev_out, 0) != hipSuccess) r.failed.store(1);
+  if (i != 0 && hipStreamWaitEvent(st, r.ev_out.h, 0) != hipSuccess) r.failed.store(1);
   return r.failed.load() ? -1 : 0;
 }
 
@@ -212,10 +212,10 @@ __global__ void __launch_bounds__(kP2PThreads) p2pAllreduceKernel(P2PArgs a) {
 
 struct P2PReducer {
   int n = 0;
-  std::vector<double *> recv;
-  std::vector<unsigned long long *> flags;
+  std::vector<DeviceMem<double>> recv;
+  std::vector<DeviceMem<unsigned long long>> flags;
   std::vector<unsigned long long> generation;  // per shard: collectives issued so far (all shards issue the same sequence)
-  int *error = nullptr;                        // pinned host memory, one word per shard
+  PinnedMem<int> error;                        // one word per shard
   std::vector<int> device;
   bool one_device = false;                     // every shard on the same device: one launch plays all shards (see the kernel)
 };
@@ -233,11 +233,11 @@ int p2pAllreduce(void *user, void *device_buffer, size_t count, void *stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   P2PArgs a;
   for (int p = 0; p < r.n; ++p) {
-    a.recv_of[p] = r.recv[static_cast<size_t>(p)];
-    a.flags_of[p] = r.flags[static_cast<size_t>(p)];
+    a.recv_of[p] = r.recv[static_cast<size_t>(p)].get();
+    a.flags_of[p] = r.flags[static_cast<size_t>(p)].get();
     a.buf_of[p] = nullptr;
   }
-  a.error = r.error;
+  a.error = r.error.get();
   a.n = r.n;
   a.count = static_cast<unsigned>(count);
   if (!r.one_device) {
@@ -252,7 +252,7 @@ int p2pAllreduce(void *user, void *device_buffer, size_t count, void *stream) {
   LocalReducer &lr = *u->local->red;
   const int i = u->shard;
   lr.slot[static_cast<size_t>(i)] = {static_cast<double *>(device_buffer), count, st};
-  if (hipEventRecord(lr.ev_in[static_cast<size_t>(i)], st) != hipSuccess) lr.failed.store(1);
+  if (hipEventRecord(lr.ev_in[static_cast<size_t>(i)].h, st) != hipSuccess) lr.failed.store(1);
   if (!lr.bar.wait()) return -2;
   if (i == 0) {
     bool ok = true;
@@ -260,7 +260,7 @@ int p2pAllreduce(void *user, void *device_buffer, size_t count, void *stream) {
       const LocalReducer::Slot &sl = lr.slot[static_cast<size_t>(j)];
       ok = ok && sl.count == count && sl.buf != nullptr;
       a.buf_of[j] = sl.buf;
-      if (j > 0 && hipStreamWaitEvent(st, lr.ev_in[static_cast<size_t>(j)], 0) != hipSuccess) ok = false;
+      if (j > 0 && hipStreamWaitEvent(st, lr.ev_in[static_cast<size_t>(j)].h, 0) != hipSuccess) ok = false;
     }
     if (ok) {
       a.generation = ++r.generation[0];
@@ -268,11 +268,11 @@ int p2pAllreduce(void *user, void *device_buffer, size_t count, void *stream) {
       p2pAllreduceKernel<<<dim3(kP2PBlocks, static_cast<unsigned>(r.n)), kP2PThreads, 0, st>>>(a);
       ok = hipGetLastError() == hipSuccess;
     }
-    if (hipEventRecord(lr.ev_out, st) != hipSuccess) ok = false;
+    if (hipEventRecord(lr.ev_out.h, st) != hipSuccess) ok = false;
     if (!ok) lr.failed.store(1);
   }
   if (!lr.bar.wait()) return -2;
-  if (i != 0 && hipStreamWaitEvent(st, lr.ev_out, 0) != hipSuccess) lr.failed.store(1);
+  if (i != 0 && hipStreamWaitEvent(st, lr.ev_out.h, 0) != hipSuccess) lr.failed.store(1);
   return lr.failed.load() ? -1 : 0;
 }
 
@@ -440,7 +440,7 @@ void fanOut(G &g, Body &&body) {
   g.pool.run([&](int s) -> int { return body(s, g.win[static_cast<size_t>(s)]); });
   if (g.p2p.error) {  // DSOPP_HIP_TRANSPORT_P2P: a bounded wait of the one-shot all-reduce ran out (raised by the kernel in pinned memory)
     for (int s = 0; s < g.n; ++s)
-      if (g.p2p.error[s]) {
+      if (g.p2p.error.get()[s]) {
         g.poisoned.store(true);
         fail(DSOPP_HIP_ERR_HIP, "shard %d: the peer-to-peer all-reduce timed out waiting for another shard's partial sums (its results are invalid; destroy the group)", s);
       }
@@ -540,7 +540,7 @@ int dsopp_hip_window_group_create(const dsopp_hip_options *options, const int32_
       r.n = n;
       r.device = g->device;
       r.slot.resize(static_cast<size_t>(n));
-      r.ev_in.assign(static_cast<size_t>(n), nullptr);
+      r.ev_in.resize(static_cast<size_t>(n));
       r.bar.n = n;
       // shard 0's device adds the buffers of all shards: it needs peer access to every other device of the group
       HIP_CHECK(hipSetDevice(g->device[0]));
@@ -553,7 +553,7 @@ int dsopp_hip_window_group_create(const dsopp_hip_options *options, const int32_
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_CHECK(e);
         (void)hipGetLastError();
       }
-      HIP_CHECK(hipEventCreateWithFlags(&r.ev_out, hipEventDisableTiming));
+      (void)r.ev_out.get(hipEventDisableTiming);
       const bool p2p = transport == DSOPP_HIP_TRANSPORT_P2P;
       if (p2p) {
         // every shard writes into every shard's receive area: peer access between all pairs of distinct devices
@@ -586,15 +586,15 @@ int dsopp_hip_window_group_create(const dsopp_hip_options *options, const int32_
           fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "DSOPP_HIP_TRANSPORT_P2P across distinct devices is experimental (never run on a multi-GPU node): set "
                                                "DSOPP_HIP_P2P_EXPERIMENTAL=1 to opt in, or use DSOPP_HIP_TRANSPORT_RCCL / _LOCAL");
         q.one_device = same;
-        q.recv.assign(static_cast<size_t>(n), nullptr);
-        q.flags.assign(static_cast<size_t>(n), nullptr);
+        q.recv.resize(static_cast<size_t>(n));
+        q.flags.resize(static_cast<size_t>(n));
         q.generation.assign(static_cast<size_t>(n), 0);
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&q.error), sizeof(int) * static_cast<size_t>(n), hipHostMallocDefault));
-        for (int i = 0; i < n; ++i) q.error[i] = 0;
+        q.error.reserve(sizeof(int) * static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) q.error.get()[i] = 0;
         g->p2p_users.resize(static_cast<size_t>(n));
       }
       fanOut(*g, [&](int s, dsopp_hip_window *w) {
-        if (hipEventCreateWithFlags(&r.ev_in[static_cast<size_t>(s)], hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&r.ev_in[static_cast<size_t>(s)].h, hipEventDisableTiming) != hipSuccess) {
           lastError() = "hipEventCreate failed";
           return static_cast<int>(DSOPP_HIP_ERR_HIP);
         }
@@ -604,15 +604,14 @@ int dsopp_hip_window_group_create(const dsopp_hip_options *options, const int32_
         P2PReducer &q = g->p2p;
         const size_t recv_bytes = 2 * static_cast<size_t>(n) * kP2PCapacity * sizeof(double);
         const size_t flag_bytes = 2 * static_cast<size_t>(n) * kP2PBlocks * sizeof(unsigned long long);
-        void *rp = nullptr, *fp = nullptr;
-        if (hipExtMallocWithFlags(&rp, recv_bytes, hipDeviceMallocFinegrained) != hipSuccess ||
-            hipExtMallocWithFlags(&fp, flag_bytes, hipDeviceMallocFinegrained) != hipSuccess || hipMemset(fp, 0, flag_bytes) != hipSuccess ||
+        double *&rp = q.recv[static_cast<size_t>(s)].h;
+        unsigned long long *&fp = q.flags[static_cast<size_t>(s)].h;
+        if (hipExtMallocWithFlags(reinterpret_cast<void **>(&rp), recv_bytes, hipDeviceMallocFinegrained) != hipSuccess ||
+            hipExtMallocWithFlags(reinterpret_cast<void **>(&fp), flag_bytes, hipDeviceMallocFinegrained) != hipSuccess || hipMemset(fp, 0, flag_bytes) != hipSuccess ||
             hipDeviceSynchronize() != hipSuccess) {
           lastError() = "allocation of the peer-to-peer receive area failed";
           return static_cast<int>(DSOPP_HIP_ERR_HIP);
         }
-        q.recv[static_cast<size_t>(s)] = static_cast<double *>(rp);
-        q.flags[static_cast<size_t>(s)] = static_cast<unsigned long long *>(fp);
         g->p2p_users[static_cast<size_t>(s)] = {&q, &g->users[static_cast<size_t>(s)], s};
         return dsopp_hip_window_set_allreduce(w, &p2pAllreduce, &g->p2p_users[static_cast<size_t>(s)], s, n);
       });
@@ -630,17 +629,17 @@ void dsopp_hip_window_group_destroy(dsopp_hip_window_group *g) {
       if (i > 0 && i < set.of_shard.size() && set.of_shard[i]) dsopp_hip_depth_maps_destroy(set.of_shard[i]);  // ([0] is the caller's)
     if (g->win[i]) dsopp_hip_window_destroy(g->win[i]);
     if (g->comm[i]) dsopp_hip_comm_destroy(g->comm[i]);
-    if (static_cast<size_t>(s) < g->reducer.ev_in.size() && g->reducer.ev_in[i]) (void)hipEventDestroy(g->reducer.ev_in[i]);
+    if (i < g->reducer.ev_in.size()) g->reducer.ev_in[i].reset();
     if (i < g->p2p.recv.size()) {
-      if (g->p2p.recv[i]) (void)hipFree(g->p2p.recv[i]);
-      if (g->p2p.flags[i]) (void)hipFree(g->p2p.flags[i]);
+      g->p2p.recv[i].reset();
+      g->p2p.flags[i].reset();
     }
     return DSOPP_HIP_OK;
   };
   try {
     g->poisoned.store(false);  // (the release job itself must run)
     if (g->p2p.error)
-      for (int s = 0; s < g->n; ++s) g->p2p.error[s] = 0;
+      for (int s = 0; s < g->n; ++s) g->p2p.error.get()[s] = 0;
     if (!g->pool.threads.empty())
       g->pool.run(release);
     else
@@ -648,11 +647,7 @@ void dsopp_hip_window_group_destroy(dsopp_hip_window_group *g) {
   } catch (...) {
   }
   g->pool.stop();
-  if (g->p2p.error) (void)hipHostFree(g->p2p.error);
-  if (g->reducer.ev_out) {
-    (void)hipSetDevice(g->device[0]);
-    (void)hipEventDestroy(g->reducer.ev_out);
-  }
+  if (g->reducer.ev_out) (void)hipSetDevice(g->device[0]);  // (where the reducer's closing event was created)
   delete g;
 }
 
