@@ -768,9 +768,6 @@ struct AlignPyramidResult {
 };
 #ifdef DSOPP_HIP_STAMPS
 #define AP_STAMP(i) do { if (blk == 0 && tid == 0 && lvl == 0 && pass == 2) h_out->stamps[i] = wall_clock64(); } while (0)
-#elif defined(DSOPP_HIP_MARKS)
-// ISA reading aid (scripts/isa_phase_count.py): a comment line in the assembly at every phase boundary
-#define AP_STAMP(i) asm volatile("; ##AP_MARK " #i)
 #else
 #define AP_STAMP(i) do { } while (0)
 #endif
@@ -860,12 +857,6 @@ __device__ __forceinline__ int alignPackedIndex(int lane, int v) {
   if (j == 9) return i == 8 ? 44 : (i == 9 ? 45 : -1);
   return -1;
 }
-
-#ifdef DSOPP_HIP_MARKS
-#define PD_MARK(i) asm volatile("; ##PD_MARK " #i)
-#else
-#define PD_MARK(i) do { } while (0)
-#endif
 
 /**
  * 8 x 8 NormalLinearSystem::solve for the persistent kernel's control step: (H + lambda diag(H)) x = b by an LDL^T factorisation, written for
@@ -973,7 +964,6 @@ __device__ __forceinline__ void pyramidDecide(AlignControl &c, const double *tot
 #pragma unroll
   for (int a = 0; a < 8; ++a) step_sq += stepv[a] * stepv[a];
   const bool conv_p = step_sq < parameter_tolerance * ((a0 * a0 + a1 * a1) + parameter_tolerance);
-  PD_MARK(1);
   const bool accept = !first && has && better;   // acceptStep (eigen_pose_alignment.cpp:208-212)
   const bool take = first || accept;             // the evaluated state's system becomes the accepted state's
   iteration += first ? 0 : 1;
@@ -987,17 +977,14 @@ __device__ __forceinline__ void pyramidDecide(AlignControl &c, const double *tot
   ab_eps0 = accept ? cand_ab0 : ab_eps0;
   ab_eps1 = accept ? cand_ab1 : ab_eps1;
   // ---- calculateStep (eigen_pose_alignment.cpp:194-206): (H + lambda diag(H)) step = b from the packed sums of the accepted state
-  PD_MARK(2);
   // (a pointer the compiler cannot see through: left to itself it reads BOTH systems and selects entry by entry)
   using LdsDouble = const __attribute__((address_space(3))) double;
   LdsDouble *src = take ? (LdsDouble *)tot : (LdsDouble *)acc_sys;
   asm volatile("" : "+v"(src));
   double stepn[8];
   solve8Ldl([&](int i, int j) { return src[j * 8 - j * (j - 1) / 2 + (i - j)]; }, [&](int i) { return src[36 + i]; }, lambda, stepn);
-  PD_MARK(3);
   if (take && lane < 44) acc_sys[lane] = sys_new;  // (behind the solve's reads: nothing waits for it)
   const Rigid E = rigidExp(stepn);
-  PD_MARK(4);
   double Em[12], candTn[12];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -1006,7 +993,6 @@ __device__ __forceinline__ void pyramidDecide(AlignControl &c, const double *tot
     Em[4 * i + 3] = E.t[i];
   }
   mat34Compose(Em, Ttr, candTn);
-  PD_MARK(5);
   // ---- one batch of stores (lane 0)
   if (lane == 0) {
 #pragma unroll

@@ -584,16 +584,10 @@ __device__ __forceinline__ void estimateDepthsBody(const DepthFrame &f, const De
   finish(2 * error_step * 10.0, kImGood);
 }
 
-#ifndef DSOPP_DEPTH_WAVES
-#define DSOPP_DEPTH_WAVES 4  // 141 -> 128 registers: 4 waves per SIMD, 90.9 -> 88.9 us at 14 000 landmarks (5 and 6 spill: 105 / 130 us)
-#endif
-#if DSOPP_DEPTH_WAVES > 0
-#define DSOPP_DEPTH_BOUNDS __launch_bounds__(64, DSOPP_DEPTH_WAVES)
-#else
-#define DSOPP_DEPTH_BOUNDS __launch_bounds__(64)
-#endif
+// __launch_bounds__(64, 4) on the estimator's kernels: 141 -> 128 registers, 4 waves per SIMD, 90.9 -> 88.9 us at 14 000 landmarks
+// (5 and 6 spill: 105 / 130 us)
 template <typename S>
-__global__ void DSOPP_DEPTH_BOUNDS estimateDepthsKernel(DepthFrame f, DepthLandmarks L) {
+__global__ void __launch_bounds__(64, 4) estimateDepthsKernel(DepthFrame f, DepthLandmarks L) {
   extern __shared__ double energies[];  // [f.max_line]
   estimateDepthsBody<S>(f, L, blockIdx.x, energies);
 }
@@ -601,7 +595,7 @@ __global__ void DSOPP_DEPTH_BOUNDS estimateDepthsKernel(DepthFrame f, DepthLandm
 /** the same over several keyframes' sets in one launch (blockIdx.y = set): the estimator runs for every keyframe of the
  *  window on every frame (monocular_tracker.cpp:74-102), so one dispatch fills the machine instead of seven partial ones */
 template <typename S>
-__global__ void DSOPP_DEPTH_BOUNDS estimateDepthsBatchKernel(const DepthFrame *__restrict__ frames, const DepthLandmarks *__restrict__ landmarks) {
+__global__ void __launch_bounds__(64, 4) estimateDepthsBatchKernel(const DepthFrame *__restrict__ frames, const DepthLandmarks *__restrict__ landmarks) {
   extern __shared__ double energies[];
   const DepthFrame f = frames[blockIdx.y];
   if (static_cast<int>(blockIdx.x) >= f.n) return;
@@ -618,7 +612,7 @@ struct ArgTables {
 };
 static_assert(sizeof(ArgTables) <= 3840, "the tables must fit the kernel-argument segment next to nothing else");
 template <typename S>
-__global__ void DSOPP_DEPTH_BOUNDS estimateDepthsBatchArgKernel(ArgTables t) {
+__global__ void __launch_bounds__(64, 4) estimateDepthsBatchArgKernel(ArgTables t) {
   extern __shared__ double energies[];
   const DepthFrame f = t.f[blockIdx.y];
   if (static_cast<int>(blockIdx.x) >= f.n) return;

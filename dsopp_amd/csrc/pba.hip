@@ -106,12 +106,6 @@ struct dsopp_hip_window {
     return kTwoStageMinChunks;
   }
   bool twoStage() const { return deterministic || n_schur_blocks > twoStageMinChunks(); }
-  /** chunks above which calculateIdepths runs as its own kernel in front of the sweep instead of inside it (the fused form re-reads a
-   *  landmark's Schur row once per (landmark, target) item) */
-  int backsubSplitMinChunks() const {
-    static const int override_chunks = std::getenv("DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS") ? std::atoi(std::getenv("DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS")) : 0;  // tuning aid
-    return override_chunks > 0 ? override_chunks : twoStageMinChunks();
-  }
   DeviceMem<unsigned> d_bs_flag;  // ticket counter + hand-over buffers of the back-substitution inside the solve launch (pba_solve_combined.hpp)
   unsigned bs_seq = 0, bs_ticket_base = 0;
   PinnedMem<int> h_bs_fault;  // raised by a landmark workgroup of the solve launch whose bounded wait for the step ran out (checkSolveLaunchFault)
@@ -934,7 +928,7 @@ struct SweepExtras {
   const int *run_flag = nullptr;
   bool fused_lin_backsub = false;
   bool combined = false;  // the following reduction builds the combined system: only that much has to be zeroed
-  bool external_backsub = false;  // calculateIdepths ran in backsubKernel in front of this sweep (large windows)
+  bool external_backsub = false;  // calculateIdepths ran in front of this sweep (the solve launch, or backsubKernel on large windows)
   bool write_fej = false;         // opening linearisation of a fused solve: the sweep takes the first-estimate snapshot itself
 };
 
@@ -1508,8 +1502,8 @@ void launchRestore(W &w) {
  *                 + one workgroup (64 on the two-stage path) that adds up K1's energy scalars
  *             K3  prologue: decide step_r from those sums, apply accept / reject (the landmark workgroups);
  *                 the solving workgroup: solve -> step_{r+1}; the landmark workgroups: calculateIdepths for step_{r+1} as soon as it is
- *                 published, under the solver's tail (round 4; until then a kernel of its own in front of K1 on large windows, fused into
- *                 K1 on small ones: DSOPP_HIP_K3_BACKSUB=0)
+ *                 published, under the solver's tail.  Windows with optimize_idepths = 0 or without Schur chunks have no
+ *                 inverse-depth step to wait for: their rounds keep the sweep-side forms (see the round loop)
  * (large windows: K2 = partial systems + ordered sum, two launches)
  * max_iterations + 1 rounds, one host synchronisation.  A rejected step without force_accept costs one extra round (the
  * sweep re-linearises at the reverted state, which reproduces the system the reference keeps via linear_system_valid).
@@ -1563,16 +1557,13 @@ void lmSolveFusedEnqueue(W &w) {
   const int rounds = (w.opt.force_accept ? w.opt.max_iterations : 2 * w.opt.max_iterations) + 1;
   bool result_written_by_kernel = false;
   // calculateIdepths inside the solve launch (its landmark workgroups wait for the step under the factorisation): no back-substitution
-  // kernel in front of the sweeps of large windows, no Schur-row reads in the sweeps of small ones.  DSOPP_HIP_K3_BACKSUB=0: the round-3 flow
-  static const int k3_env = std::getenv("DSOPP_HIP_K3_BACKSUB") ? std::atoi(std::getenv("DSOPP_HIP_K3_BACKSUB")) : 1;
-  const bool k3_backsub = k3_env != 0 && w.opt.optimize_idepths && w.n_schur_blocks > 0;
-  // atomics path of an unsharded window of up to 8 keyframes: the reduction launch accumulates into several copies of the combined system
-  // and the solve launch adds them while loading (the queue of same-address f64 atomics is that launch's tail).  DSOPP_HIP_COMB_COPIES=1: off
-  static const int comb_copies_env = std::getenv("DSOPP_HIP_COMB_COPIES") ? std::atoi(std::getenv("DSOPP_HIP_COMB_COPIES")) : 4;
+  // kernel in front of the sweeps of large windows, no Schur-row reads in the sweeps of small ones
+  const bool k3_backsub = w.opt.optimize_idepths && w.n_schur_blocks > 0;
+  // atomics path of an unsharded window of up to 8 keyframes: the reduction launch accumulates into kMaxCombCopies copies of the combined
+  // system and the solve launch adds them while loading (the queue of same-address f64 atomics is that launch's tail).
+  // DSOPP_HIP_COMB_COPIES_MIN_CHUNKS (test aid): the window size, in chunks of 64 landmarks, from which the copies are used
   static const int comb_copies_min_chunks = std::getenv("DSOPP_HIP_COMB_COPIES_MIN_CHUNKS") ? std::atoi(std::getenv("DSOPP_HIP_COMB_COPIES_MIN_CHUNKS")) : 80;
-  w.comb_copies_active = (!w.twoStage() && !w.allreduce && w.F() <= 7 && w.n_schur_blocks >= comb_copies_min_chunks)
-                             ? std::max(1, std::min(comb_copies_env, kMaxCombCopies))
-                             : 1;
+  w.comb_copies_active = (!w.twoStage() && !w.allreduce && w.F() <= 7 && w.n_schur_blocks >= comb_copies_min_chunks) ? kMaxCombCopies : 1;
   struct CopiesReset {
     W &w;
     ~CopiesReset() { w.comb_copies_active = 1; }
@@ -1587,7 +1578,7 @@ void lmSolveFusedEnqueue(W &w) {
     ex.combined = true;
     ex.write_fej = r == 0 && sweep_takes_fej;
     // the closing round only has to evaluate the last candidate (no linear system is built from it): residual-only sweep
-    const bool large = w.n_schur_blocks > w.backsubSplitMinChunks();
+    const bool large = w.n_schur_blocks > w.twoStageMinChunks();
     if (k3_backsub) {
       // calculateIdepths for this round's candidate ran in the solve launch that produced its step (launchSolveCombined): the sweep
       // only reads the inverse-depth steps
@@ -1595,6 +1586,8 @@ void lmSolveFusedEnqueue(W &w) {
       ex.external_backsub = true;
       launchSweep(w, /*lin=*/r + 1 < rounds, true, false, cin, false, 0.0, ex);
     } else if (large && r + 1 == rounds) {
+      // (this branch and the two below: windows with optimize_idepths = 0 or without Schur chunks, whose solve launch back-substitutes
+      // nothing)
       // closing round of a large window: the same split (the residual-only sweep with the back-substitution fused in took 115 us
       // at 12 frames / 50 000 landmarks against 10 + 47 us as two kernels)
       launchBacksub(w, 0.0, cin, ex.ublk_read, /*gate_on_pending=*/true);
@@ -3355,15 +3348,12 @@ int dsopp_hip_window_time_kernel(dsopp_hip_window *w, int kernel_class, int repe
         case DSOPP_HIP_KERNEL_SWEEP_ENERGY: launchSweep(*w, false, true, false); break;
         case DSOPP_HIP_KERNEL_SWEEP_LINEARIZE_LOOP: {
           // exactly the launch of lmSolveFusedEnqueue's rounds >= 1: linearises at the candidate state whose inverse-depth steps the
-          // solve launch in front of it left (DSOPP_HIP_K3_BACKSUB=0: the round-3 flow — the sweep reads the Schur rows / pose step of
-          // the previous round and back-substitutes itself)
-          static const int k3_env = std::getenv("DSOPP_HIP_K3_BACKSUB") ? std::atoi(std::getenv("DSOPP_HIP_K3_BACKSUB")) : 1;
+          // solve launch in front of it left
           SweepExtras ex;
           ex.ublk_read = 0;
           ex.ublk_write = 1;
-          ex.fused_lin_backsub = k3_env == 0;
-          ex.external_backsub = k3_env != 0;
-          launchSweep(*w, true, true, false, nullptr, k3_env == 0, 1e-5, ex);
+          ex.external_backsub = true;
+          launchSweep(*w, true, true, false, nullptr, false, 1e-5, ex);
           break;
         }
         case DSOPP_HIP_KERNEL_SCHUR: {  // as the fused loop launches it (combined system), without the decision prologue

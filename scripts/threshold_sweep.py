@@ -1,4 +1,4 @@
-"""tuning aid: per-iteration time of a window for the current DSOPP_HIP_TWO_STAGE_MIN_CHUNKS / DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS
+"""tuning aid: per-iteration time of a window for the current DSOPP_HIP_TWO_STAGE_MIN_CHUNKS
     python scripts/threshold_sweep.py F P [seed]"""
 import os
 import sys
@@ -21,4 +21,4 @@ for _ in range(9):
     done, _ = g.optimize_repeated(14)
     ts.append((time.perf_counter() - t0) / done)
 ts.sort()
-print(f"F={F} P={P} two_stage_min={os.environ.get('DSOPP_HIP_TWO_STAGE_MIN_CHUNKS','-')} backsub_split_min={os.environ.get('DSOPP_HIP_BACKSUB_SPLIT_MIN_CHUNKS','-')}: {ts[len(ts)//2]*1e6:.1f} us per iteration")
+print(f"F={F} P={P} two_stage_min={os.environ.get('DSOPP_HIP_TWO_STAGE_MIN_CHUNKS','-')}: {ts[len(ts)//2]*1e6:.1f} us per iteration")

@@ -475,50 +475,41 @@ def test_large_window_two_stage_is_bit_reproducible():
     g.close()
 
 
-_K3_BACKSUB_SCRIPT = r"""
-import sys
-import numpy as np
-from dsopp_amd import capi, synthetic as syn
-out = {}
-for name, (F, P, W, H, seed) in {"small": (5, 600, 320, 240, 3), "wide": (10, 1500, 320, 240, 5), "large": (7, 14000, 640, 480, 7),
-                                   "fourteen": (14, 1800, 320, 240, 9)}.items():  # (13 - 16 keyframes: four frame slots per lane, ONE prefetched pass)
-    win = syn.make_window(num_frames=F, num_points=P, width=W, height=H, seed=seed)
-    g = capi.HipWindow(capi.default_pba_options()); syn.load_window(g, win)
+def _solve_and_repeat(win, lm_mode):
+    """solve(), then optimize_repeated(21) from the window's snapshot: (energy, iterations, n_valid, poses, inverse depths, repeated
+    iterations, repeated energy)"""
+    from dsopp_amd import capi
+    g = capi.HipWindow(capi.default_pba_options())
+    syn.load_window(g, win)
+    g.set_lm_mode(lm_mode)
     e, it, nv = g.solve()
     poses = np.concatenate([np.concatenate(g.get_pose(f.frame_id)) for f in win.frames])
     idepths = np.concatenate([g.get_landmarks(f.frame_id, with_hpib=False)["idepth"] for f in win.frames])
-    # the same window again through a batch of back-to-back solves (every solve launch draws its own tickets / sequence number)
-    g.snapshot(); g.restore()
+    # the same window again through a batch of back-to-back solves (every solve launch draws its own tickets / sequence number).  One
+    # iteration per solve: the fused loop plans a batch's budgets before its results return, the host-driven stages after every solve,
+    # so a solve that converges early would split the 21 iterations differently in the two modes and end on another last solve
+    g.snapshot()
+    g.restore()
+    g.set_max_iterations(1)
     n, e_rep = g.optimize_repeated(21)
-    out[name] = (e, it, nv, poses, idepths, n, e_rep)
     g.close()
-np.savez(sys.argv[1], **{f"{k}_{i}": np.asarray(v) for k, t in out.items() for i, v in enumerate(t)})
-print("k3 flow ok")
-"""
+    return e, it, nv, poses, idepths, n, e_rep
 
 
-def test_idepth_back_substitution_inside_the_solve_launch_equals_the_kernel_flow(tmp_path):
-    """calculateIdepths by the landmark workgroups of the solve launch (default) against the round-3 flow (DSOPP_HIP_K3_BACKSUB=0, read
-    once per process: a back-substitution kernel on large windows, fused into the sweep on small ones) — 256- and 512-thread solve
-    kernels, atomic and two-stage Schur builds: same iterations and residual counts, energies / poses / inverse depths to rounding."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = {}
-    for flow in ("1", "0"):
-        path = str(tmp_path / f"flow{flow}.npz")
-        env = dict(os.environ, DSOPP_HIP_K3_BACKSUB=flow, PYTHONPATH=root)
-        r = subprocess.run([sys.executable, "-c", _K3_BACKSUB_SCRIPT, path], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and "k3 flow ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
-        res[flow] = np.load(path)
-    a, b = res["1"], res["0"]
-    for name in ("small", "wide", "large", "fourteen"):
-        assert int(a[f"{name}_1"]) == int(b[f"{name}_1"]) and int(a[f"{name}_2"]) == int(b[f"{name}_2"]), name
-        assert abs(float(a[f"{name}_0"]) - float(b[f"{name}_0"])) <= 1e-9 * abs(float(b[f"{name}_0"])), name
-        assert np.abs(a[f"{name}_3"] - b[f"{name}_3"]).max() <= 1e-9, name
-        assert np.abs(a[f"{name}_4"] - b[f"{name}_4"]).max() <= 1e-8 * max(1.0, np.abs(b[f"{name}_4"]).max()), name
-        assert int(a[f"{name}_5"]) == int(b[f"{name}_5"]) and abs(float(a[f"{name}_6"]) - float(b[f"{name}_6"])) <= 1e-9 * abs(float(b[f"{name}_6"])), name
+def test_idepth_back_substitution_inside_the_solve_launch_equals_the_kernel_flow():
+    """calculateIdepths by the landmark workgroups of the solve launch (the fused loop, default) against the host-driven stages
+    (lm_mode 1, which back-substitute in a kernel of their own) — 256- and 512-thread solve kernels, atomic and two-stage Schur builds:
+    same iterations and residual counts, energies / poses / inverse depths to rounding."""
+    windows = {"small": (5, 600, 320, 240, 3), "wide": (10, 1500, 320, 240, 5), "large": (7, 14000, 640, 480, 7),
+               "fourteen": (14, 1800, 320, 240, 9)}  # (13 - 16 keyframes: four frame slots per lane, ONE prefetched pass)
+    for name, (F, P, W, H, seed) in windows.items():
+        win = syn.make_window(num_frames=F, num_points=P, width=W, height=H, seed=seed)
+        a, b = _solve_and_repeat(win, lm_mode=0), _solve_and_repeat(win, lm_mode=1)
+        assert a[1] == b[1] and a[2] == b[2], name
+        assert abs(a[0] - b[0]) <= 1e-9 * abs(b[0]), name
+        assert np.abs(a[3] - b[3]).max() <= 1e-9, name
+        assert np.abs(a[4] - b[4]).max() <= 1e-8 * max(1.0, np.abs(b[4]).max()), name
+        assert a[5] == b[5] and abs(a[6] - b[6]) <= 1e-9 * abs(b[6]), name
 
 
 _COMB_COPIES_SCRIPT = r"""
@@ -545,27 +536,26 @@ def test_combined_system_accumulated_in_several_copies_equals_the_single_copy(tm
     """The reduction launch of an unsharded window on the atomics path may spread its f64 atomics over several copies of the combined
     system, which the solve launch adds while loading (pba.hip: comb_copies_active; by default from 80 chunks of 64 landmarks up to the
     two-stage threshold, at most 7 keyframes).  Forced on for every window (DSOPP_HIP_COMB_COPIES_MIN_CHUNKS=1, read once per process)
-    with 4 and with 2 copies against the single copy: same iterations and residual counts, energies / poses / inverse depths to rounding."""
+    against a threshold no window reaches (the single copy): same iterations and residual counts, energies / poses / inverse depths to
+    rounding."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
-    for copies in ("1", "2", "4"):
-        path = str(tmp_path / f"copies{copies}.npz")
-        env = dict(os.environ, DSOPP_HIP_COMB_COPIES=copies, DSOPP_HIP_COMB_COPIES_MIN_CHUNKS="1", PYTHONPATH=root)
+    for min_chunks in ("1", "1000000"):
+        path = str(tmp_path / f"min_chunks{min_chunks}.npz")
+        env = dict(os.environ, DSOPP_HIP_COMB_COPIES_MIN_CHUNKS=min_chunks, PYTHONPATH=root)
         r = subprocess.run([sys.executable, "-c", _COMB_COPIES_SCRIPT, path], cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "comb copies ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
-        res[copies] = np.load(path)
-    b = res["1"]
-    for copies in ("2", "4"):
-        a = res[copies]
-        for name in ("small", "seven", "mid"):
-            assert int(a[f"{name}_1"]) == int(b[f"{name}_1"]) and int(a[f"{name}_2"]) == int(b[f"{name}_2"]), (copies, name)
-            assert abs(float(a[f"{name}_0"]) - float(b[f"{name}_0"])) <= 1e-9 * abs(float(b[f"{name}_0"])), (copies, name)
-            assert np.abs(a[f"{name}_3"] - b[f"{name}_3"]).max() <= 1e-9, (copies, name)
-            assert np.abs(a[f"{name}_4"] - b[f"{name}_4"]).max() <= 1e-8 * max(1.0, np.abs(b[f"{name}_4"]).max()), (copies, name)
-            assert int(a[f"{name}_5"]) == int(b[f"{name}_5"]) and abs(float(a[f"{name}_6"]) - float(b[f"{name}_6"])) <= 1e-9 * abs(float(b[f"{name}_6"])), (copies, name)
+        res[min_chunks] = np.load(path)
+    a, b = res["1"], res["1000000"]
+    for name in ("small", "seven", "mid"):
+        assert int(a[f"{name}_1"]) == int(b[f"{name}_1"]) and int(a[f"{name}_2"]) == int(b[f"{name}_2"]), name
+        assert abs(float(a[f"{name}_0"]) - float(b[f"{name}_0"])) <= 1e-9 * abs(float(b[f"{name}_0"])), name
+        assert np.abs(a[f"{name}_3"] - b[f"{name}_3"]).max() <= 1e-9, name
+        assert np.abs(a[f"{name}_4"] - b[f"{name}_4"]).max() <= 1e-8 * max(1.0, np.abs(b[f"{name}_4"]).max()), name
+        assert int(a[f"{name}_5"]) == int(b[f"{name}_5"]) and abs(float(a[f"{name}_6"]) - float(b[f"{name}_6"])) <= 1e-9 * abs(float(b[f"{name}_6"])), name
 
 
 def test_residual_list_that_ends_inside_a_landmark_batch():
