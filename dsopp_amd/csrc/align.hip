@@ -36,14 +36,15 @@ struct AlignFrameDev {
   double ab0[2];
 };
 
-/** LM state of the aligner, double-buffered by launch parity */
+/** LM state of the aligner, double-buffered by launch parity.  A linear system is kept packed as the sums deliver it: the upper
+ *  triangle of H row by row (36) | b (8), the affine prior folded in. */
 struct AlignControl {
   double T_tr[12];       // accepted state: [R | t] rows of T_target_reference
   double ab_eps[2];
   double cand_T[12];     // candidate evaluated by the launch that reads this block
   double cand_ab[2];
-  double H[64], b[8];    // system_ of the accepted state (last linearize)
-  double H_used[64];     // system_ used by the most recent calculateStep (== problem.hessian())
+  double sys[44];        // system_ of the accepted state (last linearize)
+  double sys_used[44];   // system_ used by the most recent calculateStep (== problem.hessian()); dsopp_hip_aligner_solve only
   double step[8];
   double lambda;
   double energy;         // result.energy
@@ -52,15 +53,14 @@ struct AlignControl {
   int active;
   int iteration;
   int have_candidate;    // 0: the evaluated state IS the accepted state (first launch)
-  int linear_system_valid;
-  int pad0, pad1;
+  int pad[3];            // size a multiple of 16 bytes: the LDS arrays behind the block in alignPyramidKernel keep their b128 accesses
 };
 
 struct AlignParams {
   double sigma_huber;
   double affine_reg[2];
   double function_tolerance, parameter_tolerance;
-  double decrease_on_accept, increase_on_reject;
+  double inv_decrease, increase_on_reject;  // inv_decrease = 1 / decrease_on_accept, exact: the control step multiplies
   int max_iterations;
   int n_points;
   int n_blocks;
@@ -86,31 +86,29 @@ __device__ __forceinline__ double alignRcp(double x) {
 }
 __device__ __forceinline__ float alignRcp(float x) { return 1.0f / x; }
 
-/** 1/sqrt(x) for x > 0: hardware estimate + two Newton steps (~1 ulp); a libm sqrt + division pair costs ~180 cycles on
- *  the single thread that runs the LM control, this a dozen instructions */
-__device__ inline double rsqrtNewton(double x) {
-  const double h = 0.5 * x;
-  double r = __builtin_amdgcn_rsq(x);  // v_rsq_f64, 2^-23 relative: no f32 round trip on the dependent chain
-  r = fma(r, fma(-h * r, r, 0.5), r);
-  r = fma(r, fma(-h * r, r, 0.5), r);
-  return r;
-}
-
-/** 8x8 NormalLinearSystem::solve, single thread.  The reference solves the Jacobi-scaled system p H p, p = 1 / sqrt(diag + 10)
- *  (normal_linear_system.cpp:10-16,52-59) with a pivoted LDL^T; a Cholesky factorisation is invariant under symmetric diagonal
- *  scaling, so the scaling itself is not carried out (as in the window's K x K solve, pba_solve_combined.hpp) — only the zero-pivot
- *  guard refers to the scaled pivot d / (diag + 10).  The control step runs on one wave at one instruction per ~4.7 cycles: the
- *  160 instructions of the scaling were 0.35 us of every LM pass. */
+/**
+ * 8 x 8 NormalLinearSystem::solve of the LM control step: (H + lambda diag(H)) x = b by an LDL^T factorisation, written for LATENCY.  One
+ * wave runs this alone, in order, at ~8 cycles per dependent f64 operation: what it costs is the length of its dependency chain, not its
+ * instruction count.  Hence
+ *   * right-looking: as soon as a pivot's reciprocal is known the whole trailing matrix is updated by independent FMAs, which the
+ *     scheduler interleaves with the NEXT pivot's reciprocal chain (the left-looking form the compiler made of a Cholesky put a
+ *     dot-product chain in front of every pivot);
+ *   * the right-hand side is carried as a ninth column, so the forward substitution costs no extra chain;
+ *   * LDL^T: a reciprocal (v_rcp_f64 + 2 Newton steps, 5 dependent operations) per pivot instead of a reciprocal square root (8), unit
+ *     triangles in the substitutions;
+ *   * no branches: a basic-block boundary is a wall for the scheduler.  A pivot that fails the guard (the reference's zero-pivot test on
+ *     the Jacobi-scaled pivot d / (diag + 10), normal_linear_system.cpp:10-16,52-59) gets reciprocal 0: its column, its y and its x vanish.
+ * Chain: 8 x (reciprocal 5 + scale 1 + update 1) + back substitution 8 = ~64 dependent operations (the Cholesky form: ~170).
+ */
 template <typename GetH, typename GetB>
-__device__ __forceinline__ void solve8Impl(GetH getH /* (i, j), j <= i */, GetB getB, double lambda, double *x) {
-  // the system is H + lambda * diag(H) (calculateStep, eigen_pose_alignment.cpp:194-198), formed on the fly
-  double A[36], y[8], linv[8], guard[8];
+__device__ __forceinline__ void solve8Ldl(GetH getH /* (i, j), j <= i */, GetB getB, double lambda, double *x) {
+  double A[36], y[8], dinv[8], guard[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
 #pragma unroll
     for (int j = 0; j < i; ++j) A[i * (i + 1) / 2 + j] = getH(i, j);
     const double hii = getH(i, i);
-    const double dg = hii + hii * lambda;
+    const double dg = hii + hii * lambda;  // H + lambda * diag(H) (calculateStep, eigen_pose_alignment.cpp:194-198)
     A[i * (i + 1) / 2 + i] = dg;
     guard[i] = 1e-300 * (dg + 10.0);
     y[i] = getB(i);
@@ -119,53 +117,143 @@ __device__ __forceinline__ void solve8Impl(GetH getH /* (i, j), j <= i */, GetB 
   for (int k = 0; k < 8; ++k) {
     const double d = A[k * (k + 1) / 2 + k];
     const bool ok = d > guard[k];
-    const double inv = ok ? rsqrtNewton(ok ? d : 1.0) : 0.0;
-    linv[k] = inv;
-    A[k * (k + 1) / 2 + k] = ok ? d * inv : 0.0;
+    double r = __builtin_amdgcn_rcp(d);  // (a pivot that fails the guard: whatever this becomes is dropped by the select below)
+    r = fma(fma(-d, r, 1.0), r, r);
+    r = fma(fma(-d, r, 1.0), r, r);
+    const double inv = ok ? r : 0.0;
+    dinv[k] = inv;
+    // column k of L (unit diagonal): l_ik = a_ik / d_k, kept beside the unscaled a_ik the update needs
+    double l[8];
 #pragma unroll
-    for (int i = k + 1; i < 8; ++i) A[i * (i + 1) / 2 + k] *= inv;
+    for (int i = k + 1; i < 8; ++i) l[i] = A[i * (i + 1) / 2 + k] * inv;
 #pragma unroll
     for (int j = k + 1; j < 8; ++j)
 #pragma unroll
-      for (int i = j; i < 8; ++i) A[i * (i + 1) / 2 + j] -= A[i * (i + 1) / 2 + k] * A[j * (j + 1) / 2 + k];
-  }
+      for (int i = j; i < 8; ++i) A[i * (i + 1) / 2 + j] = fma(-l[i], A[j * (j + 1) / 2 + k], A[i * (i + 1) / 2 + j]);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    double s = y[i];
-#pragma unroll
-    for (int j = 0; j < i; ++j) s -= A[i * (i + 1) / 2 + j] * y[j];
-    y[i] = s * linv[i];  // 0 for a zero pivot
+    for (int i = k + 1; i < 8; ++i) {
+      y[i] = fma(-l[i], y[k], y[i]);
+      A[i * (i + 1) / 2 + k] = l[i];
+    }
   }
+  // D z = y, L^T x = z
 #pragma unroll
   for (int i = 7; i >= 0; --i) {
-    double s = y[i];
+    double sacc = y[i] * dinv[i];
 #pragma unroll
-    for (int j = i + 1; j < 8; ++j) s -= A[j * (j + 1) / 2 + i] * y[j];
-    y[i] = s * linv[i];
+    for (int j = i + 1; j < 8; ++j) sacc = fma(-A[j * (j + 1) / 2 + i], y[j], sacc);
+    y[i] = sacc;
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) x[i] = y[i];
 }
 
-/** from the stored 8 x 8 system (row-major H, b) */
-__device__ inline void solve8(const double *Hin, double lambda, const double *bin, double *x) {
-  solve8Impl([&](int i, int j) { return Hin[8 * i + j]; }, [&](int i) { return bin[i]; }, lambda, x);
+/** the affine prior (eigen_pose_alignment.cpp:183-190) for entry e of the packed sums: H66 and H77 (33, 35) get reg0 and reg1, b6 and
+ *  b7 (42, 43) get reg0 tab0 and reg1 tab1, every other entry 0 */
+__device__ __forceinline__ double alignPrior(int e, double reg0, double reg1, double tab0, double tab1) {
+  const double pc0 = e == 33 ? reg0 : (e == 35 ? reg1 : 0.0);
+  const double pc1 = e == 42 ? reg0 : 0.0, pc2 = e == 43 ? reg1 : 0.0;
+  return fma(pc2, tab1, fma(pc1, tab0, pc0));
 }
 
-/** straight from a pass's sums (packed upper triangle 36 | b 8) plus the affine prior (eigen_pose_alignment.cpp:174-190): what the
- *  control step solves when it has just taken a new system — without the round trip of writing the expanded system to LDS and
- *  reading it back */
-__device__ inline void solve8FromSums(const double *red, const double *affine_reg, double tab0, double tab1, double lambda, double *x) {
-  solve8Impl(
-      [&](int i, int j) {
-        const double v = red[j * 8 - j * (j - 1) / 2 + (i - j)];
-        return (i == j && i >= 6) ? v + affine_reg[i - 6] : v;
-      },
-      [&](int i) {
-        const double v = red[36 + i];
-        return i == 6 ? v + affine_reg[0] * tab0 : (i == 7 ? v + affine_reg[1] * tab1 : v);
-      },
-      lambda, x);
+/**
+ * The LM control step of one iteration (levenberg_marquardt_algorithm.hpp:77-128, eigen_pose_alignment.cpp:101-104,174-212), the one all
+ * three aligner kernels run: `tot` (LDS) holds the sums of the pass that evaluated the candidate in `c` (LDS), packed like c.sys with the
+ * affine prior folded in, + energy | n_valid; decides accept / reject, keeps or replaces the accepted state's system `acc_sys` (LDS: c.sys,
+ * or an array of the persistent kernel's own), solves for the next step and stores the next candidate.  Written in the form one wave
+ * executes fastest — one instruction per ~4.7 cycles whatever it does, so the step costs what its instruction count says:
+ *   * the solve reads ONE of the two packed systems through a selected pointer — one instance of the factorisation instead of two, no
+ *     expanded 8 x 8 copies;
+ *   * decisions are selects, not branches (the branchy form spent a third of its instructions on register copies at the joins);
+ *   * no f64 division: lambda / decrease_on_accept is a multiplication by its exact reciprocal (decrease_on_accept is 2), and
+ *     |e - e'| / e < tol is decided by |e - e'| < tol e outside a 1e-12 band around the threshold (inside it: the division).
+ * kRecordUsed: also keep the solved system in c.sys_used (dsopp_hip_aligner_solve reports it; estimatePose does not).
+ * All 64 lanes of one wave run it redundantly; lane 0 stores.
+ */
+template <bool kRecordUsed>
+__device__ __forceinline__ void alignDecide(AlignControl &c, const double *tot, double *acc_sys, double tgt_ab0, double tgt_ab1, double reg0, double reg1,
+                                            double function_tolerance, double parameter_tolerance, double inv_decrease, double increase, int max_iterations) {
+  const int lane = threadIdx.x & 63;
+  // ---- loads
+  const double cand_ab0 = c.cand_ab[0], cand_ab1 = c.cand_ab[1];
+  double ab_eps0 = c.ab_eps[0], ab_eps1 = c.ab_eps[1];
+  double energy = c.energy, lambda = c.lambda;
+  int n_valid = c.n_valid, converged = c.converged, iteration = c.iteration;
+  const bool first = c.have_candidate == 0;
+  double stepv[8], Ttr[12], candT[12];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) stepv[a] = c.step[a];
+#pragma unroll
+  for (int a = 0; a < 12; ++a) {
+    Ttr[a] = c.T_tr[a];
+    candT[a] = c.cand_T[a];
+  }
+  const double red_energy = tot[44], red_n = tot[45];
+  const double sys_new = lane < 44 ? tot[lane] : 0.0;
+  // ---- decision (uniform)
+  const double tab0 = tgt_ab0 + cand_ab0, tab1 = tgt_ab1 + cand_ab1;
+  const double e_eval = red_energy + 0.5 * (tab0 * reg0 * tab0 + tab1 * reg1 * tab1);
+  const int n_eval = static_cast<int>(red_n + 0.5);
+  const bool has = n_eval != 0, better = e_eval < energy;
+  const double diff = fabs(energy - e_eval), thr = function_tolerance * energy;
+  bool conv_f = diff < thr * (1.0 - 1e-12);
+  if (!conv_f && !(diff > thr * (1.0 + 1e-12))) conv_f = diff / energy < function_tolerance;  // on the threshold (or not a number): the reference's own expression
+  const double a0 = tgt_ab0 + ab_eps0, a1 = tgt_ab1 + ab_eps1;
+  double step_sq = 0;
+#pragma unroll
+  for (int a = 0; a < 8; ++a) step_sq += stepv[a] * stepv[a];
+  const bool conv_p = step_sq < parameter_tolerance * ((a0 * a0 + a1 * a1) + parameter_tolerance);
+  const bool accept = !first && has && better;   // acceptStep (eigen_pose_alignment.cpp:208-212)
+  const bool take = first || accept;             // the evaluated state's system becomes the accepted state's
+  iteration += first ? 0 : 1;
+  converged = (!first && has && (conv_f || (better && conv_p))) ? 1 : converged;
+  lambda = accept ? lambda * inv_decrease : ((!first && has) ? lambda * increase : lambda);  // rejectStep: the accepted state and its system stay
+  energy = take ? e_eval : energy;
+  n_valid = take ? n_eval : n_valid;
+  int active = first ? ((max_iterations > 0 && n_eval > 0) ? 1 : 0) : ((has && !converged && iteration < max_iterations) ? 1 : 0);
+#pragma unroll
+  for (int a = 0; a < 12; ++a) Ttr[a] = accept ? candT[a] : Ttr[a];
+  ab_eps0 = accept ? cand_ab0 : ab_eps0;
+  ab_eps1 = accept ? cand_ab1 : ab_eps1;
+  // ---- calculateStep (eigen_pose_alignment.cpp:194-206): (H + lambda diag(H)) step = b from the packed sums of the accepted state
+  // (a pointer the compiler cannot see through: left to itself it reads BOTH systems and selects entry by entry)
+  using LdsDouble = const __attribute__((address_space(3))) double;
+  LdsDouble *src = take ? (LdsDouble *)tot : (LdsDouble *)acc_sys;
+  asm volatile("" : "+v"(src));
+  double stepn[8];
+  solve8Ldl([&](int i, int j) { return src[j * 8 - j * (j - 1) / 2 + (i - j)]; }, [&](int i) { return src[36 + i]; }, lambda, stepn);
+  if (kRecordUsed && active && lane < 44) c.sys_used[lane] = src[lane];
+  if (take && lane < 44) acc_sys[lane] = sys_new;  // (behind the solve's reads: nothing waits for it)
+  const Rigid E = rigidExp(stepn);
+  double Em[12], candTn[12];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Em[4 * i + j] = E.R[3 * i + j];
+    Em[4 * i + 3] = E.t[i];
+  }
+  mat34Compose(Em, Ttr, candTn);
+  // ---- one batch of stores (lane 0)
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 12; ++a) {
+      c.T_tr[a] = Ttr[a];
+      c.cand_T[a] = candTn[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a) c.step[a] = stepn[a];
+    c.ab_eps[0] = ab_eps0;
+    c.ab_eps[1] = ab_eps1;
+    c.cand_ab[0] = ab_eps0 - stepn[6];
+    c.cand_ab[1] = ab_eps1 - stepn[7];
+    c.lambda = lambda;
+    c.energy = energy;
+    c.n_valid = n_valid;
+    c.converged = converged;
+    c.active = active;
+    c.iteration = iteration;
+    c.have_candidate = 1;
+  }
 }
 
 /** sample the reference intensities of the points: PatternPatch::getIntensities with PatternSize 1 (local_frame.hpp:384-388) */
@@ -179,212 +267,6 @@ __global__ void sampleReferenceKernel(const Texel<S> *__restrict__ img, int W, c
   const S dx = x - static_cast<S>(ix), dy = y - static_cast<S>(iy), dxdy = dx * dy;
   const Texel<S> *p = img + static_cast<size_t>(iy) * W + ix;
   intensity[i] = static_cast<double>(dxdy * p[W + 1].I + (dy - dxdy) * p[W].I + (dx - dxdy) * p[1].I + (S(1) - dx - dy + dxdy) * p[0].I);
-}
-
-/** The LM control step of one iteration (levenberg_marquardt_algorithm.hpp:77-128 unrolled over launches): `red` holds the
- *  sums of the pass that evaluated the candidate in `c` (H upper 36 | b 8 | energy | n_valid); decides accept / reject,
- *  keeps or replaces the linear system, solves for the next step and stores the next candidate.  Single thread. */
-__device__ inline void alignDecide(AlignControl &c, const double *red, const AlignFrameDev &tgt, const AlignParams &prm) {
-    // evaluated state = candidate (or the initial state): energy with the affine prior (eigen_pose_alignment.cpp:101-104)
-    const double tab0 = tgt.ab0[0] + c.cand_ab[0], tab1 = tgt.ab0[1] + c.cand_ab[1];
-    const double e_eval = red[44] + 0.5 * (tab0 * prm.affine_reg[0] * tab0 + tab1 * prm.affine_reg[1] * tab1);
-    const int n_eval = static_cast<int>(red[45] + 0.5);
-    bool take_system = false;
-    if (!c.have_candidate) {
-      // result = problem.calculateEnergy() before the loop (levenberg_marquardt_algorithm.hpp:82)
-      c.energy = e_eval;
-      c.n_valid = n_eval;
-      c.active = (prm.max_iterations > 0 && n_eval > 0) ? 1 : 0;
-      take_system = true;
-    } else {
-      c.iteration += 1;
-      if (n_eval == 0) {
-        c.active = 0;  // rejectStep(); break;
-      } else {
-        if (fabs(c.energy - e_eval) / c.energy < prm.function_tolerance) c.converged = 1;
-        if (e_eval < c.energy) {
-          // acceptStep (eigen_pose_alignment.cpp:208-212)
-          const double a0 = tgt.ab0[0] + c.ab_eps[0], a1 = tgt.ab0[1] + c.ab_eps[1];
-          double step_sq = 0;
-          for (int a = 0; a < 8; ++a) step_sq += c.step[a] * c.step[a];
-          if (step_sq < prm.parameter_tolerance * ((a0 * a0 + a1 * a1) + prm.parameter_tolerance)) c.converged = 1;
-          for (int a = 0; a < 12; ++a) c.T_tr[a] = c.cand_T[a];
-          c.ab_eps[0] = c.cand_ab[0];
-          c.ab_eps[1] = c.cand_ab[1];
-          c.energy = e_eval;
-          c.n_valid = n_eval;
-          c.lambda /= prm.decrease_on_accept;
-          take_system = true;
-        } else {
-          c.lambda *= prm.increase_on_reject;  // rejectStep: the accepted state and its system stay
-        }
-        if (c.converged || c.iteration >= prm.max_iterations) c.active = 0;
-      }
-    }
-    if (take_system) {
-      // system of the evaluated state: symmetric expansion of the 36 sums + affine prior block (eigen_pose_alignment.cpp:183-187)
-      int e = 0;
-      for (int a = 0; a < 8; ++a)
-        for (int b2 = a; b2 < 8; ++b2) {
-          c.H[8 * a + b2] = c.H[8 * b2 + a] = red[e];
-          ++e;
-        }
-      for (int a = 0; a < 8; ++a) c.b[a] = red[36 + a];
-      c.H[8 * 6 + 6] += prm.affine_reg[0];
-      c.H[8 * 7 + 7] += prm.affine_reg[1];
-      c.b[6] += prm.affine_reg[0] * tab0;
-      c.b[7] += prm.affine_reg[1] * tab1;
-    }
-    if (c.active) {
-      // calculateStep (eigen_pose_alignment.cpp:194-206): H + lambda * diag(H), leftIncrement, ab_eps -= step[6:8]
-      for (int a = 0; a < 64; ++a) c.H_used[a] = c.H[a];
-      double step[8];
-      solve8(c.H, c.lambda, c.b, step);
-#pragma unroll
-      for (int a = 0; a < 8; ++a) c.step[a] = step[a];
-      const Rigid E = rigidExp(step);
-      double Em[12];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Em[4 * i + j] = E.R[3 * i + j];
-        Em[4 * i + 3] = E.t[i];
-      }
-      mat34Compose(Em, c.T_tr, c.cand_T);
-      c.cand_ab[0] = c.ab_eps[0] - step[6];
-      c.cand_ab[1] = c.ab_eps[1] - step[7];
-      c.have_candidate = 1;
-    }
-}
-
-/**
- * alignDecide executed by ONE WAVE (all 64 lanes of wave 0, uniform control flow) on register copies.  The single-lane form
- * above works in place on the LDS control block: every access is an LDS instruction whose address the compiler cannot prove
- * distinct from the previous store, so the ~300 loads and stores of a control step serialise at one LDS latency each
- * (measured: 4.7 us per step, more than the sweep, the workgroup reduction and the cross-workgroup exchange together).
- * Here everything is loaded first (one LDS latency), the 8 x 8 system is expanded / copied one entry per lane, the decision
- * and the solve run in registers (redundantly in every lane: no cross-lane traffic), and the results leave in one batch of
- * stores.  Same arithmetic, operation for operation, as alignDecide.
- */
-__device__ inline void alignDecideWave(AlignControl &c, const double *red, const AlignFrameDev &tgt, const AlignParams &prm) {
-  const int lane = threadIdx.x & 63;
-  const int hi = lane >> 3, hj = lane & 7;
-  // ---- loads
-  const double cand_ab0 = c.cand_ab[0], cand_ab1 = c.cand_ab[1];
-  double ab_eps0 = c.ab_eps[0], ab_eps1 = c.ab_eps[1];
-  double energy = c.energy, lambda = c.lambda;
-  int n_valid = c.n_valid, converged = c.converged, active = c.active, iteration = c.iteration;
-  const int have_candidate = c.have_candidate;
-  double stepv[8], Ttr[12], candT[12];
-#pragma unroll
-  for (int a = 0; a < 8; ++a) stepv[a] = c.step[a];
-#pragma unroll
-  for (int a = 0; a < 12; ++a) {
-    Ttr[a] = c.T_tr[a];
-    candT[a] = c.cand_T[a];
-  }
-  const double red_energy = red[44], red_n = red[45];
-  const int lo8 = hi < hj ? hi : hj, hi8 = hi < hj ? hj : hi;
-  const double h_new = red[lo8 * 8 - lo8 * (lo8 - 1) / 2 + (hi8 - lo8)], h_old = c.H[lane];  // packed upper triangle, as alignDecide expands it
-  const double b_new = red[36 + hj], b_old = c.b[hj];
-  // ---- decision (uniform)
-  const double tab0 = tgt.ab0[0] + cand_ab0, tab1 = tgt.ab0[1] + cand_ab1;
-  const double e_eval = red_energy + 0.5 * (tab0 * prm.affine_reg[0] * tab0 + tab1 * prm.affine_reg[1] * tab1);
-  const int n_eval = static_cast<int>(red_n + 0.5);
-  bool take_system = false;
-  if (!have_candidate) {
-    energy = e_eval;
-    n_valid = n_eval;
-    active = (prm.max_iterations > 0 && n_eval > 0) ? 1 : 0;
-    take_system = true;
-  } else {
-    iteration += 1;
-    if (n_eval == 0) {
-      active = 0;
-    } else {
-      if (fabs(energy - e_eval) / energy < prm.function_tolerance) converged = 1;
-      if (e_eval < energy) {
-        const double a0 = tgt.ab0[0] + ab_eps0, a1 = tgt.ab0[1] + ab_eps1;
-        double step_sq = 0;
-#pragma unroll
-        for (int a = 0; a < 8; ++a) step_sq += stepv[a] * stepv[a];
-        if (step_sq < prm.parameter_tolerance * ((a0 * a0 + a1 * a1) + prm.parameter_tolerance)) converged = 1;
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Ttr[a] = candT[a];
-        ab_eps0 = cand_ab0;
-        ab_eps1 = cand_ab1;
-        energy = e_eval;
-        n_valid = n_eval;
-        lambda /= prm.decrease_on_accept;
-        take_system = true;
-      } else {
-        lambda *= prm.increase_on_reject;
-      }
-      if (converged || iteration >= prm.max_iterations) active = 0;
-    }
-  }
-  // ---- system of the accepted state: one entry per lane
-  double h = h_old, b = b_old;
-  if (take_system) {
-    h = h_new;
-    b = b_new;
-    if (lane == 8 * 6 + 6) h += prm.affine_reg[0];
-    if (lane == 8 * 7 + 7) h += prm.affine_reg[1];
-    if (hj == 6) b += prm.affine_reg[0] * tab0;
-    if (hj == 7) b += prm.affine_reg[1] * tab1;
-    c.H[lane] = h;
-    if (lane < 8) c.b[lane] = b;
-  }
-  double stepn[8], candTn[12], cand_abn0 = cand_ab0, cand_abn1 = cand_ab1;
-  int have_candidate_n = have_candidate;
-  if (active) {
-    c.H_used[lane] = h;
-    if (take_system) {
-      // the new system is solved from the sums it came from (same values, entry for entry, as the expansion stored above)
-      solve8FromSums(red, prm.affine_reg, tab0, tab1, lambda, stepn);
-    } else {
-      // (kept system: nothing was stored to c.H / c.b in this step)
-      solve8(c.H, lambda, c.b, stepn);
-    }
-    const Rigid E = rigidExp(stepn);
-    double Em[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Em[4 * i + j] = E.R[3 * i + j];
-      Em[4 * i + 3] = E.t[i];
-    }
-    mat34Compose(Em, Ttr, candTn);
-    cand_abn0 = ab_eps0 - stepn[6];
-    cand_abn1 = ab_eps1 - stepn[7];
-    have_candidate_n = 1;
-  } else {
-#pragma unroll
-    for (int a = 0; a < 8; ++a) stepn[a] = stepv[a];
-#pragma unroll
-    for (int a = 0; a < 12; ++a) candTn[a] = candT[a];
-  }
-  // ---- one batch of stores (lane 0)
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 12; ++a) {
-      c.T_tr[a] = Ttr[a];
-      c.cand_T[a] = candTn[a];
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) c.step[a] = stepn[a];
-    c.ab_eps[0] = ab_eps0;
-    c.ab_eps[1] = ab_eps1;
-    c.cand_ab[0] = cand_abn0;
-    c.cand_ab[1] = cand_abn1;
-    c.lambda = lambda;
-    c.energy = energy;
-    c.n_valid = n_valid;
-    c.converged = converged;
-    c.active = active;
-    c.iteration = iteration;
-    c.have_candidate = have_candidate_n;
-  }
 }
 
 /** per-pass constants of the sweep: reprojection matrices of the candidate pose, photometric parameters */
@@ -556,8 +438,8 @@ __global__ void __launch_bounds__(kAlignThreads) alignIterationKernel(AlignFrame
     // deterministic sum of the previous launch's partials: thread e < 48 adds column e over all workgroups
     // (5 thread groups of 48 take the workgroups g, g + 5, ... with four independent loads in flight each — a single
     // dependent load-add chain over all workgroups costs one memory round trip per workgroup — then a fixed-order combine)
+    constexpr int kGroups = kAlignThreads / kAlignPartial;  // 5
     {
-      constexpr int kGroups = kAlignThreads / kAlignPartial;  // 5
       const int e = tid % kAlignPartial, grp = tid / kAlignPartial;
       double p0 = 0, p1 = 0, p2 = 0, p3 = 0;
       if (grp < kGroups) {
@@ -580,22 +462,27 @@ __global__ void __launch_bounds__(kAlignThreads) alignIterationKernel(AlignFrame
         for (int b = grp + 8 * kGroups; b < prm.n_blocks; b += kGroups) p0 += src[static_cast<size_t>(b) * kAlignPartial];
         red[kAlignPartial + grp * kAlignPartial + e] = (p0 + p1) + (p2 + p3);
       }
-      __syncthreads();
-      if (tid < kAlignPartial) {
-        double tot = 0;
-#pragma unroll
-        for (int g2 = 0; g2 < kGroups; ++g2) tot += red[kAlignPartial + g2 * kAlignPartial + tid];
-        red[tid] = tot;
-      }
     }
-    __syncthreads();
     if (tid < kCtrlWords) reinterpret_cast<double *>(&sc)[tid] = ctrl_word;
     __syncthreads();
     if (!sc.active) {
       if (blockIdx.x == 0 && tid < kCtrlWords) reinterpret_cast<double *>(cout)[tid] = ctrl_word;
       return;
     }
-    if (tid < 64) alignDecideWave(sc, red, tgt, prm);  // wave 0, register copies (see alignDecideWave)
+    if (tid < 64) {
+      // wave 0: the groups' sums in a fixed order, affine prior folded in, then the LM control step
+      if (tid < kAlignPartial) {
+        double tot = 0;
+#pragma unroll
+        for (int g2 = 0; g2 < kGroups; ++g2) tot += red[kAlignPartial + g2 * kAlignPartial + tid];
+        red[tid] = tot + alignPrior(tid, prm.affine_reg[0], prm.affine_reg[1], tgt.ab0[0] + sc.cand_ab[0], tgt.ab0[1] + sc.cand_ab[1]);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      alignDecide<true>(sc, red, sc.sys, tgt.ab0[0], tgt.ab0[1], prm.affine_reg[0], prm.affine_reg[1], prm.function_tolerance, prm.parameter_tolerance,
+                        prm.inv_decrease, prm.increase_on_reject, prm.max_iterations);
+    }
     __syncthreads();
     if (blockIdx.x == 0 && tid < kCtrlWords) reinterpret_cast<double *>(cout)[tid] = reinterpret_cast<const double *>(&sc)[tid];
     if (!sc.active) return;
@@ -643,7 +530,7 @@ __global__ void __launch_bounds__(kAlignThreads) alignIterationKernel(AlignFrame
 /**
  * The whole LM loop of one alignment in ONE launch of ONE workgroup (1024 threads): up to a few thousand reference points
  * are a latency problem, not a throughput one — a launch per iteration costs more than the iteration.  Per iteration:
- * control step (thread 0, alignDecide) -> sweep (<= a dozen points per thread) -> deterministic reduction: two DPP steps
+ * control step (wave 0, alignDecide) -> sweep (<= a dozen points per thread) -> deterministic reduction: two DPP steps
  * fold 4 lanes, an LDS transpose of the 256 remaining columns, 16 lanes per row.  Same state machine and arithmetic as
  * alignIterationKernel (the multi-workgroup path stays for large point sets).
  */
@@ -674,7 +561,9 @@ __global__ void __launch_bounds__(kLoopThreads) alignLoopKernel(AlignFrameDev re
   const int total_passes = prm.max_iterations + 2;  // initial evaluation + one per iteration + the closing control step
   for (int pass = 0; pass < total_passes; ++pass) {
     if (pass > 0) {
-      if (tid < 64) alignDecideWave(sc, tot, tgt, prm);
+      if (tid < 64)
+        alignDecide<true>(sc, tot, sc.sys, tgt.ab0[0], tgt.ab0[1], prm.affine_reg[0], prm.affine_reg[1], prm.function_tolerance, prm.parameter_tolerance,
+                          prm.inv_decrease, prm.increase_on_reject, prm.max_iterations);
       __syncthreads();
       if (!sc.active) break;
     }
@@ -707,7 +596,9 @@ __global__ void __launch_bounds__(kLoopThreads) alignLoopKernel(AlignFrameDev re
       sacc += alignDpp<0xB1>(sacc);
       sacc += alignDpp<0x4E>(sacc);
       sacc += alignDpp<0x141>(sacc);
-      if (row < kAlignPartial && part == 0) tot[row] = sacc;
+      // (affine prior folded in at the candidate this pass evaluated)
+      if (row < kAlignPartial && part == 0)
+        tot[row] = sacc + alignPrior(row, prm.affine_reg[0], prm.affine_reg[1], tgt.ab0[0] + sc.cand_ab[0], tgt.ab0[1] + sc.cand_ab[1]);
     }
     __syncthreads();
   }
@@ -858,172 +749,14 @@ __device__ __forceinline__ int alignPackedIndex(int lane, int v) {
   return -1;
 }
 
-/**
- * 8 x 8 NormalLinearSystem::solve for the persistent kernel's control step: (H + lambda diag(H)) x = b by an LDL^T factorisation, written for
- * LATENCY.  One wave runs this alone, in order, at ~8 cycles per dependent f64 operation: what it costs is the length of its dependency
- * chain, not its instruction count.  Hence
- *   * right-looking: as soon as a pivot's reciprocal is known the whole trailing matrix is updated by independent FMAs, which the
- *     scheduler interleaves with the NEXT pivot's reciprocal chain (the left-looking form the compiler made of the Cholesky above put a
- *     dot-product chain in front of every pivot);
- *   * the right-hand side is carried as a ninth column, so the forward substitution costs no extra chain;
- *   * LDL^T: a reciprocal (v_rcp_f64 + 2 Newton steps, 5 dependent operations) per pivot instead of a reciprocal square root (8), unit
- *     triangles in the substitutions;
- *   * no branches: a basic-block boundary is a wall for the scheduler.  A pivot that fails the guard (the reference's zero-pivot test on
- *     the Jacobi-scaled pivot d / (diag + 10), normal_linear_system.cpp:10-16,52-59) gets reciprocal 0: its column, its y and its x vanish.
- * Chain: 8 x (reciprocal 5 + scale 1 + update 1) + back substitution 8 = ~64 dependent operations (the Cholesky form: ~170).
- */
-template <typename GetH, typename GetB>
-__device__ __forceinline__ void solve8Ldl(GetH getH /* (i, j), j <= i */, GetB getB, double lambda, double *x) {
-  double A[36], y[8], dinv[8], guard[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int j = 0; j < i; ++j) A[i * (i + 1) / 2 + j] = getH(i, j);
-    const double hii = getH(i, i);
-    const double dg = hii + hii * lambda;  // H + lambda * diag(H) (calculateStep, eigen_pose_alignment.cpp:194-198)
-    A[i * (i + 1) / 2 + i] = dg;
-    guard[i] = 1e-300 * (dg + 10.0);
-    y[i] = getB(i);
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double d = A[k * (k + 1) / 2 + k];
-    const bool ok = d > guard[k];
-    double r = __builtin_amdgcn_rcp(d);  // (a pivot that fails the guard: whatever this becomes is dropped by the select below)
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    const double inv = ok ? r : 0.0;
-    dinv[k] = inv;
-    // column k of L (unit diagonal): l_ik = a_ik / d_k, kept beside the unscaled a_ik the update needs
-    double l[8];
-#pragma unroll
-    for (int i = k + 1; i < 8; ++i) l[i] = A[i * (i + 1) / 2 + k] * inv;
-#pragma unroll
-    for (int j = k + 1; j < 8; ++j)
-#pragma unroll
-      for (int i = j; i < 8; ++i) A[i * (i + 1) / 2 + j] = fma(-l[i], A[j * (j + 1) / 2 + k], A[i * (i + 1) / 2 + j]);
-#pragma unroll
-    for (int i = k + 1; i < 8; ++i) {
-      y[i] = fma(-l[i], y[k], y[i]);
-      A[i * (i + 1) / 2 + k] = l[i];
-    }
-  }
-  // D z = y, L^T x = z
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {
-    double sacc = y[i] * dinv[i];
-#pragma unroll
-    for (int j = i + 1; j < 8; ++j) sacc = fma(-A[j * (j + 1) / 2 + i], y[j], sacc);
-    y[i] = sacc;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = y[i];
-}
-
-/**
- * The LM control step of the persistent kernel: alignDecideWave's state machine and arithmetic (levenberg_marquardt_algorithm.hpp:77-128,
- * eigen_pose_alignment.cpp:101-104,174-212) in the form one wave executes fastest — one instruction per ~4.7 cycles whatever it does, so
- * the step costs what its instruction count says:
- *   * `tot` arrives with the affine prior already folded into its four entries, and the accepted state's system is kept in the same packed
- *     form (`acc_sys`): the solve reads ONE of the two through a selected pointer — one instance of the factorisation instead of two, no
- *     expanded 8 x 8 copies (H / H_used are not results of estimatePose);
- *   * decisions are selects, not branches (the branchy form spent a third of its instructions on register copies at the joins);
- *   * no f64 division: lambda / decrease_on_accept is a multiplication by the exact reciprocal of a power of two (checked by the host), and
- *     |e - e'| / e < tol is decided by |e - e'| < tol e outside a 1e-12 band around the threshold (inside it: the division).
- * All 64 lanes run it redundantly; lane 0 stores.
- */
-__device__ __forceinline__ void pyramidDecide(AlignControl &c, const double *tot, double *acc_sys, double tgt_ab0, double tgt_ab1, double reg0, double reg1,
-                                              double function_tolerance, double parameter_tolerance, double inv_decrease, double increase, int max_iterations) {
-  const int lane = threadIdx.x & 63;
-  // ---- loads
-  const double cand_ab0 = c.cand_ab[0], cand_ab1 = c.cand_ab[1];
-  double ab_eps0 = c.ab_eps[0], ab_eps1 = c.ab_eps[1];
-  double energy = c.energy, lambda = c.lambda;
-  int n_valid = c.n_valid, converged = c.converged, iteration = c.iteration;
-  const bool first = c.have_candidate == 0;
-  double stepv[8], Ttr[12], candT[12];
-#pragma unroll
-  for (int a = 0; a < 8; ++a) stepv[a] = c.step[a];
-#pragma unroll
-  for (int a = 0; a < 12; ++a) {
-    Ttr[a] = c.T_tr[a];
-    candT[a] = c.cand_T[a];
-  }
-  const double red_energy = tot[44], red_n = tot[45];
-  const double sys_new = lane < 44 ? tot[lane] : 0.0;
-  // ---- decision (uniform)
-  const double tab0 = tgt_ab0 + cand_ab0, tab1 = tgt_ab1 + cand_ab1;
-  const double e_eval = red_energy + 0.5 * (tab0 * reg0 * tab0 + tab1 * reg1 * tab1);
-  const int n_eval = static_cast<int>(red_n + 0.5);
-  const bool has = n_eval != 0, better = e_eval < energy;
-  const double diff = fabs(energy - e_eval), thr = function_tolerance * energy;
-  bool conv_f = diff < thr * (1.0 - 1e-12);
-  if (!conv_f && !(diff > thr * (1.0 + 1e-12))) conv_f = diff / energy < function_tolerance;  // on the threshold (or not a number): the reference's own expression
-  const double a0 = tgt_ab0 + ab_eps0, a1 = tgt_ab1 + ab_eps1;
-  double step_sq = 0;
-#pragma unroll
-  for (int a = 0; a < 8; ++a) step_sq += stepv[a] * stepv[a];
-  const bool conv_p = step_sq < parameter_tolerance * ((a0 * a0 + a1 * a1) + parameter_tolerance);
-  const bool accept = !first && has && better;   // acceptStep (eigen_pose_alignment.cpp:208-212)
-  const bool take = first || accept;             // the evaluated state's system becomes the accepted state's
-  iteration += first ? 0 : 1;
-  converged = (!first && has && (conv_f || (better && conv_p))) ? 1 : converged;
-  lambda = accept ? lambda * inv_decrease : ((!first && has) ? lambda * increase : lambda);  // rejectStep: the accepted state and its system stay
-  energy = take ? e_eval : energy;
-  n_valid = take ? n_eval : n_valid;
-  int active = first ? ((max_iterations > 0 && n_eval > 0) ? 1 : 0) : ((has && !converged && iteration < max_iterations) ? 1 : 0);
-#pragma unroll
-  for (int a = 0; a < 12; ++a) Ttr[a] = accept ? candT[a] : Ttr[a];
-  ab_eps0 = accept ? cand_ab0 : ab_eps0;
-  ab_eps1 = accept ? cand_ab1 : ab_eps1;
-  // ---- calculateStep (eigen_pose_alignment.cpp:194-206): (H + lambda diag(H)) step = b from the packed sums of the accepted state
-  // (a pointer the compiler cannot see through: left to itself it reads BOTH systems and selects entry by entry)
-  using LdsDouble = const __attribute__((address_space(3))) double;
-  LdsDouble *src = take ? (LdsDouble *)tot : (LdsDouble *)acc_sys;
-  asm volatile("" : "+v"(src));
-  double stepn[8];
-  solve8Ldl([&](int i, int j) { return src[j * 8 - j * (j - 1) / 2 + (i - j)]; }, [&](int i) { return src[36 + i]; }, lambda, stepn);
-  if (take && lane < 44) acc_sys[lane] = sys_new;  // (behind the solve's reads: nothing waits for it)
-  const Rigid E = rigidExp(stepn);
-  double Em[12], candTn[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Em[4 * i + j] = E.R[3 * i + j];
-    Em[4 * i + 3] = E.t[i];
-  }
-  mat34Compose(Em, Ttr, candTn);
-  // ---- one batch of stores (lane 0)
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 12; ++a) {
-      c.T_tr[a] = Ttr[a];
-      c.cand_T[a] = candTn[a];
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) c.step[a] = stepn[a];
-    c.ab_eps[0] = ab_eps0;
-    c.ab_eps[1] = ab_eps1;
-    c.cand_ab[0] = ab_eps0 - stepn[6];
-    c.cand_ab[1] = ab_eps1 - stepn[7];
-    c.lambda = lambda;
-    c.energy = energy;
-    c.n_valid = n_valid;
-    c.converged = converged;
-    c.active = active;
-    c.iteration = iteration;
-    c.have_candidate = 1;
-  }
-}
-
 template <typename S>
 __global__ void __launch_bounds__(kAlignThreads) alignPyramidKernel(AlignPyramidArgs a) {
   // one LDS block, the small hot arrays first: their addresses fit the 16-bit offset field of the LDS instructions (an address beyond
   // 64 KB costs a v_mov per access — the control step makes ~120 of them), the 72 KB of point rows behind
   struct PyramidLds {
-    AlignControl sc;                         // (H, H_used, b: not maintained by this kernel)
+    AlignControl sc;
     double tot[kAlignPartial];               // sums of the pass, affine prior folded in
-    double acc_sys[kAlignPartial];           // system of the accepted state, same packed form
+    double acc_sys[kAlignPartial];           // system of the accepted state, same packed form (sc.sys and sc.sys_used stay unused)
     double psum[kAlignWaves][kAlignPartial]; // per wave: its quarter of the participants' sums
     double wsum[kAlignWaves][kAlignPartial]; // per wave: packed sums of its points
     double T_cur[12], ab_cur[2];             // current estimate (T_target_reference rows, affine brightness)
@@ -1033,7 +766,6 @@ __global__ void __launch_bounds__(kAlignThreads) alignPyramidKernel(AlignPyramid
   __shared__ __attribute__((aligned(16))) PyramidLds lds;
   AlignControl &sc = lds.sc;
   double(&tot)[kAlignPartial] = lds.tot;
-  double(&acc_sys)[kAlignPartial] = lds.acc_sys;
   double(&psum)[kAlignWaves][kAlignPartial] = lds.psum;
   double(&wsum)[kAlignWaves][kAlignPartial] = lds.wsum;
   double(&s_T_cur)[12] = lds.T_cur;
@@ -1092,7 +824,7 @@ __global__ void __launch_bounds__(kAlignThreads) alignPyramidKernel(AlignPyramid
     // reset(); pushFrame(reference); pushFrame(target, current estimate): the control block dsopp_hip_aligner_solve prepares, written
     // straight into LDS one entry per thread (as a private AlignControl filled by one lane it lived in 1.4 KB of scratch)
     if (tid < 48) {
-      acc_sys[tid] = 0;
+      lds.acc_sys[tid] = 0;
     } else if (tid < 64) {
       // (nothing)
     } else if (tid < 64 + 12) {
@@ -1110,8 +842,6 @@ __global__ void __launch_bounds__(kAlignThreads) alignPyramidKernel(AlignPyramid
       sc.active = 1;
       sc.iteration = 0;
       sc.have_candidate = 0;
-      sc.linear_system_valid = 0;
-      sc.pad0 = sc.pad1 = 0;
     }
     __syncthreads();
     // up to kPreload points per thread are read once per level (all of them when the level has <= kPreload * G * 256 points)
@@ -1264,8 +994,8 @@ __global__ void __launch_bounds__(kAlignThreads) alignPyramidKernel(AlignPyramid
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         AP_STAMP(7);
-        pyramidDecide(sc, tot, acc_sys, tgt.ab0[0], tgt.ab0[1], reg0, reg1, a.function_tolerance, a.parameter_tolerance, a.inv_decrease,
-                      a.increase_on_reject, a.max_iterations);
+        alignDecide<false>(sc, tot, lds.acc_sys, tgt.ab0[0], tgt.ab0[1], reg0, reg1, a.function_tolerance, a.parameter_tolerance, a.inv_decrease,
+                           a.increase_on_reject, a.max_iterations);
         AP_STAMP(8);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the publishing wave drains its stores (sums and re-arming)
@@ -1821,7 +1551,7 @@ int dsopp_hip_aligner_solve(dsopp_hip_aligner *a, dsopp_hip_align_result *result
     prm.affine_reg[1] = a->opt.affine_brightness_regularizer[1];
     prm.function_tolerance = a->opt.function_tolerance;
     prm.parameter_tolerance = a->opt.parameter_tolerance;
-    prm.decrease_on_accept = 2.0;  // eigen_pose_alignment.cpp:304-305
+    prm.inv_decrease = 0.5;  // exactly 1 / decrease_on_accept, which is 2 (eigen_pose_alignment.cpp:304-305)
     prm.increase_on_reject = 2.0;
     prm.max_iterations = a->opt.max_iterations;
     prm.n_points = n;
@@ -1903,13 +1633,14 @@ int dsopp_hip_aligner_solve(dsopp_hip_aligner *a, dsopp_hip_align_result *result
     rigidToParams(a->T_w_tgt, result->T_world_target);
     result->affine_brightness[0] = a->tgt.ab0[0];
     result->affine_brightness[1] = a->tgt.ab0[1];
+    // problem.hessian(): symmetric expansion of the packed system the last calculateStep used
+    for (int i = 0, e = 0; i < 8; ++i)
+      for (int j = i; j < 8; ++j, ++e) result->H[8 * i + j] = result->H[8 * j + i] = h.sys_used[e];
     if (!a->skip_covariance) {
-      hostla::Mat Hm(h.H_used, h.H_used + 64);
-      const hostla::Mat pinv = hostla::pinvRankRevealing(Hm, 8);
+      const hostla::Mat pinv = hostla::pinvRankRevealing(hostla::Mat(result->H, result->H + 64), 8);
       for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) result->covariance[6 * i + j] = pinv[static_cast<size_t>(8 * i + j)];
     }
-    std::memcpy(result->H, h.H_used, sizeof(h.H_used));
   });
 }
 
