@@ -46,6 +46,7 @@ SYMBOLS = [
     "dsopp_hip_immature_sets_estimate",
     "dsopp_hip_feature_extractor_create", "dsopp_hip_feature_extractor_destroy", "dsopp_hip_feature_extractor_set_mask",
     "dsopp_hip_feature_extractor_extract", "dsopp_hip_feature_extractor_get_state", "dsopp_hip_features_shuffle_order",
+    "dsopp_hip_feature_extractor_create_eigen", "dsopp_hip_feature_extractor_get_eigen_stats", "dsopp_hip_eigen_random_pattern",
     "dsopp_hip_immature_set_create_from_features", "dsopp_hip_immature_set_download_inputs",
     "dsopp_hip_aligner_set_rotation_prior",
     "dsopp_hip_window_refill_reference_depth_maps",
@@ -999,6 +1000,33 @@ class FeatureExtractor:
         _chk(lib().dsopp_hip_feature_extractor_get_state(self._h, C.byref(init), C.byref(thr), C.byref(ws), C.byref(dens), C.byref(found)))
         return dict(initialized=bool(init.value), grad_norm_threshold=thr.value, window_size=ws.value, point_density=dens.value,
                     found_last=found.value)
+
+
+def eigen_random_pattern(width, height):
+    """the eigen extractor's random pattern, (height, width) uint8: srand(3141592), then (uint8_t)rand() per pixel (no device needed)"""
+    out = np.zeros((int(height), int(width)), dtype=np.uint8)
+    _chk(lib().dsopp_hip_eigen_random_pattern(int(width), int(height), _p(out, np.uint8)))
+    return out
+
+
+class EigenFeatureExtractor(FeatureExtractor):
+    """features::EigenTrackingFeaturesExtractor (DSO's pixel selector) on the device: the same handle type and methods as
+    FeatureExtractor (dsopp_hip_feature_extractor_create_eigen); the window size (current_potential_) persists across extract() calls."""
+
+    def __init__(self, width, height, point_density_for_detector=1500.0, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.device = int(width), int(height), device
+        self._mask = None
+        self._capacity = 4096
+        _chk(lib().dsopp_hip_feature_extractor_create_eigen(int(device), C.c_void_p(stream or 0), self.width, self.height,
+                                                            C.c_double(point_density_for_detector), C.byref(self._h)))
+
+    def stats(self):
+        """the last extract's passes, window size and emissions per pass, and the top windows walked in order"""
+        passes, chained = C.c_int32(), C.c_int32()
+        potentials, found = (C.c_int32 * 2)(), (C.c_int32 * 2)()
+        _chk(lib().dsopp_hip_feature_extractor_get_eigen_stats(self._h, C.byref(passes), potentials, found, C.byref(chained)))
+        return dict(passes=passes.value, potentials=list(potentials), found=list(found), chained_windows=chained.value)
 
 
 class HipAligner:

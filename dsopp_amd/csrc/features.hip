@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "features.hpp"
 #include "immature_set.hpp"
 #include "pyramid.hpp"
 
@@ -32,7 +33,6 @@ namespace {
 constexpr int kGradBins = 2041;   // |Sx| + |Sy| <= 4 * 255 + 4 * 255
 constexpr int kErodeRadius = 7;   // getEroded(4) then getEroded(3): a 15 x 15 rectangle
 constexpr int kBlock = 256;
-constexpr int kInitialWindow = 15;  // TrackingFeaturesExtractor::current_potential_ before the first call (tracking_features_extractor.hpp:51)
 
 // cv::Sobel(img, CV_16S, 1, 0) / (0, 1) with BORDER_REFLECT_101, then |Sx| + |Sy| (sobel_tracking_features_extractor.cpp:80-90).
 // HIST: also counts the norms into bins (first call: the quantile threshold), LDS bins per workgroup, then global atomics.
@@ -174,28 +174,6 @@ int updatedThreshold(int num_pixels, int desired, int found, int thr) {
 
 using namespace dsopp_hip;
 
-struct dsopp_hip_feature_extractor {
-  StreamRef sr;
-  int width = 0, height = 0;
-  double density = 0, quantile = 0;
-  // the reference extractor's state (sobel_tracking_features_extractor.hpp:33-37, tracking_features_extractor.hpp:49-53)
-  bool initialized = false;
-  int threshold = 0;
-  int window_size = kInitialWindow;
-  int found_last = 0;
-  bool has_mask = false;
-  DeviceBuffer<uint8_t> d_image, d_mask, d_valid;  // u8 image | caller's mask (row pass output reuses it) | eroded mask (1 = valid)
-  DeviceBuffer<int16_t> d_grad;
-  DeviceBuffer<unsigned> d_hist;
-  DeviceBuffer<int> d_hit, d_list, d_count, d_final;  // per-window hit | hits in window order | their count | the returned list
-  DeviceBuffer<char> d_temp;                          // device select scratch
-  PinnedMem<uint8_t> h_image;
-  PinnedMem<int> h_count, h_list, h_final;
-  PinnedMem<unsigned> h_hist;
-  std::vector<int> final_list;  // the returned list as pixel indices y * W + x (host copy)
-  Event final_ready;            // d_final written (recorded behind its upload)
-};
-
 extern "C" {
 
 int dsopp_hip_features_shuffle_order(int32_t n, int32_t *perm) {
@@ -270,6 +248,7 @@ int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const 
 int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n) {
   return guarded([&] {
     if (!ex || !image_host || !n || capacity < 0 || (capacity > 0 && !xy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (ex->kind == ExtractorKind::Eigen) return eigenExtract(ex, image_host, capacity, xy, n);
     ex->sr.use();
     hipStream_t st = ex->sr.stream;
     const int W = ex->width, H = ex->height, N = W * H;

@@ -526,20 +526,15 @@ class HipPoseAlignment {
   time_point target_time_ = 0;
 };
 
-/** features::SobelTrackingFeaturesExtractor (src/features/src/sobel_tracking_features_extractor.cpp:70-134) on the device: the candidate
- *  pixels of a new keyframe.  Stateful as the reference: the first extract fixes the gradient-norm threshold and the window size, every
- *  later call adapts the threshold.  extract() mirrors TrackingFeaturesExtractor::extract(image, mask) and returns the features'
- *  coordinates (TrackingFeaturesFrame); the list also stays on the device for DeviceImmatureSet's constructor from an extractor. */
-class HipSobelTrackingFeaturesExtractor {
+/** What both device tracking-feature extractors share (one handle type, dsopp_hip_feature_extractor): extract() mirrors
+ *  TrackingFeaturesExtractor::extract(image, mask) and returns the features' coordinates (TrackingFeaturesFrame); the list also stays on
+ *  the device for DeviceImmatureSet's constructor from an extractor. */
+class HipTrackingFeaturesExtractor {
  public:
   using Feature = std::array<double, 2>;
-  HipSobelTrackingFeaturesExtractor(int width, int height, double point_density_for_detector = 1500, double quantile_level = 0.6,
-                                    int device = 0, void *stream = nullptr) {
-    check(dsopp_hip_feature_extractor_create(device, stream, width, height, point_density_for_detector, quantile_level, &ex_));
-  }
-  ~HipSobelTrackingFeaturesExtractor() { dsopp_hip_feature_extractor_destroy(ex_); }
-  HipSobelTrackingFeaturesExtractor(const HipSobelTrackingFeaturesExtractor &) = delete;
-  HipSobelTrackingFeaturesExtractor &operator=(const HipSobelTrackingFeaturesExtractor &) = delete;
+  ~HipTrackingFeaturesExtractor() { dsopp_hip_feature_extractor_destroy(ex_); }
+  HipTrackingFeaturesExtractor(const HipTrackingFeaturesExtractor &) = delete;
+  HipTrackingFeaturesExtractor &operator=(const HipTrackingFeaturesExtractor &) = delete;
   /** image: W x H 8-bit grey (CameraFeatures::frame_data_); mask: the camera's level-0 CameraMask bytes, nullptr = all valid.  The mask
    *  is a per-camera constant (CameraFeatures::pyramidOfMasks()[0]): it is eroded again only when a different array is passed. */
   std::vector<Feature> extract(const uint8_t *image, const uint8_t *mask) {
@@ -561,11 +556,35 @@ class HipSobelTrackingFeaturesExtractor {
   }
   const dsopp_hip_feature_extractor *handle() const { return ex_; }
 
- private:
+ protected:
+  HipTrackingFeaturesExtractor() = default;
   dsopp_hip_feature_extractor *ex_ = nullptr;
+
+ private:
   const uint8_t *mask_ = nullptr;
   bool mask_set_ = false;
   std::vector<double> xy_ = std::vector<double>(2 * 4096);
+};
+
+/** features::SobelTrackingFeaturesExtractor (src/features/src/sobel_tracking_features_extractor.cpp:70-134) on the device: the candidate
+ *  pixels of a new keyframe.  Stateful as the reference: the first extract fixes the gradient-norm threshold and the window size, every
+ *  later call adapts the threshold. */
+class HipSobelTrackingFeaturesExtractor : public HipTrackingFeaturesExtractor {
+ public:
+  HipSobelTrackingFeaturesExtractor(int width, int height, double point_density_for_detector = 1500, double quantile_level = 0.6,
+                                    int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_feature_extractor_create(device, stream, width, height, point_density_for_detector, quantile_level, &ex_));
+  }
+};
+
+/** features::EigenTrackingFeaturesExtractor (src/features/src/eigen_tracking_features_extractor.cpp:432-469) on the device, the extractor
+ *  camera_fabric.cpp:120-123 builds for `features_extractor: type: eigen`: DSO's pixel selector.  The window size (current_potential_)
+ *  persists across calls; the list is in emission order. */
+class HipEigenTrackingFeaturesExtractor : public HipTrackingFeaturesExtractor {
+ public:
+  HipEigenTrackingFeaturesExtractor(int width, int height, double point_density_for_detector, int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_feature_extractor_create_eigen(device, stream, width, height, point_density_for_detector, &ex_));
+  }
 };
 
 /** The immature landmarks of one keyframe kept on the device for their lifetime (ActiveKeyframe::immature_landmarks_:
@@ -590,7 +609,7 @@ class DeviceImmatureSet {
   /** buildFeatures + pushImmatureLandmarks (build_features.hpp:20-32, active_keyframe.cpp:95-112) on the device for the extractor's last
    *  list over level 0 of the keyframe's pyramid: features outside insideCameraROI are dropped.  `landmarks` receives the host copy
    *  (projection, direction, patch, gradient; the estimator state at the constructor defaults) that the activator keeps. */
-  DeviceImmatureSet(const HipSobelTrackingFeaturesExtractor &extractor, const DevicePyramid &keyframe_pyramid, const PinholeModel &model,
+  DeviceImmatureSet(const HipTrackingFeaturesExtractor &extractor, const DevicePyramid &keyframe_pyramid, const PinholeModel &model,
                     std::vector<ImmatureLandmarkView> &landmarks, int device = 0, void *stream = nullptr) {
     const double intr[4] = {model.fx, model.fy, model.cx, model.cy};
     int32_t n = 0;

@@ -455,12 +455,33 @@ int dsopp_hip_immature_set_download_inputs(const dsopp_hip_immature_set *s, doub
  * camera_fabric.cpp:103-123 builds when nothing else is configured, run once per keyframe on the 8-bit grey image
  * (camera_features.cpp:36-41).  Stateful as the reference: the first extract() fixes the gradient-norm threshold (the
  * quantile_level quantile of |Sx| + |Sy|) and the window size sqrt(W * H * (1 - q) / density); every later call adapts the
- * threshold.  The `eigen` extractor (DSO's pixel selector) is not provided.
+ * threshold.  The `eigen` extractor (DSO's pixel selector) is the second kind of the same handle: see
+ * dsopp_hip_feature_extractor_create_eigen.
  * width, height >= 16; point_density_for_detector > 0; quantile_level in (0, 1), else DSOPP_HIP_ERR_INVALID_ARGUMENT.
  * Before the first extract the state reads initialized 0, threshold 0, window size 15 (tracking_features_extractor.hpp:51). */
 typedef struct dsopp_hip_feature_extractor dsopp_hip_feature_extractor;
 int dsopp_hip_feature_extractor_create(int device, void *stream, int width, int height, double point_density_for_detector, double quantile_level,
                                        dsopp_hip_feature_extractor **out);
+/* features::EigenTrackingFeaturesExtractor (src/features/src/eigen_tracking_features_extractor.cpp:432-469), the extractor
+ * camera_fabric.cpp:120-123 builds for `features_extractor: type: eigen`: DSO's pixel selector over the extractor's own raw pyramid
+ * (5 levels, identity LUT, no vignette), a (W/32) x (H/32) gradient threshold map, 16 directions picked by a fixed random pattern
+ * (srand(3141592)) and a window size (current_potential_, 15 before the first call) adapted by at most one re-sampling per call; a
+ * final random reduction when the list is still too long.  The list is in emission order, neither shuffled nor truncated.  The
+ * same handle as the Sobel extractor: set_mask, extract, get_state, destroy and dsopp_hip_immature_set_create_from_features serve
+ * both kinds, with the same capacity contract.  For this kind get_state reads threshold 0, window size = current_potential_, and
+ * found_last = the emissions of the last pass before the reduction.  width, height >= 32 and point_density_for_detector > 0, else
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT.  The projection |cos dx + sin dy| rounds each product and the sum (no fused multiply-add); a
+ * reference compiled with FMA contraction may differ where that rounding decides a comparison. */
+int dsopp_hip_feature_extractor_create_eigen(int device, void *stream, int width, int height, double point_density_for_detector,
+                                             dsopp_hip_feature_extractor **out);
+/* the passes of the last extract of an eigen extractor (1 or 2), the window size and emission count of each (0 for a pass not run),
+ * and the number of top windows whose emission count depended on the directions and were walked in order; DSOPP_HIP_ERR_STATE for a
+ * Sobel extractor.  Any pointer may be NULL. */
+int dsopp_hip_feature_extractor_get_eigen_stats(const dsopp_hip_feature_extractor *ex, int32_t *passes, int32_t potentials[2], int32_t found[2],
+                                                int32_t *chained_windows);
+/* The eigen extractor's random pattern: srand(3141592), then width * height bytes (uint8_t)rand() of glibc's generator, written out in
+ * the library (no libc state is touched).  Needs no device. */
+int dsopp_hip_eigen_random_pattern(int width, int height, uint8_t *out);
 void dsopp_hip_feature_extractor_destroy(dsopp_hip_feature_extractor *ex);
 /* the camera mask the extractor erodes (CameraMask::getEroded(4).getEroded(3), camera_mask.cpp:20-29: a 15 x 15 erosion whose
  * image edge never erodes) and uses for every later extract; NULL = all pixels valid (CameraMask(rows, cols)).  W x H bytes,

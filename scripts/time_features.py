@@ -2,8 +2,9 @@
 first hits, compaction, count and list read-back, host shuffle) and dsopp_hip_immature_set_create_from_features (set allocation, ROI
 scan, build from pyramid level 0), with the reference's default configuration (density 1500, quantile 0.6).  Each is the median of
 --calls calls after --warmup, on frames of a rendered scene; the extractor alternates between frames so that every call adapts.
-Prints one JSON line per size.
-    python scripts/time_features.py [--sizes 640x480,1280x1024 --calls 200 --warmup 20]"""
+--kind eigen times the eigen extractor (dsopp_hip_feature_extractor_create_eigen: its own pyramid, threshold map, the window walk
+and up to two passes) instead, and reports its pass statistics.  Prints one JSON line per size.
+    python scripts/time_features.py [--kind sobel|eigen --sizes 640x480,1280x1024 --calls 200 --warmup 20]"""
 import argparse
 import json
 import os
@@ -19,6 +20,7 @@ if ROOT not in sys.path:
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=("sobel", "eigen"), default="sobel")
     ap.add_argument("--sizes", default="640x480,1280x1024")
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -38,7 +40,10 @@ def main():
             T = syn.se3_exp(np.array([0.03 * i, -0.01 * i, 0.02 * i, 0.002 * i, -0.003 * i, 0.001 * i]))
             img, _ = scene.render_torch(T, 0.0, 0.0, "cuda")
             frames.append(np.clip(np.round(img), 0, 255).astype(np.uint8))
-        ex = capi.FeatureExtractor(W, H, args.density, args.quantile)
+        if args.kind == "eigen":
+            ex = capi.EigenFeatureExtractor(W, H, args.density)
+        else:
+            ex = capi.FeatureExtractor(W, H, args.density, args.quantile)
         pyr = capi.Pyramid(W, H, 1)
         pyr.build(frames[0])
         ex.extract(frames[0])
@@ -57,15 +62,19 @@ def main():
                 n_features.append(len(xy))
                 n_landmarks.append(s.n)
         st = ex.state()
+        if args.kind == "eigen":
+            extra = dict(eigen_stats_last=ex.stats())
+        else:
+            extra = dict(quantile=args.quantile, grad_norm_threshold=st["grad_norm_threshold"])
         ex.close()
         pyr.close()
-        print(json.dumps(dict(size=size, calls=args.calls, density=args.density, quantile=args.quantile,
+        print(json.dumps(dict(kind=args.kind, size=size, calls=args.calls, density=args.density,
                               extract_us_median=1e6 * float(np.median(t_extract)), extract_us_p10=1e6 * float(np.percentile(t_extract, 10)),
                               extract_us_p90=1e6 * float(np.percentile(t_extract, 90)),
                               from_features_us_median=1e6 * float(np.median(t_build)), from_features_us_p10=1e6 * float(np.percentile(t_build, 10)),
                               from_features_us_p90=1e6 * float(np.percentile(t_build, 90)),
                               features_median=int(np.median(n_features)), landmarks_median=int(np.median(n_landmarks)),
-                              window_size=st["window_size"], grad_norm_threshold=st["grad_norm_threshold"])), flush=True)
+                              window_size=st["window_size"], **extra)), flush=True)
 
 
 if __name__ == "__main__":
