@@ -1119,11 +1119,9 @@ SolveArgs makeSolveArgs(W &w) {
   a.Hsc = w.dHsc();
   a.bsc = w.dbsc();
   a.use_marginal = w.marg_nonzero ? 1 : 0;
-  a.dbg_stamps = w.dbg_stamps.get();
   a.Hm = w.d_Hm.ptr;
   a.bm = w.d_bm.ptr;
   a.step = w.d_step.ptr;
-  a.ctrl = nullptr;
   a.lambda = 0;
   a.affine_reg[0] = w.opt.affine_brightness_regularizer[0];
   a.affine_reg[1] = w.opt.affine_brightness_regularizer[1];

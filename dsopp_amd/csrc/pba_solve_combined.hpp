@@ -11,7 +11,7 @@
 //   * the Jacobi guard (pivot threshold) is taken while the diagonal is written, not in a pass of its own.
 // The factorisation itself (blocked Cholesky over the frame blocks with a look-ahead panel wave, right-hand side as an extra row,
 // v_rsq_f64 seed + two Newton steps, pivots below 1e-30 of the Jacobi-scaled diagonal treated as zero) and the back-substitution
-// are those of assembleSolveKernel.
+// are shared with assembleSolveKernel: choleskyAugmented and backSubstituteWave (pba_solve_kernels.hpp), one definition each.
 #pragma once
 #include "pba_solve_kernels.hpp"
 
@@ -612,225 +612,13 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
   // each a memory round trip on the solving workgroup's path.
   if (main_wg) requestPairInputs();
 
-  // (Measured alternatives, all slower on this part — scripts/probes/bcast_probe.hip, dbg_stamps.py: a single barrier per block
-  // step with the panel wave applying the previous panel to its own column: 10.2 us against 9.2 us for the 7-frame window; L D L^T
-  // with v_rcp_f64 pivots: 11.0 us; the diagonal block eliminated redundantly per lane from LDS broadcast reads: 11.5 us.  The
-  // panel wave is bound by its instruction count (~4.7 cycles per instruction, v_readlane ~8) and by the LDS instructions a lone
-  // wave can issue, not by dependent latency.)
-  // ---- blocked Cholesky A = L L^T on the augmented (K+1) x (K+1) matrix: the last row of L becomes y^T = (L^-1 b)^T.
-  // Look-ahead schedule, one barrier per 8x8 frame block: wave 0 ("panel wave") brings block column kb+1 up to date with
-  // panel kb, factors its diagonal block in registers and solves the panel below it, WHILE waves 1..3 apply panel kb to
-  // the rest of the trailing matrix (columns >= kb+2).  The sequential factor chain is thus off the other waves' path.
-  auto readLane = [](double v, int src_lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-  };
-  auto factorAndPanel = [&](int kb) {
-    // wave 0 only.  Lane i owns row k0 + i of block column kb (the 8 rows of the diagonal block AND the panel rows below
-    // it): one elimination loop does the Cholesky of the diagonal block and the triangular solve of the panel together.
-    // Per pivot k: d = C[k][k] (v_readlane from lane k), l_ik = c_ik / sqrt(d) in every lane, then for the remaining columns
-    // j the row-k factor l_jk is broadcast by v_readlane and every lane updates its own c_ij.  A wave issues one
-    // instruction per ~4.7 cycles whether or not it depends on the previous one (measured), so what matters is the
-    // instruction count: ~200 here against ~430 for a per-lane redundant 8x8 factorisation + per-row substitution.
-    // Two variants were built, parity-green and slower, then removed (DESIGN.md sections 4 and 0d): pivots eliminated in pairs, 19.45 against
-    // 18.29 us per solve launch (profiles/r05/paired_pivots_ab.txt); the row-k factors broadcast by v_fmac_f64_dpp row_newbcast instead
-    // of v_readlane, C1 37.1 - 37.2 against 36.8 us per iteration (profiles/r06/solve_panel_ab.txt).
-    const int k0 = kb * kBlk;
-    const int row = k0 + lane;
-    const bool valid = row < N;
-    double c[kBlk], invd[kBlk], lj[28];  // lj: strictly-lower factor entries l_jk of the diagonal block (uniform), for rows beyond 64
-    {
-      const double *src = A + (valid ? row : k0) * ld + k0;
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) c[j] = src[j];
-    }
-    double guard[kBlk];  // zero-pivot thresholds, fetched before the pivot chain starts
-#pragma unroll
-    for (int k = 0; k < kBlk; ++k) guard[k] = 1e-30 * pv[min(k0 + k, K - 1)];
-    int e = 0;
-    // inverse square root of a pivot: the hardware estimate (v_rsq_f64, 2^-23 relative, straight on the f64 value: an f32 seed costs two
-    // conversions on the dependent chain) + two Newton steps
-    auto rsqrtRefined = [](double d) {
-      const double hd = 0.5 * d;
-      double inv = __builtin_amdgcn_rsq(d);
-      inv = fma(inv, fma(-hd * inv, inv, 0.5), inv);
-      inv = fma(inv, fma(-hd * inv, inv, 0.5), inv);
-      return inv;
-    };
-#pragma unroll
-    for (int k = 0; k < kBlk; ++k) {
-      const double d = readLane(c[k], k);
-      // pivots whose Jacobi-scaled value d / (diag + 10) is below 1e-30 are treated as zero, as a rank-revealing factorisation would
-      const bool okp = d > guard[k];
-      double inv = rsqrtRefined(d);
-      inv = okp ? inv : 0.0;
-      invd[k] = inv;
-      const double l = c[k] * inv;  // lane k: sqrt(d); lanes i > k: l_ik
-      c[k] = l;
-#pragma unroll
-      for (int j = k + 1; j < kBlk; ++j) {
-        const double ljk = readLane(l, j);
-        lj[e++] = ljk;
-        c[j] -= l * ljk;
-      }
-    }
-    if (valid) {
-      double *dst = A + row * ld + k0;
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j)
-        if (lane >= kBlk || j <= lane) dst[j] = c[j];  // the diagonal block keeps its lower triangle only
-    }
-    // rows beyond the first 64 of this block column (windows of more than 7 frames): substitution with the broadcast factors
-    for (int r2 = row + 64; r2 < N; r2 += 64) {
-      double v[kBlk];
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) v[j] = A[r2 * ld + k0 + j];
-      int e2 = 0;
-#pragma unroll
-      for (int k = 0; k < kBlk; ++k) {
-        v[k] *= invd[k];
-#pragma unroll
-        for (int j = k + 1; j < kBlk; ++j) v[j] -= v[k] * lj[e2++];
-      }
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) A[r2 * ld + k0 + j] = v[j];
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int cidx = 0; cidx < kBlk; ++cidx) Linv[kb * 36 + lowIdx(cidx, cidx)] = invd[cidx];  // diagonal of the inverse; completed below
-    }
-  };
-  // (tuning aid, stamps build: where the panel wave's time goes over the block steps — slots 12 column update, 13 its barrier, 14 factor +
-  // panel, 15 the barrier behind it)
-  long long cs_acc[4] = {0, 0, 0, 0}, cs_t = (kStamps && a.dbg_stamps) ? wall_clock64() : 0;
-  auto csMark = [&](int slot) {
-    if (kStamps && a.dbg_stamps) {
-      const long long now = wall_clock64();
-      cs_acc[slot] += now - cs_t;
-      cs_t = now;
-    }
-  };
-  if (wave == 0) factorAndPanel(0);
-  ldsBarrier();
-  csMark(2);
-  for (int kb = 0; kb < F; ++kb) {
-    const int k0 = kb * kBlk, k1 = k0 + kBlk, k2 = k1 + kBlk;
-    if (kb + 1 < F) {
-      // all waves: block column kb+1 (rows k1 .. N-1, columns k1 .. k1+7) -= panel kb contribution (one element per thread)
-      const int n_el = (N - k1) * kBlk;
-      for (int e = tid; e < n_el; e += THREADS) {
-        const int row = k1 + (e >> 3), col = k1 + (e & 7);
-        if (col > row) continue;
-        const double *li = A + row * ld + k0, *lj = A + col * ld + k0;
-        double sacc = 0;
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) sacc += li[c] * lj[c];
-        A[row * ld + col] -= sacc;
-      }
-    }
-    csMark(0);
-    ldsBarrier();
-    csMark(1);
-    if (wave == 0) {
-      if (kb + 1 < F) factorAndPanel(kb + 1);
-      csMark(2);
-    } else {
-      // trailing update of columns >= k2 with panel kb: A_ij -= sum_c L_ic L_jc  (the other waves as a 12 x 16 / 28 x 16 tile)
-      const int t = tid - 64, tr = t >> 4, tc = t & 15;
-      for (int row = k2 + tr; row < N; row += (THREADS - 64) / 16) {
-        const double *li = A + row * ld + k0;
-        double lic[kBlk];
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) lic[c] = li[c];
-        for (int col = k2 + tc; col <= row; col += 16) {
-          const double *lj = A + col * ld + k0;
-          double sacc = 0;
-#pragma unroll
-          for (int c = 0; c < kBlk; ++c) sacc += lic[c] * lj[c];
-          A[row * ld + col] -= sacc;
-        }
-      }
-    }
-    ldsBarrier();
-    csMark(3);
-  }
-  if (kStamps && a.dbg_stamps && tid == 0) {
-    for (int q = 0; q < 4; ++q) a.dbg_stamps[12 + q] = cs_acc[q];
-  }
+  choleskyAugmented<THREADS>(A, pv, Linv, F, tid, a.dbg_stamps);
   SC_STAMP(2);
   // what only the kernel's tail reads (pair-constant refresh, prior energy of the candidate) is requested HERE, to land under the
   // back-substitution: requested at the head, these 24 doubles per thread were held — or spilled and reloaded — across the factorisation
   if (ticketed) requestTailInputs();
-  // ---- back substitution x = L^-T y (y = row K of L), column-oriented on one wave: lane j carries y_j (and y_{j+64});
-  // going down from k = K-1, x_k = y_k / L_kk is broadcast with v_readlane and every lane j < k takes y_j -= L_kj x_k.
-  // 4-7 instructions per unknown, no LDS round trip or barrier inside the chain (L_kj is prefetched a frame block ahead).
   if (wave == 0) {
-    // No masking anywhere: lane j is consumed at step k = j (x_j = y_j / L_jj); whatever the later steps k < j add to it
-    // (entries on / above the diagonal, uninitialised LDS) is never read again.  x_k leaves the chain as a wave-uniform
-    // value and is written to LDS by lane 0, eight at a time.
-    auto run = [&](auto two_tag) {
-      constexpr bool TWO = decltype(two_tag)::value;
-      const int j0 = lane, j1 = lane + 64;
-      double y0 = j0 < K ? A[K * ld + j0] : 0.0, y1 = (TWO && j1 < K) ? A[K * ld + j1] : 0.0;
-      const double gi0 = j0 < K ? Linv[(j0 >> 3) * 36 + lowIdx(j0 & 7, j0 & 7)] : 0.0;
-      const double gi1 = (TWO && j1 < K) ? Linv[(j1 >> 3) * 36 + lowIdx(j1 & 7, j1 & 7)] : 0.0;
-      double g0[kBlk], g1[kBlk], n0[kBlk], n1[kBlk];
-      auto loadBlock = [&](int kb, double *o0, double *o1) {
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) {
-          o0[c] = A[(kb * kBlk + c) * ld + j0];  // lanes beyond the row read into the next row: in bounds, never used
-          if (TWO) o1[c] = j1 < K ? A[(kb * kBlk + c) * ld + j1] : 0.0;
-        }
-      };
-      // Unknowns 64 .. K-1 (windows of more than 8 frames) are carried by y1: while they are eliminated (frame blocks >= 8) every
-      // step updates both halves; from block 7 down nothing above lane 63 is read again, so the loop is the one-register loop of
-      // a small window (no second load, multiply, broadcast pair or update per step: 9.0 -> about 5 us at 12 frames).
-      auto sweepBlocks = [&](auto upper_tag, int kb_from, int kb_to) {
-        constexpr bool UPPER = decltype(upper_tag)::value;
-        for (int kb = kb_from; kb >= kb_to; --kb) {
-          if (kb > 0) {
-#pragma unroll
-            for (int c = 0; c < kBlk; ++c) {
-              n0[c] = A[((kb - 1) * kBlk + c) * ld + j0];  // lanes beyond the row read into the next row: in bounds, never used
-              if (UPPER) n1[c] = j1 < K ? A[((kb - 1) * kBlk + c) * ld + j1] : 0.0;
-            }
-          }
-          double xo[kBlk];
-#pragma unroll
-          for (int c = kBlk - 1; c >= 0; --c) {
-            const int k = kb * kBlk + c;
-            const double xk = UPPER ? readLane(y1 * gi1, k & 63) : readLane(y0 * gi0, k);
-            xo[c] = xk;
-            y0 -= g0[c] * xk;
-            if (UPPER) y1 -= g1[c] * xk;
-          }
-          if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < kBlk; ++c) xs[kb * kBlk + c] = xo[c];
-          }
-#pragma unroll
-          for (int c = 0; c < kBlk; ++c) {
-            g0[c] = n0[c];
-            if (UPPER) g1[c] = n1[c];
-          }
-        }
-      };
-      loadBlock(F - 1, g0, g1);
-      if (TWO) {
-        sweepBlocks(std::true_type{}, F - 1, 8);
-        sweepBlocks(std::false_type{}, 7, 0);
-      } else {
-        sweepBlocks(std::false_type{}, F - 1, 0);
-      }
-    };
-    // (Measured and dropped: back-substitution by frame blocks with inverted diagonal blocks, x_blk = W^T y_blk then y -= L_blk^T x_blk,
-    // which halves the dependent chain but doubles the broadcasts: 3.2 us against 2.6 us.  A v_readlane pair costs as much as three
-    // dependent f64 FMAs here (scripts/probes/bcast_probe.hip), so the count of broadcasts decides, not the chain length.)
-    if (K > 64)
-      run(std::true_type{});
-    else
-      run(std::false_type{});
+    backSubstituteWave(A, Linv, xs, F, lane);
     SC_STAMP(6);
   }
   __syncthreads();

@@ -778,7 +778,6 @@ struct SolveArgs {
   double *Hsc_copy = nullptr;       // optional (with store_system): full symmetric copy of H_schur for the covariance read-back
   const double *Hm, *bm;            // marginal prior
   double *step;                     // out: K
-  LmControl *ctrl;                  // nullable (host-driven stages pass lambda explicitly)
   double lambda;
   double affine_reg[2];
   double fixed_reg;
@@ -789,9 +788,7 @@ struct SolveArgs {
   int store_system;  // write H_pp / b_pp (with priors) and the symmetrised H_schur back (stage API, marginalisation, covariance)
   int add_priors;
   int use_marginal;  // the marginal prior is non-zero
-  long long *dbg_stamps;  // nullable: wall_clock64() stamps of the phases (tuning aid)
 };
-#define DSOPP_STAMP(i) do { if (kStamps && a.dbg_stamps && tid == 0) a.dbg_stamps[i] = wall_clock64(); } while (0)
 
 /** prior + marginal energy terms of calculateEnergy (problem.hpp:293-312) for state x = eps (+ step); whole workgroup */
 __device__ inline double priorEnergyBlock(const SolveArgs &a, bool with_step, double *lds /* K + 8 */, int tid) {
@@ -823,12 +820,254 @@ __device__ inline double priorEnergyBlock(const SolveArgs &a, bool with_step, do
 /** packed lower-triangular index of an 8x8 block */
 __host__ __device__ constexpr int lowIdx(int i, int j) { return i * (i + 1) / 2 + j; }
 
+/** v_readlane of a double: the value of lane `src_lane` (wave-uniform) in every lane */
+__device__ __forceinline__ double readLane(double v, int src_lane) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
+  return __hiloint2double(hi, lo);
+}
+
+/**
+ * NormalLinearSystem::solve (normal_linear_system.cpp:10-16,52-59: Jacobi preconditioner + LDL^T), first half: the factorisation both
+ * dense solves of the window share — solveCombinedKernel (K3 of the fused LM loop, THREADS = 256 or 512) and assembleSolveKernel (stage
+ * API, marginalisation, covariance, lm_mode 1; THREADS = kSolveThreads).  Whole workgroup; LDS only.
+ * A: the augmented (K+1) x (K+1) system, K = 8 F, row stride K + 2, lower triangle, right-hand side as row K — overwritten with L, whose
+ * last row is y^T = (L^-1 b)^T.  pv: the K Jacobi-scaled diagonals diag + 10 the zero-pivot guard refers to.  Linv: reciprocal pivots out
+ * (frame block kb at 36 kb + lowIdx(c, c)).  stamps: nullable, -DDSOPP_HIP_STAMPS builds only (slots 12 - 15 of the fused kernel).
+ * The caller has a barrier between its last store to A / pv and this call; the routine ends behind one.
+ */
+template <int THREADS>
+__device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, double *Linv, int F, int tid, long long *stamps) {
+  const int K = kBlk * F;
+  const int N = K + 1;   // augmented with the right-hand side row
+  const int ld = N + 1;
+  const int wave = tid >> 6, lane = tid & 63;
+  // (Measured alternatives, all slower on this part — scripts/probes/bcast_probe.hip, dbg_stamps.py: a single barrier per block
+  // step with the panel wave applying the previous panel to its own column: 10.2 us against 9.2 us for the 7-frame window; L D L^T
+  // with v_rcp_f64 pivots: 11.0 us; the diagonal block eliminated redundantly per lane from LDS broadcast reads: 11.5 us.  The
+  // panel wave is bound by its instruction count (~4.7 cycles per instruction, v_readlane ~8) and by the LDS instructions a lone
+  // wave can issue, not by dependent latency.)
+  // ---- blocked Cholesky A = L L^T on the augmented (K+1) x (K+1) matrix: the last row of L becomes y^T = (L^-1 b)^T.
+  // Look-ahead schedule, one barrier per 8x8 frame block: wave 0 ("panel wave") brings block column kb+1 up to date with
+  // panel kb, factors its diagonal block in registers and solves the panel below it, WHILE waves 1..3 apply panel kb to
+  // the rest of the trailing matrix (columns >= kb+2).  The sequential factor chain is thus off the other waves' path.
+  auto factorAndPanel = [&](int kb) {
+    // wave 0 only.  Lane i owns row k0 + i of block column kb (the 8 rows of the diagonal block AND the panel rows below
+    // it): one elimination loop does the Cholesky of the diagonal block and the triangular solve of the panel together.
+    // Per pivot k: d = C[k][k] (v_readlane from lane k), l_ik = c_ik / sqrt(d) in every lane, then for the remaining columns
+    // j the row-k factor l_jk is broadcast by v_readlane and every lane updates its own c_ij.  A wave issues one
+    // instruction per ~4.7 cycles whether or not it depends on the previous one (measured), so what matters is the
+    // instruction count: ~200 here against ~430 for a per-lane redundant 8x8 factorisation + per-row substitution.
+    // Two variants were built, parity-green and slower, then removed (DESIGN.md sections 4 and 0d): pivots eliminated in pairs, 19.45 against
+    // 18.29 us per solve launch (profiles/r05/paired_pivots_ab.txt); the row-k factors broadcast by v_fmac_f64_dpp row_newbcast instead
+    // of v_readlane, C1 37.1 - 37.2 against 36.8 us per iteration (profiles/r06/solve_panel_ab.txt).
+    const int k0 = kb * kBlk;
+    const int row = k0 + lane;
+    const bool valid = row < N;
+    double c[kBlk], invd[kBlk], lj[28];  // lj: strictly-lower factor entries l_jk of the diagonal block (uniform), for rows beyond 64
+    {
+      const double *src = A + (valid ? row : k0) * ld + k0;
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j) c[j] = src[j];
+    }
+    double guard[kBlk];  // zero-pivot thresholds, fetched before the pivot chain starts
+#pragma unroll
+    for (int k = 0; k < kBlk; ++k) guard[k] = 1e-30 * pv[min(k0 + k, K - 1)];
+    int e = 0;
+    // inverse square root of a pivot: the hardware estimate (v_rsq_f64, 2^-23 relative, straight on the f64 value: an f32 seed costs two
+    // conversions on the dependent chain) + two Newton steps
+    auto rsqrtRefined = [](double d) {
+      const double hd = 0.5 * d;
+      double inv = __builtin_amdgcn_rsq(d);
+      inv = fma(inv, fma(-hd * inv, inv, 0.5), inv);
+      inv = fma(inv, fma(-hd * inv, inv, 0.5), inv);
+      return inv;
+    };
+#pragma unroll
+    for (int k = 0; k < kBlk; ++k) {
+      const double d = readLane(c[k], k);
+      // pivots whose Jacobi-scaled value d / (diag + 10) is below 1e-30 are treated as zero, as a rank-revealing factorisation would
+      const bool okp = d > guard[k];
+      double inv = rsqrtRefined(d);
+      inv = okp ? inv : 0.0;
+      invd[k] = inv;
+      const double l = c[k] * inv;  // lane k: sqrt(d); lanes i > k: l_ik
+      c[k] = l;
+#pragma unroll
+      for (int j = k + 1; j < kBlk; ++j) {
+        const double ljk = readLane(l, j);
+        lj[e++] = ljk;
+        c[j] -= l * ljk;
+      }
+    }
+    if (valid) {
+      double *dst = A + row * ld + k0;
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j)
+        if (lane >= kBlk || j <= lane) dst[j] = c[j];  // the diagonal block keeps its lower triangle only
+    }
+    // rows beyond the first 64 of this block column (windows of more than 7 frames): substitution with the broadcast factors
+    for (int r2 = row + 64; r2 < N; r2 += 64) {
+      double v[kBlk];
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j) v[j] = A[r2 * ld + k0 + j];
+      int e2 = 0;
+#pragma unroll
+      for (int k = 0; k < kBlk; ++k) {
+        v[k] *= invd[k];
+#pragma unroll
+        for (int j = k + 1; j < kBlk; ++j) v[j] -= v[k] * lj[e2++];
+      }
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j) A[r2 * ld + k0 + j] = v[j];
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int cidx = 0; cidx < kBlk; ++cidx) Linv[kb * 36 + lowIdx(cidx, cidx)] = invd[cidx];  // diagonal of the inverse; completed below
+    }
+  };
+  // (tuning aid, stamps build: where the panel wave's time goes over the block steps — slots 12 column update, 13 its barrier, 14 factor +
+  // panel, 15 the barrier behind it)
+  long long cs_acc[4] = {0, 0, 0, 0}, cs_t = (kStamps && stamps) ? wall_clock64() : 0;
+  auto csMark = [&](int slot) {
+    if (kStamps && stamps) {
+      const long long now = wall_clock64();
+      cs_acc[slot] += now - cs_t;
+      cs_t = now;
+    }
+  };
+  if (wave == 0) factorAndPanel(0);
+  ldsBarrier();
+  csMark(2);
+  for (int kb = 0; kb < F; ++kb) {
+    const int k0 = kb * kBlk, k1 = k0 + kBlk, k2 = k1 + kBlk;
+    if (kb + 1 < F) {
+      // all waves: block column kb+1 (rows k1 .. N-1, columns k1 .. k1+7) -= panel kb contribution (one element per thread)
+      const int n_el = (N - k1) * kBlk;
+      for (int e = tid; e < n_el; e += THREADS) {
+        const int row = k1 + (e >> 3), col = k1 + (e & 7);
+        if (col > row) continue;
+        const double *li = A + row * ld + k0, *lj = A + col * ld + k0;
+        double sacc = 0;
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) sacc += li[c] * lj[c];
+        A[row * ld + col] -= sacc;
+      }
+    }
+    csMark(0);
+    ldsBarrier();
+    csMark(1);
+    if (wave == 0) {
+      if (kb + 1 < F) factorAndPanel(kb + 1);
+      csMark(2);
+    } else {
+      // trailing update of columns >= k2 with panel kb: A_ij -= sum_c L_ic L_jc  (the other waves as a 12 x 16 / 28 x 16 tile)
+      const int t = tid - 64, tr = t >> 4, tc = t & 15;
+      for (int row = k2 + tr; row < N; row += (THREADS - 64) / 16) {
+        const double *li = A + row * ld + k0;
+        double lic[kBlk];
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) lic[c] = li[c];
+        for (int col = k2 + tc; col <= row; col += 16) {
+          const double *lj = A + col * ld + k0;
+          double sacc = 0;
+#pragma unroll
+          for (int c = 0; c < kBlk; ++c) sacc += lic[c] * lj[c];
+          A[row * ld + col] -= sacc;
+        }
+      }
+    }
+    ldsBarrier();
+    csMark(3);
+  }
+  if (kStamps && stamps && tid == 0) {
+    for (int q = 0; q < 4; ++q) stamps[12 + q] = cs_acc[q];
+  }
+}
+
+/**
+ * Second half: back substitution x = L^-T y (y = row K of L), column-oriented on one wave: lane j carries y_j (and y_{j+64});
+ * going down from k = K-1, x_k = y_k / L_kk is broadcast with v_readlane and every lane j < k takes y_j -= L_kj x_k.
+ * 4-7 instructions per unknown, no LDS round trip or barrier inside the chain (L_kj is prefetched a frame block ahead).
+ * Wave 0 only (lane = its lane index), behind the barrier choleskyAugmented ends with; x goes to xs[0 .. K-1].
+ */
+__device__ __forceinline__ void backSubstituteWave(const double *A, const double *Linv, double *xs, int F, int lane) {
+  const int K = kBlk * F, ld = K + 2;
+  // No masking anywhere: lane j is consumed at step k = j (x_j = y_j / L_jj); whatever the later steps k < j add to it
+  // (entries on / above the diagonal, uninitialised LDS) is never read again.  x_k leaves the chain as a wave-uniform
+  // value and is written to LDS by lane 0, eight at a time.
+  auto run = [&](auto two_tag) {
+    constexpr bool TWO = decltype(two_tag)::value;
+    const int j0 = lane, j1 = lane + 64;
+    double y0 = j0 < K ? A[K * ld + j0] : 0.0, y1 = (TWO && j1 < K) ? A[K * ld + j1] : 0.0;
+    const double gi0 = j0 < K ? Linv[(j0 >> 3) * 36 + lowIdx(j0 & 7, j0 & 7)] : 0.0;
+    const double gi1 = (TWO && j1 < K) ? Linv[(j1 >> 3) * 36 + lowIdx(j1 & 7, j1 & 7)] : 0.0;
+    double g0[kBlk], g1[kBlk], n0[kBlk], n1[kBlk];
+    auto loadBlock = [&](int kb, double *o0, double *o1) {
+#pragma unroll
+      for (int c = 0; c < kBlk; ++c) {
+        o0[c] = A[(kb * kBlk + c) * ld + j0];  // lanes beyond the row read into the next row: in bounds, never used
+        if (TWO) o1[c] = j1 < K ? A[(kb * kBlk + c) * ld + j1] : 0.0;
+      }
+    };
+    // Unknowns 64 .. K-1 (windows of more than 8 frames) are carried by y1: while they are eliminated (frame blocks >= 8) every
+    // step updates both halves; from block 7 down nothing above lane 63 is read again, so the loop is the one-register loop of
+    // a small window (no second load, multiply, broadcast pair or update per step: 9.0 -> about 5 us at 12 frames).
+    auto sweepBlocks = [&](auto upper_tag, int kb_from, int kb_to) {
+      constexpr bool UPPER = decltype(upper_tag)::value;
+      for (int kb = kb_from; kb >= kb_to; --kb) {
+        if (kb > 0) {
+#pragma unroll
+          for (int c = 0; c < kBlk; ++c) {
+            n0[c] = A[((kb - 1) * kBlk + c) * ld + j0];  // lanes beyond the row read into the next row: in bounds, never used
+            if (UPPER) n1[c] = j1 < K ? A[((kb - 1) * kBlk + c) * ld + j1] : 0.0;
+          }
+        }
+        double xo[kBlk];
+#pragma unroll
+        for (int c = kBlk - 1; c >= 0; --c) {
+          const int k = kb * kBlk + c;
+          const double xk = UPPER ? readLane(y1 * gi1, k & 63) : readLane(y0 * gi0, k);
+          xo[c] = xk;
+          y0 -= g0[c] * xk;
+          if (UPPER) y1 -= g1[c] * xk;
+        }
+        if (lane == 0) {
+#pragma unroll
+          for (int c = 0; c < kBlk; ++c) xs[kb * kBlk + c] = xo[c];
+        }
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) {
+          g0[c] = n0[c];
+          if (UPPER) g1[c] = n1[c];
+        }
+      }
+    };
+    loadBlock(F - 1, g0, g1);
+    if (TWO) {
+      sweepBlocks(std::true_type{}, F - 1, 8);
+      sweepBlocks(std::false_type{}, 7, 0);
+    } else {
+      sweepBlocks(std::false_type{}, F - 1, 0);
+    }
+  };
+  // (Measured and dropped: back-substitution by frame blocks with inverted diagonal blocks, x_blk = W^T y_blk then y -= L_blk^T x_blk,
+  // which halves the dependent chain but doubles the broadcasts: 3.2 us against 2.6 us.  A v_readlane pair costs as much as three
+  // dependent f64 FMAs here (scripts/probes/bcast_probe.hip), so the count of broadcasts decides, not the chain length.)
+  if (K > 64)
+    run(std::true_type{});
+  else
+    run(std::false_type{});
+}
+
 /**
  * evaluateLinearSystemPrior (problem.hpp:37-77), calculateStep (problem.hpp:342-361) and NormalLinearSystem::solve
- * (normal_linear_system.cpp:10-16,52-59: Jacobi preconditioner + LDL^T; here a blocked Cholesky over the 8x8 frame blocks
- * with the right-hand side carried as an extra row, each thread factoring/inverting the current diagonal block in
- * registers so a block step costs two barriers) — one workgroup.  Also rebuilds the pair constants and the prior energy
- * for the candidate state eps + step, so the energy sweep can follow immediately.
+ * (normal_linear_system.cpp:10-16,52-59; here choleskyAugmented + backSubstituteWave, the arithmetic of the fused loop's
+ * solveCombinedKernel) from the four systems H_pp, b_pp, H_schur, b_schur — one workgroup.  Three callers (pba.hip): stageLinearize and
+ * foldMarginalized assemble only (store_system: system_pose with priors, the symmetrised H_schur and Hsc_copy are written back, and
+ * !do_solve ends the kernel there); stageStep — the stage API's calculate_step and every step of lm_mode 1 — solves: it stores the step
+ * and, with first-estimate Jacobians, moves the pair constants that follow the state to eps + step (without them the host launches
+ * pairSetupKernel behind it).  lambda is the caller's: on this path the LM control (decision, candidate prior energy, norms) is the host's.
  */
 __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -839,54 +1078,10 @@ __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArg
   double *pv = A + N * ld;                           // K preconditioner
   double *xs = pv + K;                               // K + 16 scratch
   double *Linv = xs + K + 16;                        // F x 36 inverses of the diagonal blocks
-  double *epsl = Linv + 36 * kMaxFrames;             // K: state increment eps of every frame
-  double *stpl = epsl + K;                           // K: the new step (-x), kept in LDS for the pair refresh / prior energy
-  double *ab0l = stpl + K;                           // 2 F: affine brightness at the linearisation point
   const int tid = threadIdx.x;
-  // Control block, pair-refresh inputs and the first tile batch are all requested before anything waits: the kernel
-  // start costs one memory round trip.  (The early exit is taken after the first barrier, which keeps the loads above it.)
-  int c_active = 1, c_relin = 0;
-  double lam = a.lambda;
-  if (a.ctrl) {
-    c_active = a.ctrl->active;
-    c_relin = a.ctrl->relin;
-    lam = a.ctrl->lambda;
-  }
-  DSOPP_STAMP(0);
-  // inputs of refreshPairCurrent for pair (r, t) = (tid / F, tid % F): constant over the solve.  Raw loads only: any
-  // arithmetic on a loaded value here would make the compiler wait for the round trip before issuing the next loads.
-  struct {
-    int valid;
-    Rigid T0;
-    double fxr, fyr, cxr, cyr, fxt, fyt, cxt, cyt, exposure_r, exposure_t;
-  } pp;
-  pp.valid = 0;
-  const bool fast_refresh = a.fej && a.do_solve && a.ctrl;
-  if (fast_refresh && tid < F * F) {
-    const int r = tid / F, t = tid - F * (tid / F);
-    const PairConst &P = a.pc[r * kMaxFrames + t];
-    pp.valid = P.valid;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) pp.T0.R[3 * i + j] = P.T0rel[4 * i + j];
-      pp.T0.t[i] = P.T0rel[4 * i + 3];
-    }
-    const FrameDev &fr = a.frames[r];
-    const FrameDev &ft = a.frames[t];
-    pp.fxr = fr.fx;
-    pp.fyr = fr.fy;
-    pp.cxr = fr.cx;
-    pp.cyr = fr.cy;
-    pp.fxt = ft.fx;
-    pp.fyt = ft.fy;
-    pp.cxt = ft.cx;
-    pp.cyt = ft.cy;
-    pp.exposure_r = fr.exposure;
-    pp.exposure_t = ft.exposure;
-  }
-
-  // ---- system_pose = sums + priors (problem.hpp:39-62)
+  const double lam = a.lambda;
+  // ---- system_pose = sums + priors (problem.hpp:39-62).  This thread's vector entries and the first tile batch are requested before
+  // anything waits: the kernel start costs one memory round trip.
   double eps_c = 0, ab0_c = 0, bpp_c = 0, bsc_c = 0, bm_c = 0;  // this thread's entry c = tid (K <= 128 < kSolveThreads)
   int fixed_c = 0, tomarg_c = 0;
   if (tid < K) {
@@ -935,18 +1130,15 @@ __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArg
   };
   loadBatch(0);
   // opaque to the optimiser: stops it from testing these loaded flags (and waiting for them) above the tile loads
-  asm volatile("" : "+v"(fixed_c), "+v"(tomarg_c), "+v"(pp.valid), "+v"(c_active), "+v"(c_relin));
+  asm volatile("" : "+v"(fixed_c), "+v"(tomarg_c));
   int prior_kind = 0;  // 0 none, 1 fixed frame, 2 affine brightness
   if (tid < K) {
     if (a.add_priors && !tomarg_c) prior_kind = fixed_c ? 1 : ((tid & 7) >= 6 ? 2 : 0);
     const double pd_c = prior_kind == 1 ? a.fixed_reg : (prior_kind == 2 ? a.affine_reg[(tid & 7) - 6] : 0.0);
     xs[tid] = eps_c;
-    epsl[tid] = eps_c;
     prior_diag[tid] = pd_c;
-    if ((tid & 7) >= 6) ab0l[2 * (tid >> 3) + (tid & 7) - 6] = ab0_c;
   }
   __syncthreads();  // fence: keeps every load above; prior_diag visible
-  if (!c_active || c_relin) return;
   const double sc = -1.0 / (1.0 + lam);
   auto storeBatch = [&]() {
 #pragma unroll
@@ -1001,282 +1193,22 @@ __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArg
   if (tid == 0) A[K * ld + K] = 0;
   if (!a.do_solve) return;
   __syncthreads();
-  DSOPP_STAMP(1);
-  // ---- blocked Cholesky A = L L^T on the augmented (K+1) x (K+1) matrix: the last row of L becomes y^T = (L^-1 b)^T.
-  // Look-ahead schedule, one barrier per 8x8 frame block: wave 0 ("panel wave") brings block column kb+1 up to date with
-  // panel kb, factors its diagonal block in registers and solves the panel below it, WHILE waves 1..3 apply panel kb to
-  // the rest of the trailing matrix (columns >= kb+2).  The sequential factor chain is thus off the other waves' path.
-  DSOPP_STAMP(2);
-  const int wave = tid >> 6, lane = tid & 63;
-  auto readLane = [](double v, int src_lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-  };
-  auto factorAndPanel = [&](int kb) {
-    // wave 0 only.  Lane i owns row k0 + i of block column kb (the 8 rows of the diagonal block AND the panel rows below
-    // it): one elimination loop does the Cholesky of the diagonal block and the triangular solve of the panel together.
-    // Per pivot k: d = C[k][k] (v_readlane from lane k), l_ik = c_ik / sqrt(d) in every lane, then for the remaining columns
-    // j the row-k factor l_jk is broadcast by v_readlane and every lane updates its own c_ij.  A wave issues one
-    // instruction per ~4.7 cycles whether or not it depends on the previous one (measured), so what matters is the
-    // instruction count: ~200 here against ~430 for a per-lane redundant 8x8 factorisation + per-row substitution.
-    const int k0 = kb * kBlk;
-    const int row = k0 + lane;
-    const bool valid = row < N;
-    double c[kBlk], invd[kBlk], lj[28];  // lj: strictly-lower factor entries l_jk of the diagonal block (uniform), for rows beyond 64
-    {
-      const double *src = A + (valid ? row : k0) * ld + k0;
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) c[j] = src[j];
-    }
-    double guard[kBlk];  // zero-pivot thresholds, fetched before the pivot chain starts
-#pragma unroll
-    for (int k = 0; k < kBlk; ++k) guard[k] = 1e-30 * pv[min(k0 + k, K - 1)];
-    int e = 0;
-#pragma unroll
-    for (int k = 0; k < kBlk; ++k) {
-      const double d = readLane(c[k], k);
-      // inv = 1/sqrt(d) from the f32 estimate + two Newton steps in f64; pivots whose Jacobi-scaled value d / (diag + 10) is
-      // below 1e-30 are treated as zero, as a rank-revealing factorisation would
-      const bool okp = d > guard[k];
-      double inv = static_cast<double>(__frsqrt_rn(static_cast<float>(okp ? d : 1.0)));
-      inv = inv * (1.5 - 0.5 * d * inv * inv);
-      inv = inv * (1.5 - 0.5 * d * inv * inv);
-      inv = okp ? inv : 0.0;
-      invd[k] = inv;
-      const double l = c[k] * inv;  // lane k: sqrt(d); lanes i > k: l_ik
-      c[k] = l;
-#pragma unroll
-      for (int j = k + 1; j < kBlk; ++j) {
-        const double ljk = readLane(l, j);
-        lj[e++] = ljk;
-        c[j] -= l * ljk;
-      }
-    }
-    if (valid) {
-      double *dst = A + row * ld + k0;
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j)
-        if (lane >= kBlk || j <= lane) dst[j] = c[j];  // the diagonal block keeps its lower triangle only
-    }
-    // rows beyond the first 64 of this block column (windows of more than 7 frames): substitution with the broadcast factors
-    for (int r2 = row + 64; r2 < N; r2 += 64) {
-      double v[kBlk];
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) v[j] = A[r2 * ld + k0 + j];
-      int e2 = 0;
-#pragma unroll
-      for (int k = 0; k < kBlk; ++k) {
-        v[k] *= invd[k];
-#pragma unroll
-        for (int j = k + 1; j < kBlk; ++j) v[j] -= v[k] * lj[e2++];
-      }
-#pragma unroll
-      for (int j = 0; j < kBlk; ++j) A[r2 * ld + k0 + j] = v[j];
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int cidx = 0; cidx < kBlk; ++cidx) Linv[kb * 36 + lowIdx(cidx, cidx)] = invd[cidx];  // diagonal of the inverse; completed below
-    }
-  };
-  if (wave == 0) factorAndPanel(0);
-  __syncthreads();
-  DSOPP_STAMP(16);
-  for (int kb = 0; kb < F; ++kb) {
-    const int k0 = kb * kBlk, k1 = k0 + kBlk, k2 = k1 + kBlk;
-    if (kb + 1 < F) {
-      // all waves: block column kb+1 (rows k1 .. N-1, columns k1 .. k1+7) -= panel kb contribution (one element per thread)
-      const int n_el = (N - k1) * kBlk;
-      for (int e = tid; e < n_el; e += kSolveThreads) {
-        const int row = k1 + (e >> 3), col = k1 + (e & 7);
-        if (col > row) continue;
-        const double *li = A + row * ld + k0, *lj = A + col * ld + k0;
-        double sacc = 0;
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) sacc += li[c] * lj[c];
-        A[row * ld + col] -= sacc;
-      }
-    }
-    __syncthreads();
-    DSOPP_STAMP(17 + 3 * kb);
-    if (wave == 0) {
-      if (kb + 1 < F) factorAndPanel(kb + 1);
-      DSOPP_STAMP(18 + 3 * kb);
-    } else {
-      // trailing update of columns >= k2 with panel kb: A_ij -= sum_c L_ic L_jc  (192 threads as a 12 x 16 tile)
-      const int t = tid - 64, tr = t >> 4, tc = t & 15;
-      for (int row = k2 + tr; row < N; row += 12) {
-        const double *li = A + row * ld + k0;
-        double lic[kBlk];
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) lic[c] = li[c];
-        for (int col = k2 + tc; col <= row; col += 16) {
-          const double *lj = A + col * ld + k0;
-          double sacc = 0;
-#pragma unroll
-          for (int c = 0; c < kBlk; ++c) sacc += lic[c] * lj[c];
-          A[row * ld + col] -= sacc;
-        }
-      }
-    }
-    __syncthreads();
-    DSOPP_STAMP(19 + 3 * kb);
-  }
-  // ---- back substitution x = L^-T y (y = row K of L), column-oriented on one wave: lane j carries y_j (and y_{j+64});
-  // going down from k = K-1, x_k = y_k / L_kk is broadcast with v_readlane and every lane j < k takes y_j -= L_kj x_k.
-  // 4-7 instructions per unknown, no LDS round trip or barrier inside the chain (L_kj is prefetched a frame block ahead).
-  DSOPP_STAMP(3);
-  if (wave == 0) {
-    // No masking anywhere: lane j is consumed at step k = j (x_j = y_j / L_jj); whatever the later steps k < j add to it
-    // (entries on / above the diagonal, uninitialised LDS) is never read again.  x_k leaves the chain as a wave-uniform
-    // value and is written to LDS by lane 0, eight at a time.
-    auto run = [&](auto two_tag) {
-      constexpr bool TWO = decltype(two_tag)::value;
-      const int j0 = lane, j1 = lane + 64;
-      double y0 = j0 < K ? A[K * ld + j0] : 0.0, y1 = (TWO && j1 < K) ? A[K * ld + j1] : 0.0;
-      const double gi0 = j0 < K ? Linv[(j0 >> 3) * 36 + lowIdx(j0 & 7, j0 & 7)] : 0.0;
-      const double gi1 = (TWO && j1 < K) ? Linv[(j1 >> 3) * 36 + lowIdx(j1 & 7, j1 & 7)] : 0.0;
-      double g0[kBlk], g1[kBlk], n0[kBlk], n1[kBlk];
-      auto loadBlock = [&](int kb, double *o0, double *o1) {
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) {
-          o0[c] = A[(kb * kBlk + c) * ld + j0];  // lanes beyond the row read into the next row: in bounds, never used
-          if (TWO) o1[c] = j1 < K ? A[(kb * kBlk + c) * ld + j1] : 0.0;
-        }
-      };
-      loadBlock(F - 1, g0, g1);
-      for (int kb = F - 1; kb >= 0; --kb) {
-        if (kb > 0) loadBlock(kb - 1, n0, n1);
-        double xo[kBlk];
-#pragma unroll
-        for (int c = kBlk - 1; c >= 0; --c) {
-          const int k = kb * kBlk + c;
-          const double xk = (!TWO || k < 64) ? readLane(y0 * gi0, k & 63) : readLane(y1 * gi1, k & 63);
-          xo[c] = xk;
-          y0 -= g0[c] * xk;
-          if (TWO) y1 -= g1[c] * xk;
-        }
-        if (lane == 0) {
-#pragma unroll
-          for (int c = 0; c < kBlk; ++c) xs[kb * kBlk + c] = xo[c];
-        }
-#pragma unroll
-        for (int c = 0; c < kBlk; ++c) {
-          g0[c] = n0[c];
-          if (TWO) g1[c] = n1[c];
-        }
-      }
-    };
-    if (K > 64)
-      run(std::true_type{});
-    else
-      run(std::false_type{});
-  }
+  choleskyAugmented<kSolveThreads>(A, pv, Linv, F, tid, nullptr);
+  if (tid < 64) backSubstituteWave(A, Linv, xs, F, tid);  // wave 0
   __syncthreads();
   if (tid < K) {
     const double x = xs[tid];
-    stpl[tid] = -x;
     a.step[tid] = x;
     a.st->step[tid >> 3][tid & 7] = -x;  // problem.hpp:353-357
   }
-  DSOPP_STAMP(4);
-  if (fast_refresh) {
-    // FEJ: only the current reprojection / brightness constants move with the state; all inputs are in registers / LDS
-    ldsBarrier();
-    Rigid *E = reinterpret_cast<Rigid *>(A);  // [2][F]: exp(+xi_f), exp(-xi_f); A is free now
-    if (tid < 2 * F) {
-      const int f = tid < F ? tid : tid - F;
-      const double sign = tid < F ? 1.0 : -1.0;
-      double xi[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) xi[i] = sign * (epsl[kBlk * f + i] + stpl[kBlk * f + i]);
-      E[tid] = rigidExp(xi);
-    }
-    ldsBarrier();
-    if (tid < F * F && pp.valid) {
-      const int r = tid / F, t = tid - F * (tid / F);
-      PairConst &P = a.pc[r * kMaxFrames + t];
-      const Rigid T_tr = rigidMul(E[F + t], rigidMul(pp.T0, E[r]));
-      // ArrayReprojector ctor — camera_reproject.hpp:235-260 (as buildProjectionMatrices)
-      const double ifx = 1.0 / pp.fxr, ify = 1.0 / pp.fyr;
-      const double k02 = -pp.cxr * ifx, k12 = -pp.cyr * ify;
-      double U[12];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        U[4 * i + 0] = T_tr.R[3 * i + 0] * ifx;
-        U[4 * i + 1] = T_tr.R[3 * i + 1] * ify;
-        U[4 * i + 2] = T_tr.R[3 * i + 0] * k02 + T_tr.R[3 * i + 1] * k12 + T_tr.R[3 * i + 2];
-        U[4 * i + 3] = T_tr.t[i];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        P.M[0 + j] = pp.fxt * U[0 + j] + pp.cxt * U[8 + j];
-        P.M[4 + j] = pp.fyt * U[4 + j] + pp.cyt * U[8 + j];
-        P.M[8 + j] = U[8 + j];
-      }
-      const double a_r = ab0l[2 * r] + epsl[kBlk * r + 6] + stpl[kBlk * r + 6];
-      const double a_t = ab0l[2 * t] + epsl[kBlk * t + 6] + stpl[kBlk * t + 6];
-      P.s = (pp.exposure_t / pp.exposure_r) * exp(a_t - a_r);
-      P.b_t = ab0l[2 * t + 1] + epsl[kBlk * t + 7] + stpl[kBlk * t + 7];
-      P.b_r = ab0l[2 * r + 1] + epsl[kBlk * r + 7] + stpl[kBlk * r + 7];
-    }
-  } else {
-    __syncthreads();  // the state written above is re-read from memory below
-    Rigid *E = reinterpret_cast<Rigid *>(A);
-    if (tid < 2 * F) E[tid] = frameIncrement(a.st, tid % F, tid < F ? 1.0 : -1.0);
-    __syncthreads();
-    // without first-estimate Jacobians every pair constant moves with the state: the host launches pairSetupKernel right
-    // after this kernel (keeping that 15 KB routine and its stack frame out of here spares every launch the scratch setup)
-    if (tid < F * F && a.fej) refreshPairCurrent(a.frames, a.st, a.pc, tid / F, tid % F, E[tid / F], E[F + tid % F]);
-  }
-  DSOPP_STAMP(5);
-  if (a.ctrl) {
-    // prior + marginal energy at the candidate state x = eps + step (calculateEnergy, problem.hpp:293-312)
-    double part = 0;
-    if (tid < K) {
-      const double xc = epsl[tid] + stpl[tid];
-      if (a.use_marginal) {
-        double sacc = 0;
-        for (int k = 0; k < K; ++k) sacc += a.Hm[tid * K + k] * (epsl[k] + stpl[k]);
-        part += bm_c * xc + 0.5 * xc * sacc;
-      }
-      if ((tid & 7) >= 6) {
-        const double ab = ab0_c + xc;
-        part += 0.5 * ab * a.affine_reg[(tid & 7) - 6] * ab;
-      }
-    }
-    // frame part of the norms acceptStep reports for this candidate (problem.hpp:366-388): read by the deciding kernel from the
-    // control block
-    double nstate = 0, nstep = 0;
-    if (tid < K) {
-      nstate = epsl[tid] * epsl[tid] + ((tid & 7) >= 6 ? ab0_c * ab0_c : 0.0);
-      nstep = stpl[tid] * stpl[tid];
-    }
-    part = waveSum(part);
-    nstate = waveSum(nstate);
-    nstep = waveSum(nstep);
-    ldsBarrier();  // E (in A) fully consumed before the scratch below is written; stpl visible
-    if ((tid & 63) == 0) {
-      xs[tid >> 6] = part;
-      xs[4 + (tid >> 6)] = nstate;
-      xs[8 + (tid >> 6)] = nstep;
-    }
-    ldsBarrier();
-    if (tid == 0) {
-      static_assert(kSolveThreads / 64 == 4, "three groups of four wave sums in xs");
-      double total = a.energy_marginalized, s_state = 0, s_step = 0;
-      for (int w = 0; w < kSolveThreads / 64; ++w) {
-        total += xs[w];
-        s_state += xs[4 + w];
-        s_step += xs[8 + w];
-      }
-      a.ctrl->cand_prior = total;
-      a.ctrl->frame_state_sq = s_state;
-      a.ctrl->frame_step_sq = s_step;
-      a.ctrl->pending = 1;
-    }
-  }
-  DSOPP_STAMP(6);
+  __syncthreads();  // the state written above is re-read from memory below
+  Rigid *E = reinterpret_cast<Rigid *>(A);  // [2][F]: exp(+xi_f), exp(-xi_f); A is free now
+  if (tid < 2 * F) E[tid] = frameIncrement(a.st, tid % F, tid < F ? 1.0 : -1.0);
+  __syncthreads();
+  // FEJ: only the current reprojection / brightness constants move with the state.  Without first-estimate Jacobians every pair
+  // constant moves with it: the host launches pairSetupKernel right after this kernel (keeping that 15 KB routine and its stack frame
+  // out of here spares every launch the scratch setup)
+  if (tid < F * F && a.fej) refreshPairCurrent(a.frames, a.st, a.pc, tid / F, tid % F, E[tid / F], E[F + tid % F]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -54,7 +54,7 @@ def main():
     labels = (("sweep_linearize", f"sweepKernel<{S}, true, true, true, false"),
               ("sweep_linearize_loop", f"sweepKernel<{S}, true, true, true, false"),
               ("sweep_energy", f"sweepKernel<{S}, false, true, true, false"),
-              ("schur", "reduceSchurKernel"), ("assemble_solve", "assembleSolveKernel"))
+              ("schur", "reduceSchurKernel"), ("assemble_solve", "solveCombinedKernel"))
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         rows = run_pass(counter)
         by_kernel = {}
