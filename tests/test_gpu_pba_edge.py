@@ -1,5 +1,6 @@
 """GPU parity on the shapes the reference's solver tests and its tracker exercise beyond the 4-frame clique: minimum and
-large windows (K > 64 takes the second row chunk of the solve kernel and the second target group of the sweeps), ragged
+large windows (K > 64 takes the second row chunk of the solve kernel — checked at stage level, size by size, against a backward-error
+bound in tests/test_gpu_dense_solve.py; here end to end — and the second target group of the sweeps), ragged
 landmark counts incl. an empty frame, pre-set residual statuses and landmark flags, and the C1
 bench configuration itself at full size.  Same bars as tests/test_gpu_pba.py (pose update bar of BASELINE.json: 1e-5)."""
 import numpy as np
