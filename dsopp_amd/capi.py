@@ -44,6 +44,8 @@ SYMBOLS = [
     "dsopp_hip_comm_allreduce", "dsopp_hip_window_set_comm",
     "dsopp_hip_window_optimize_async", "dsopp_hip_window_optimize_wait",
     "dsopp_hip_immature_sets_estimate",
+    "dsopp_hip_undistorter_create", "dsopp_hip_undistorter_destroy", "dsopp_hip_undistorter_sizes", "dsopp_hip_undistorter_undistort",
+    "dsopp_hip_undistorter_undistort_device", "dsopp_hip_pyramid_build_undistorted", "dsopp_hip_feature_extractor_extract_from_pyramid",
     "dsopp_hip_feature_extractor_create", "dsopp_hip_feature_extractor_destroy", "dsopp_hip_feature_extractor_set_mask",
     "dsopp_hip_feature_extractor_extract", "dsopp_hip_feature_extractor_get_state", "dsopp_hip_features_shuffle_order",
     "dsopp_hip_feature_extractor_create_eigen", "dsopp_hip_feature_extractor_get_eigen_stats", "dsopp_hip_eigen_random_pattern",
@@ -146,6 +148,50 @@ def default_align_options(**kw) -> Options:
     return o
 
 
+class Undistorter:
+    """sensors::calibration::Undistorter on the device (dsopp_hip_undistorter): in_size / out_size = (width, height); map_x / map_y =
+    the two float32 remap tables of shape (out_height, out_width), both None = the identity."""
+
+    def __init__(self, in_size, out_size, map_x=None, map_y=None, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.in_size, self.out_size, self.device = (int(in_size[0]), int(in_size[1])), (int(out_size[0]), int(out_size[1])), device
+        mx = None if map_x is None else np.ascontiguousarray(map_x, dtype=np.float32)
+        my = None if map_y is None else np.ascontiguousarray(map_y, dtype=np.float32)
+        for m in (mx, my):
+            assert m is None or m.shape == (self.out_size[1], self.out_size[0]), m.shape
+        _chk(lib().dsopp_hip_undistorter_create(int(device), C.c_void_p(stream or 0), self.in_size[0], self.in_size[1], self.out_size[0],
+                                                self.out_size[1], _p(mx, np.float32), _p(my, np.float32), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_undistorter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sizes(self):
+        """((in_width, in_height), (out_width, out_height)) as the handle reports them"""
+        v = [C.c_int() for _ in range(4)]
+        _chk(lib().dsopp_hip_undistorter_sizes(self._h, *[C.byref(x) for x in v]))
+        return (v[0].value, v[1].value), (v[2].value, v[3].value)
+
+    def undistort(self, image):
+        """Undistorter::undistort(image): (in_height, in_width) uint8 -> (out_height, out_width) uint8, blocking"""
+        img = _u8(image)
+        assert img.shape == (self.in_size[1], self.in_size[0]), img.shape
+        out = np.zeros((self.out_size[1], self.out_size[0]), dtype=np.uint8)
+        _chk(lib().dsopp_hip_undistorter_undistort(self._h, _p(img, np.uint8), _p(out, np.uint8)))
+        return out
+
+    def undistort_device(self, in_ptr, out_ptr, stream=None):
+        """the same between two device buffers (addresses as integers): enqueues on `stream`, None = the undistorter's own"""
+        _chk(lib().dsopp_hip_undistorter_undistort_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+
 class Pyramid:
     """Device-resident image pyramid of one frame (dsopp_hip_pyramid)."""
 
@@ -171,6 +217,15 @@ class Pyramid:
         img = _u8(image_u8)
         assert img.shape == (self.height, self.width)
         _chk(lib().dsopp_hip_pyramid_build(self._h, _p(img, np.uint8), _p(None if lut is None else _f64(lut)), _p(_u8(vignetting), np.uint8)))
+
+    def build_undistorted(self, undistorter: "Undistorter", image, lut=None, vignetting=None):
+        """build(undistorter.undistort(image)) without the host round trip; vignetting is the already undistorted vignette"""
+        img = _u8(image)
+        assert img.shape == (undistorter.in_size[1], undistorter.in_size[0]), img.shape
+        vig = _u8(vignetting)
+        assert vig is None or vig.shape == (self.height, self.width)
+        _chk(lib().dsopp_hip_pyramid_build_undistorted(self._h, undistorter._h, _p(img, np.uint8), _p(None if lut is None else _f64(lut)),
+                                                       _p(vig, np.uint8)))
 
     def build_device(self, image_dev_ptr, lut=None, vignetting_dev_ptr=None, vignetting_max=0.0):
         _chk(lib().dsopp_hip_pyramid_build_device(self._h, C.c_void_p(image_dev_ptr), _p(None if lut is None else _f64(lut)),
@@ -991,6 +1046,24 @@ class FeatureExtractor:
         if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: the state is unchanged, run again with the room reported
             self._capacity = n
             rc, xy, n = self.extract_raw(image, self._capacity)
+        _chk(rc)
+        return xy
+
+    def extract_from_pyramid_raw(self, pyramid: Pyramid, capacity):
+        """one dsopp_hip_feature_extractor_extract_from_pyramid call: (return code, xy (n, 2) or None, n)"""
+        xy = np.zeros((max(int(capacity), 1), 2))
+        n = C.c_int32()
+        rc = lib().dsopp_hip_feature_extractor_extract_from_pyramid(self._h, pyramid._h, int(capacity), _p(xy), C.byref(n))
+        return rc, (xy[:n.value].copy() if rc == 0 else None), n.value
+
+    def extract_from_pyramid(self, pyramid: Pyramid, mask=None):
+        """extract(image, mask) of the undistorted image `pyramid` kept from its last build_undistorted"""
+        if (mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask)):
+            self.set_mask(mask)
+        rc, xy, n = self.extract_from_pyramid_raw(pyramid, self._capacity)
+        if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: the state is unchanged, run again with the room reported
+            self._capacity = n
+            rc, xy, n = self.extract_from_pyramid_raw(pyramid, self._capacity)
         _chk(rc)
         return xy
 

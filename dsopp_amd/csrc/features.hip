@@ -169,6 +169,99 @@ int updatedThreshold(int num_pixels, int desired, int found, int thr) {
   return static_cast<int>(t);
 }
 
+/** SobelTrackingFeaturesExtractor::extract over the 8-bit image img_dev, which the extractor's stream may read */
+void sobelExtract(dsopp_hip_feature_extractor *ex, const uint8_t *img_dev, int32_t capacity, double *xy, int32_t *n) {
+  hipStream_t st = ex->sr.stream;
+  const int W = ex->width, H = ex->height, N = W * H;
+  // everything below is computed into locals and committed at the end: a failed call leaves the state as it was
+  bool initialized = ex->initialized;
+  int thr = ex->threshold, ws = ex->window_size;
+  double density = ex->density;
+  if (!initialized) {
+    HIP_CHECK(hipMemsetAsync(ex->d_hist.ptr, 0, kGradBins * sizeof(unsigned), st));
+    sobelKernel<true><<<std::min(gridFor(N), 256u), kBlock, 0, st>>>(img_dev, W, H, ex->d_grad.ptr, ex->d_hist.ptr);
+    HIP_CHECK(hipGetLastError());
+    ex->h_hist.reserve(kGradBins * sizeof(unsigned));
+    HIP_CHECK(hipMemcpyAsync(ex->h_hist.get(), ex->d_hist.ptr, kGradBins * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    ex->sr.sync();
+    // quantile(): nth_element at k = (long)(size * q) — the k-th smallest norm, read off the cumulative histogram
+    const long k = static_cast<long>(static_cast<double>(N) * ex->quantile);
+    const unsigned *h = ex->h_hist.get();
+    long cum = 0;
+    thr = kGradBins - 1;
+    for (int b = 0; b < kGradBins; ++b) {
+      cum += h[b];
+      if (cum > k) {
+        thr = b;
+        break;
+      }
+    }
+    double potential = std::sqrt(static_cast<double>(N) * (1.0 - ex->quantile) / density);
+    if (potential < 1.0) {
+      density *= potential * potential / (1.0 * 1.0);
+      potential = 1.0;
+    }
+    ws = static_cast<int>(potential);
+    initialized = true;
+  } else {
+    sobelKernel<false><<<std::min(gridFor(N), 2048u), kBlock, 0, st>>>(img_dev, W, H, ex->d_grad.ptr, nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  // windows at y = 0, ws, ... while y + ws < H, the same in x
+  const int nwx = (W - 1) / ws, nwy = (H - 1) / ws, nwin = nwx * nwy;
+  int found = 0;
+  if (nwin > 0) {
+    windowFirstHitKernel<<<static_cast<unsigned>((nwin + kBlock / 64 - 1) / (kBlock / 64)), kBlock, 0, st>>>(
+        ex->d_grad.ptr, ex->has_mask ? ex->d_valid.ptr : nullptr, W, ws, nwx, nwin, thr, ex->d_hit.ptr);
+    HIP_CHECK(hipGetLastError());
+    size_t temp_bytes = 0;
+    HIP_CHECK(hipcub::DeviceSelect::If(nullptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
+    ex->d_temp.reserve(std::max<size_t>(1, temp_bytes), 0, st);
+    HIP_CHECK(hipcub::DeviceSelect::If(ex->d_temp.ptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
+    HIP_CHECK(hipMemcpyAsync(ex->h_count.get(), ex->d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    ex->sr.sync();
+    found = *ex->h_count.get();
+  }
+
+  // truncation to (long)density after the shuffle (:128-131)
+  const long needed = static_cast<double>(found) > density ? static_cast<long>(density) : found;
+  *n = static_cast<int32_t>(needed);
+  if (needed > capacity) fail(DSOPP_HIP_ERR_CAPACITY, "capacity %d < %ld features", capacity, needed);
+
+  thr = updatedThreshold(N, static_cast<int>(density), found, thr);
+
+  std::vector<int> perm(static_cast<size_t>(found));
+  std::iota(perm.begin(), perm.end(), 0);
+  std::shuffle(perm.begin(), perm.end(), std::default_random_engine{});
+  std::vector<int> final_list(static_cast<size_t>(needed));
+  if (needed > 0) {
+    ex->h_list.reserve(static_cast<size_t>(found) * sizeof(int));
+    HIP_CHECK(hipMemcpyAsync(ex->h_list.get(), ex->d_list.ptr, static_cast<size_t>(found) * sizeof(int), hipMemcpyDeviceToHost, st));
+    ex->sr.sync();
+    const int *list = ex->h_list.get();
+    for (long i = 0; i < needed; ++i) {
+      const int idx = list[perm[static_cast<size_t>(i)]];
+      final_list[static_cast<size_t>(i)] = idx;
+      xy[2 * i] = static_cast<double>(idx % W);
+      xy[2 * i + 1] = static_cast<double>(idx / W);
+    }
+    // the list stays on the device for the immature-landmark build (the stream is idle: the pinned buffer's last upload is done)
+    ex->d_final.reserve(static_cast<size_t>(needed), 0, st);
+    ex->h_final.reserve(static_cast<size_t>(needed) * sizeof(int));
+    std::memcpy(ex->h_final.get(), final_list.data(), static_cast<size_t>(needed) * sizeof(int));
+    HIP_CHECK(hipMemcpyAsync(ex->d_final.ptr, ex->h_final.get(), static_cast<size_t>(needed) * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  HIP_CHECK(hipEventRecord(ex->final_ready.h, st));
+
+  ex->initialized = initialized;
+  ex->threshold = thr;
+  ex->window_size = ws;
+  ex->density = density;
+  ex->found_last = found;
+  ex->final_list = std::move(final_list);
+}
+
 }  // namespace
 }  // namespace dsopp_hip
 
@@ -248,101 +341,28 @@ int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const 
 int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n) {
   return guarded([&] {
     if (!ex || !image_host || !n || capacity < 0 || (capacity > 0 && !xy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    if (ex->kind == ExtractorKind::Eigen) return eigenExtract(ex, image_host, capacity, xy, n);
+    if (ex->kind == ExtractorKind::Eigen) return eigenExtract(ex, image_host, nullptr, capacity, xy, n);
     ex->sr.use();
     hipStream_t st = ex->sr.stream;
-    const int W = ex->width, H = ex->height, N = W * H;
+    const size_t N = static_cast<size_t>(ex->width) * ex->height;
     // the caller's image leaves from pinned memory (the stream is idle here: every call ends with a synchronisation)
-    std::memcpy(ex->h_image.get(), image_host, static_cast<size_t>(N));
-    HIP_CHECK(hipMemcpyAsync(ex->d_image.ptr, ex->h_image.get(), static_cast<size_t>(N), hipMemcpyHostToDevice, st));
+    std::memcpy(ex->h_image.get(), image_host, N);
+    HIP_CHECK(hipMemcpyAsync(ex->d_image.ptr, ex->h_image.get(), N, hipMemcpyHostToDevice, st));
+    sobelExtract(ex, ex->d_image.ptr, capacity, xy, n);
+  });
+}
 
-    // everything below is computed into locals and committed at the end: a failed call leaves the state as it was
-    bool initialized = ex->initialized;
-    int thr = ex->threshold, ws = ex->window_size;
-    double density = ex->density;
-    if (!initialized) {
-      HIP_CHECK(hipMemsetAsync(ex->d_hist.ptr, 0, kGradBins * sizeof(unsigned), st));
-      sobelKernel<true><<<std::min(gridFor(N), 256u), kBlock, 0, st>>>(ex->d_image.ptr, W, H, ex->d_grad.ptr, ex->d_hist.ptr);
-      HIP_CHECK(hipGetLastError());
-      ex->h_hist.reserve(kGradBins * sizeof(unsigned));
-      HIP_CHECK(hipMemcpyAsync(ex->h_hist.get(), ex->d_hist.ptr, kGradBins * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      ex->sr.sync();
-      // quantile(): nth_element at k = (long)(size * q) — the k-th smallest norm, read off the cumulative histogram
-      const long k = static_cast<long>(static_cast<double>(N) * ex->quantile);
-      const unsigned *h = ex->h_hist.get();
-      long cum = 0;
-      thr = kGradBins - 1;
-      for (int b = 0; b < kGradBins; ++b) {
-        cum += h[b];
-        if (cum > k) {
-          thr = b;
-          break;
-        }
-      }
-      double potential = std::sqrt(static_cast<double>(N) * (1.0 - ex->quantile) / density);
-      if (potential < 1.0) {
-        density *= potential * potential / (1.0 * 1.0);
-        potential = 1.0;
-      }
-      ws = static_cast<int>(potential);
-      initialized = true;
-    } else {
-      sobelKernel<false><<<std::min(gridFor(N), 2048u), kBlock, 0, st>>>(ex->d_image.ptr, W, H, ex->d_grad.ptr, nullptr);
-      HIP_CHECK(hipGetLastError());
-    }
-
-    // windows at y = 0, ws, ... while y + ws < H, the same in x
-    const int nwx = (W - 1) / ws, nwy = (H - 1) / ws, nwin = nwx * nwy;
-    int found = 0;
-    if (nwin > 0) {
-      windowFirstHitKernel<<<static_cast<unsigned>((nwin + kBlock / 64 - 1) / (kBlock / 64)), kBlock, 0, st>>>(
-          ex->d_grad.ptr, ex->has_mask ? ex->d_valid.ptr : nullptr, W, ws, nwx, nwin, thr, ex->d_hit.ptr);
-      HIP_CHECK(hipGetLastError());
-      size_t temp_bytes = 0;
-      HIP_CHECK(hipcub::DeviceSelect::If(nullptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
-      ex->d_temp.reserve(std::max<size_t>(1, temp_bytes), 0, st);
-      HIP_CHECK(hipcub::DeviceSelect::If(ex->d_temp.ptr, temp_bytes, ex->d_hit.ptr, ex->d_list.ptr, ex->d_count.ptr, nwin, IsHit{}, st));
-      HIP_CHECK(hipMemcpyAsync(ex->h_count.get(), ex->d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-      ex->sr.sync();
-      found = *ex->h_count.get();
-    }
-
-    // truncation to (long)density after the shuffle (:128-131)
-    const long needed = static_cast<double>(found) > density ? static_cast<long>(density) : found;
-    *n = static_cast<int32_t>(needed);
-    if (needed > capacity) fail(DSOPP_HIP_ERR_CAPACITY, "capacity %d < %ld features", capacity, needed);
-
-    thr = updatedThreshold(N, static_cast<int>(density), found, thr);
-
-    std::vector<int> perm(static_cast<size_t>(found));
-    std::iota(perm.begin(), perm.end(), 0);
-    std::shuffle(perm.begin(), perm.end(), std::default_random_engine{});
-    std::vector<int> final_list(static_cast<size_t>(needed));
-    if (needed > 0) {
-      ex->h_list.reserve(static_cast<size_t>(found) * sizeof(int));
-      HIP_CHECK(hipMemcpyAsync(ex->h_list.get(), ex->d_list.ptr, static_cast<size_t>(found) * sizeof(int), hipMemcpyDeviceToHost, st));
-      ex->sr.sync();
-      const int *list = ex->h_list.get();
-      for (long i = 0; i < needed; ++i) {
-        const int idx = list[perm[static_cast<size_t>(i)]];
-        final_list[static_cast<size_t>(i)] = idx;
-        xy[2 * i] = static_cast<double>(idx % W);
-        xy[2 * i + 1] = static_cast<double>(idx / W);
-      }
-      // the list stays on the device for the immature-landmark build (the stream is idle: the pinned buffer's last upload is done)
-      ex->d_final.reserve(static_cast<size_t>(needed), 0, st);
-      ex->h_final.reserve(static_cast<size_t>(needed) * sizeof(int));
-      std::memcpy(ex->h_final.get(), final_list.data(), static_cast<size_t>(needed) * sizeof(int));
-      HIP_CHECK(hipMemcpyAsync(ex->d_final.ptr, ex->h_final.get(), static_cast<size_t>(needed) * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    HIP_CHECK(hipEventRecord(ex->final_ready.h, st));
-
-    ex->initialized = initialized;
-    ex->threshold = thr;
-    ex->window_size = ws;
-    ex->density = density;
-    ex->found_last = found;
-    ex->final_list = std::move(final_list);
+int dsopp_hip_feature_extractor_extract_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p, int32_t capacity, double *xy, int32_t *n) {
+  return guarded([&] {
+    if (!ex || !p || !n || capacity < 0 || (capacity > 0 && !xy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->has_undistorted) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the pyramid keeps no 8-bit image: it was not built by dsopp_hip_pyramid_build_undistorted");
+    if (p->width != ex->width || p->height != ex->height)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "pyramid is %d x %d, the extractor %d x %d", p->width, p->height, ex->width, ex->height);
+    if (p->sr.device != ex->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "extractor / pyramid live on another device");
+    ex->sr.use();
+    p->waitReady(ex->sr.stream);  // the remap is enqueued in front of the build that the event follows
+    if (ex->kind == ExtractorKind::Eigen) return eigenExtract(ex, nullptr, p->undistorted_u8.get(), capacity, xy, n);
+    sobelExtract(ex, p->undistorted_u8.get(), capacity, xy, n);
   });
 }
 

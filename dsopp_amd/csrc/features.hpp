@@ -60,6 +60,7 @@ struct dsopp_hip_feature_extractor {
 };
 
 namespace dsopp_hip {
-/** dsopp_hip_feature_extractor_extract for an eigen handle (features_eigen.hip) */
-void eigenExtract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n);
+/** dsopp_hip_feature_extractor_extract / _extract_from_pyramid for an eigen handle (features_eigen.hip): the image from the host, or,
+ *  when image_host is null, the 8-bit image image_dev that the extractor's stream may read */
+void eigenExtract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, const uint8_t *image_dev, int32_t capacity, double *xy, int32_t *n);
 }  // namespace dsopp_hip

@@ -530,12 +530,13 @@ int idealPotential(double ratio, int potential) {
 
 }  // namespace
 
-void eigenExtract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n) {
+void eigenExtract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, const uint8_t *image_dev, int32_t capacity, double *xy, int32_t *n) {
   EigenExtractorState &es = *ex->eigen;
   ex->sr.use();
   hipStream_t st = ex->sr.stream;
   const int W = ex->width, H = ex->height, N = W * H;
-  const int rc = dsopp_hip_pyramid_build(es.pyramid.get(), image_host, nullptr, nullptr);
+  const int rc = image_host ? dsopp_hip_pyramid_build(es.pyramid.get(), image_host, nullptr, nullptr)
+                            : dsopp_hip_pyramid_build_device(es.pyramid.get(), image_dev, nullptr, nullptr, 0.0);
   if (rc != DSOPP_HIP_OK) throw Error(rc, lastError());
   const dsopp_hip_pyramid &pyr = *es.pyramid;
   Levels L;

@@ -9,6 +9,7 @@
 // each thread regenerates from the parent plane (u8 + LUT at level 0, 2x2 means above) — reads are coalesced rows that
 // hit L2, writes are one full 16/32-byte texel per lane.  HBM-bound by construction: ~(1 + 4*sizeof(S)) bytes per pixel.
 #include "pyramid.hpp"
+#include "undistort.hpp"
 
 #include <memory>
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
@@ -419,6 +420,7 @@ int dsopp_hip_pyramid_build_device(dsopp_hip_pyramid *p, const void *image_dev, 
   return guarded([&] {
     if (!p || !image_dev) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
     p->sr.use();
+    p->has_undistorted = false;
     const double *lut_dev = nullptr;
     if (lut256) {
       HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
@@ -455,6 +457,32 @@ void copyToPinned(uint8_t *dst, const uint8_t *src, size_t n) {
 #endif
   std::memcpy(dst, src, n);
 }
+
+/** the caller's 8-bit image of n bytes through the pyramid's pinned buffer into dst_dev, enqueued on the pyramid's stream */
+void uploadImage(dsopp_hip_pyramid *p, uint8_t *dst_dev, const uint8_t *image_host, size_t n) {
+  HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)
+  p->h_image.reserve(n);
+  // In pieces: the DMA of a piece (1.3 MB over the host link: ~50 us, as long as the memcpy itself) runs while the host copies the next
+  // one — the consumer's wait for the pyramid shrinks by three quarters of the transfer
+  const size_t pieces = n >= (size_t(1) << 19) ? 4 : 1;
+  const size_t piece = ((n + pieces - 1) / pieces + 4095) & ~static_cast<size_t>(4095);
+  for (size_t off = 0; off < n; off += piece) {
+    const size_t len = std::min(piece, n - off);
+    copyToPinned(p->h_image.get() + off, image_host + off, len);
+    HIP_CHECK(hipMemcpyAsync(dst_dev + off, p->h_image.get() + off, len, hipMemcpyHostToDevice, p->sr.stream));
+  }
+}
+
+/** the vignette (may be null) into staging_vig; returns its maximum */
+double uploadVignette(dsopp_hip_pyramid *p, const uint8_t *vignetting_host, size_t n) {
+  double vmax = 0;
+  if (vignetting_host) {
+    // cv::minMaxLoc(vignetting, nullptr, &max) — photometrically_corrected_image.cpp:11-13
+    for (size_t i = 0; i < n; ++i) vmax = vignetting_host[i] > vmax ? vignetting_host[i] : vmax;
+    HIP_CHECK(hipMemcpyAsync(p->staging_vig.get(), vignetting_host, n, hipMemcpyHostToDevice, p->sr.stream));
+  }
+  return vmax;
+}
 }  // namespace
 
 int dsopp_hip_pyramid_build(dsopp_hip_pyramid *p, const uint8_t *image_host, const double *lut256, const uint8_t *vignetting_host) {
@@ -467,27 +495,48 @@ int dsopp_hip_pyramid_build(dsopp_hip_pyramid *p, const uint8_t *image_host, con
     // instead (a memcpy of 1.3 MB) and leaves from there as a DMA the call does not wait for: consumers order themselves behind the build
     // with waitReady(), as they do behind build_device.  (The buffer's previous upload has long completed: a pyramid is rebuilt once per
     // frame, and the synchronisation below covers the paths that keep it.)
-    HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)
-    p->h_image.reserve(n);
-    // In pieces: the DMA of a piece (1.3 MB over the host link: ~50 us, as long as the memcpy itself) runs while the host copies the next
-    // one — the consumer's wait for the pyramid shrinks by three quarters of the transfer
-    const size_t pieces = n >= (size_t(1) << 19) ? 4 : 1;
-    const size_t piece = ((n + pieces - 1) / pieces + 4095) & ~static_cast<size_t>(4095);
-    for (size_t off = 0; off < n; off += piece) {
-      const size_t len = std::min(piece, n - off);
-      copyToPinned(p->h_image.get() + off, image_host + off, len);
-      HIP_CHECK(hipMemcpyAsync(p->staging_u8.get() + off, p->h_image.get() + off, len, hipMemcpyHostToDevice, p->sr.stream));
-    }
-    double vmax = 0;
-    if (vignetting_host) {
-      // cv::minMaxLoc(vignetting, nullptr, &max) — photometrically_corrected_image.cpp:11-13
-      for (size_t i = 0; i < n; ++i) vmax = vignetting_host[i] > vmax ? vignetting_host[i] : vmax;
-      HIP_CHECK(hipMemcpyAsync(p->staging_vig.get(), vignetting_host, n, hipMemcpyHostToDevice, p->sr.stream));
-    }
+    uploadImage(p, p->staging_u8.get(), image_host, n);
+    const double vmax = uploadVignette(p, vignetting_host, n);
     int rc = dsopp_hip_pyramid_build_device(p, p->staging_u8.get(), lut256, vignetting_host ? p->staging_vig.get() : nullptr, vmax);
     if (rc != DSOPP_HIP_OK) throw Error(rc, lastError());
     // the LUT and the vignette are read straight from the caller's (pageable) arrays: those paths wait; the plain image path does not
     if (lut256 || vignetting_host) p->sr.sync();
+  });
+}
+
+int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const uint8_t *distorted_host, const double *lut256,
+                                        const uint8_t *vignetting_host) {
+  return guarded([&] {
+    if (!p || !u || !distorted_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (u->sr.device != p->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter lives on device %d, the pyramid on %d", u->sr.device, p->sr.device);
+    if (u->out_w != p->width || u->out_h != p->height)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the pyramid is %d x %d", u->out_w, u->out_h, p->width, p->height);
+    p->sr.use();
+    hipStream_t st = p->sr.stream;
+    const size_t n_in = static_cast<size_t>(u->in_w) * u->in_h, n = static_cast<size_t>(p->width) * p->height;
+    if (p->distorted_bytes < n_in) {
+      HIP_CHECK(hipStreamSynchronize(st));  // (the buffer that is replaced may still be read)
+      p->distorted_u8.alloc(n_in);
+      p->distorted_bytes = n_in;
+    }
+    if (!p->undistorted_u8) p->undistorted_u8.alloc(n);
+    p->has_undistorted = false;
+    uploadImage(p, p->distorted_u8.get(), distorted_host, n_in);
+    enqueueUndistort(u, p->distorted_u8.get(), p->undistorted_u8.get(), st);
+    const double vmax = uploadVignette(p, vignetting_host, n);  // already undistorted, as the reference keeps it (undistorted_vignetting_)
+    const double *lut_dev = nullptr;
+    if (lut256) {
+      HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, st));
+      lut_dev = p->lut_dev.get();
+    }
+    const uint8_t *vig_dev = vignetting_host ? p->staging_vig.get() : nullptr;
+    if (p->dtype == DSOPP_HIP_F64)
+      buildTyped<double>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
+    else
+      buildTyped<float>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
+    p->markReady();
+    p->has_undistorted = true;
+    if (lut256 || vignetting_host) p->sr.sync();  // (as in build: those two are read straight from the caller's arrays)
   });
 }
 
@@ -496,6 +545,7 @@ int dsopp_hip_pyramid_set_level(dsopp_hip_pyramid *p, int level, const double *p
     checkLevel(p, level);
     if (!pixelinfo_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null pixelinfo");
     p->sr.use();
+    p->has_undistorted = false;
     const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
     DeviceMem<double> tmp;
     tmp.alloc(n * 3 * sizeof(double));

@@ -91,6 +91,12 @@ struct dsopp_hip_pyramid {
   dsopp_hip::DeviceMem<uint8_t> staging_vig;
   dsopp_hip::PinnedMem<uint8_t> h_image;  // copy of the caller's 8-bit image (dsopp_hip_pyramid_build): the upload is a true DMA, the call does not wait for it
   dsopp_hip::DeviceMem<double> lut_dev;   // 256 doubles
+  // dsopp_hip_pyramid_build_undistorted: the distorted image as uploaded (sized by its first call) and its remap, the 8-bit image the
+  // levels are built from.  The remap is kept for dsopp_hip_feature_extractor_extract_from_pyramid, which reads it behind waitReady();
+  // every other rewrite of the image (build, build_device, set_level) clears has_undistorted.
+  dsopp_hip::DeviceMem<uint8_t> distorted_u8, undistorted_u8;
+  size_t distorted_bytes = 0;
+  bool has_undistorted = false;
   // Recorded on the pyramid's stream behind every write of the texels (build / build_device / set_level / set_mask).  A
   // consumer that reads the texels on another stream orders itself behind it with waitReady(): build_device only ENQUEUES
   // work, so without this a solve on the aligner's or the window's own stream could sample a half-built image.

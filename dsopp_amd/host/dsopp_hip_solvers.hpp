@@ -51,6 +51,35 @@ inline void check(int rc) {
   if (rc != DSOPP_HIP_OK) throw SolverError(rc, dsopp_hip_last_error());
 }
 
+/** sensors::calibration::Undistorter (undistorter.hpp:24-152) on the device: the two remap tables of constructRemaps, which stays host
+ *  code of the reference, folded into a device table once per camera.  No maps = Undistorter::Identity. */
+class HipUndistorter {
+ public:
+  HipUndistorter(int in_width, int in_height, int out_width, int out_height, const float *remap_x, const float *remap_y, int device = 0,
+                 void *stream = nullptr)
+      : out_width_(out_width), out_height_(out_height) {
+    check(dsopp_hip_undistorter_create(device, stream, in_width, in_height, out_width, out_height, remap_x, remap_y, &u_));
+  }
+  ~HipUndistorter() { dsopp_hip_undistorter_destroy(u_); }
+  HipUndistorter(const HipUndistorter &) = delete;
+  HipUndistorter &operator=(const HipUndistorter &) = delete;
+  /** undistort(img) of an 8-bit single-channel image, blocking: the static mask and the vignette (camera_fabric.cpp:164-167) */
+  std::vector<uint8_t> undistort(const uint8_t *image) const {
+    std::vector<uint8_t> out(static_cast<size_t>(out_width_) * static_cast<size_t>(out_height_));
+    check(dsopp_hip_undistorter_undistort(u_, image, out.data()));
+    return out;
+  }
+  /** the same between two 4-byte aligned device images; only enqueues on `stream` (nullptr = the undistorter's own) */
+  void undistortDevice(const void *image_dev, void *out_dev, void *stream = nullptr) const {
+    check(dsopp_hip_undistorter_undistort_device(u_, image_dev, out_dev, stream));
+  }
+  const dsopp_hip_undistorter *handle() const { return u_; }
+
+ private:
+  dsopp_hip_undistorter *u_ = nullptr;
+  int out_width_, out_height_;
+};
+
 /** device-resident pyramid of one frame = features::PixelDataFrame / ActiveKeyframe::pyramids() + masks */
 class DevicePyramid {
  public:
@@ -63,6 +92,12 @@ class DevicePyramid {
   /** PixelDataFrame(image, photometric_calibration, vignetting, levels) */
   void build(const uint8_t *image, const double *photometric_calibration256 = nullptr, const uint8_t *vignetting = nullptr) {
     check(dsopp_hip_pyramid_build(p_, image, photometric_calibration256, vignetting));
+  }
+  /** PixelDataFrame(undistorter.undistort(distorted_image), ...) — camera.cpp:70: the frame as the provider delivers it (grey), the
+   *  vignette already undistorted */
+  void buildUndistorted(const HipUndistorter &undistorter, const uint8_t *distorted_image, const double *photometric_calibration256 = nullptr,
+                        const uint8_t *undistorted_vignetting = nullptr) {
+    check(dsopp_hip_pyramid_build_undistorted(p_, undistorter.handle(), distorted_image, photometric_calibration256, undistorted_vignetting));
   }
   /** adopt a PixelMap<1> level built on the host by the reference */
   void setLevel(int level, const double *pixelinfo) { check(dsopp_hip_pyramid_set_level(p_, level, pixelinfo)); }
@@ -538,21 +573,13 @@ class HipTrackingFeaturesExtractor {
   /** image: W x H 8-bit grey (CameraFeatures::frame_data_); mask: the camera's level-0 CameraMask bytes, nullptr = all valid.  The mask
    *  is a per-camera constant (CameraFeatures::pyramidOfMasks()[0]): it is eroded again only when a different array is passed. */
   std::vector<Feature> extract(const uint8_t *image, const uint8_t *mask) {
-    if (!mask_set_ || mask != mask_) {
-      check(dsopp_hip_feature_extractor_set_mask(ex_, mask));
-      mask_ = mask;
-      mask_set_ = true;
-    }
-    int32_t n = 0;
-    int rc = dsopp_hip_feature_extractor_extract(ex_, image, static_cast<int32_t>(xy_.size() / 2), xy_.data(), &n);
-    if (rc == DSOPP_HIP_ERR_CAPACITY) {  // the state is unchanged: run again with the room reported
-      xy_.resize(2 * static_cast<size_t>(n));
-      rc = dsopp_hip_feature_extractor_extract(ex_, image, n, xy_.data(), &n);
-    }
-    check(rc);
-    std::vector<Feature> out(static_cast<size_t>(n));
-    for (size_t i = 0; i < out.size(); ++i) out[i] = {xy_[2 * i], xy_[2 * i + 1]};
-    return out;
+    return run(mask, [&](int32_t capacity, int32_t *n) { return dsopp_hip_feature_extractor_extract(ex_, image, capacity, xy_.data(), n); });
+  }
+  /** the same of the undistorted frame that `pyramid` kept from its last buildUndistorted: no second upload of the image */
+  std::vector<Feature> extractFromPyramid(const DevicePyramid &pyramid, const uint8_t *mask) {
+    return run(mask, [&](int32_t capacity, int32_t *n) {
+      return dsopp_hip_feature_extractor_extract_from_pyramid(ex_, pyramid.handle(), capacity, xy_.data(), n);
+    });
   }
   const dsopp_hip_feature_extractor *handle() const { return ex_; }
 
@@ -561,6 +588,25 @@ class HipTrackingFeaturesExtractor {
   dsopp_hip_feature_extractor *ex_ = nullptr;
 
  private:
+  /** set the mask when it changed, then `call(capacity, &n)`, once more with the room reported when the capacity was too small */
+  template <typename Call>
+  std::vector<Feature> run(const uint8_t *mask, Call call) {
+    if (!mask_set_ || mask != mask_) {
+      check(dsopp_hip_feature_extractor_set_mask(ex_, mask));
+      mask_ = mask;
+      mask_set_ = true;
+    }
+    int32_t n = 0;
+    int rc = call(static_cast<int32_t>(xy_.size() / 2), &n);
+    if (rc == DSOPP_HIP_ERR_CAPACITY) {  // the state is unchanged: run again with the room reported
+      xy_.resize(2 * static_cast<size_t>(n));
+      rc = call(n, &n);
+    }
+    check(rc);
+    std::vector<Feature> out(static_cast<size_t>(n));
+    for (size_t i = 0; i < out.size(); ++i) out[i] = {xy_[2 * i], xy_[2 * i + 1]};
+    return out;
+  }
   const uint8_t *mask_ = nullptr;
   bool mask_set_ = false;
   std::vector<double> xy_ = std::vector<double>(2 * 4096);

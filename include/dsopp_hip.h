@@ -112,6 +112,44 @@ int dsopp_hip_pyramid_get_level(dsopp_hip_pyramid *p, int level, double *pixelin
 int dsopp_hip_pyramid_level_size(dsopp_hip_pyramid *p, int level, int *width, int *height);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Image undistortion (replaces sensors::calibration::Undistorter::undistort — src/sensors/camera_calibration/src/undistorter.cpp:7-18 —
+ * which src/sensors/camera/src/camera.cpp:70 runs on every frame and src/sensors/sensors_builder/src/camera_fabric.cpp:164-167 once
+ * on the static mask and the vignette; src/sensors/camera_calibration/src/fabric.cpp:45-49,67-71 builds one for every simple_radial
+ * and TUM-FOV calibration)
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_undistorter dsopp_hip_undistorter;
+/* Undistorter(remapX, remapY, input_width, input_height) (undistorter.hpp:35-36): map_x / map_y are the two CV_32F remap tables
+ * (out_h x out_w floats, row-major) that constructRemaps (undistorter.hpp:69-142) fills on the host; the reference has out == in,
+ * both sizes are taken as cv::remap takes them.  NULL, NULL = Undistorter::Identity (undistorter.cpp:20-22; out must equal in).
+ * The arithmetic of every later undistort is integer and fixed here, for a single-channel 8-bit image (cv::remap INTER_LINEAR,
+ * BORDER_REFLECT_101, undistorter.cpp:16):
+ *   sx = rint(map_x * 32.0f) (half to even), ix = sx >> 5 (arithmetic: the floor), fx = sx & 31; sy, iy, fy alike;
+ *   taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1), each coordinate reflected on its own with period 2 (n - 1);
+ *   out = (sum of weight * tap + 16384) >> 15, weights (32 - fx)(32 - fy) * 32, fx (32 - fy) * 32, (32 - fx) fy * 32, fx fy * 32.
+ * So a map entry without fractions copies a pixel, and the failure marker (-1, -1) of estimateRemaps (undistorter.hpp:138-139)
+ * yields src[1, 1].  The maps are folded into a device table before the call returns and are not needed afterwards.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: a non-finite map entry, |entry| > 2^20, in_w < 2 or in_h < 2, only one of the two maps. */
+int dsopp_hip_undistorter_create(int device, void *stream, int in_w, int in_h, int out_w, int out_h, const float *map_x, const float *map_y,
+                                 dsopp_hip_undistorter **out);
+void dsopp_hip_undistorter_destroy(dsopp_hip_undistorter *u);
+/* input_width() / input_height() (undistorter.cpp:24-26) and the size of the maps; any pointer may be NULL */
+int dsopp_hip_undistorter_sizes(const dsopp_hip_undistorter *u, int *in_w, int *in_h, int *out_w, int *out_h);
+/* Undistorter::undistort(img) (undistorter.cpp:7-18) of an in_h x in_w 8-bit image into out_h x out_w bytes, blocking: the
+ * once-per-camera form for the static mask and the vignette (camera_fabric.cpp:164-167). */
+int dsopp_hip_undistorter_undistort(dsopp_hip_undistorter *u, const uint8_t *image_host, uint8_t *out_host);
+/* same, both images in HBM: the call only enqueues one launch on `stream` (a hipStream_t; NULL = the undistorter's own).  Both
+ * pointers must be 4-byte aligned, else DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+int dsopp_hip_undistorter_undistort_device(dsopp_hip_undistorter *u, const void *image_dev, void *out_dev, void *stream);
+/* The per-frame path, camera.cpp:70 followed by the PixelDataFrame ctor: dsopp_hip_pyramid_build of undistort(distorted_host).  The
+ * distorted in_h x in_w image goes through the pyramid's pinned buffer as in build, is remapped on the pyramid's stream into an 8-bit
+ * image the pyramid keeps (dsopp_hip_feature_extractor_extract_from_pyramid reads it), and the levels are built from that.
+ * vignetting_host is the vignette already undistorted, as the reference keeps it (undistorted_vignetting_,
+ * src/features/src/pixel_data_frame_extractor.cpp:8-14).  f64 and f32 pyramids.  The pyramid and the undistorter must be on one
+ * device and the pyramid's size must be the undistorter's out size, else DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const uint8_t *distorted_host, const double *lut256,
+                                        const uint8_t *vignetting_host);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Sliding-window photometric bundle adjustment
  * (replaces EigenPhotometricBundleAdjustment<SE3, PinholeCamera, 8, PixelMap, true, true, true, 1>)
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -494,6 +532,13 @@ int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const 
  * where the reference's threshold update is undefined (no feature found: an integer division by zero; a non-finite or
  * out-of-range quotient) the threshold is kept.  The list stays on the device for dsopp_hip_immature_set_create_from_features. */
 int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n);
+/* extract() of the undistorted 8-bit image that `p` kept from its last dsopp_hip_pyramid_build_undistorted — the reference extracts
+ * from the undistorted frame (camera.cpp:70, src/features/src/camera_features.cpp:36-41) — read on the device behind the pyramid's
+ * build, with no second upload.  Both kinds of extractor; lists, capacity contract and state as extract() of the same image from
+ * the host.  DSOPP_HIP_ERR_INVALID_ARGUMENT when the pyramid's last build was not build_undistorted, or its size or device is not
+ * the extractor's. */
+int dsopp_hip_feature_extractor_extract_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p, int32_t capacity, double *xy,
+                                                     int32_t *n);
 /* the extractor's state after the last extract (any pointer may be NULL): initialized_, grad_norm_threshold_, current_potential_
  * (the window size), point_density_for_detector_ (lowered by the first call when the window would be below one pixel), and the
  * number of windows with a hit before the truncation */
