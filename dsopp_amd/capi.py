@@ -69,6 +69,11 @@ SYMBOLS = [
     "dsopp_hip_window_set_profiling", "dsopp_hip_window_get_profile", "dsopp_hip_kernel_class_name", "dsopp_hip_aligner_create", "dsopp_hip_aligner_destroy", "dsopp_hip_aligner_reset",
     "dsopp_hip_aligner_push_reference_depth_map", "dsopp_hip_aligner_push_reference_points", "dsopp_hip_aligner_push_target",
     "dsopp_hip_aligner_push_known_pose", "dsopp_hip_aligner_solve", "dsopp_hip_aligner_num_points",
+    "dsopp_hip_semantics_create", "dsopp_hip_semantics_destroy", "dsopp_hip_pyramid_set_semantics", "dsopp_hip_pyramid_get_semantics",
+    "dsopp_hip_pyramid_get_mask", "dsopp_hip_feature_extractor_set_mask_from_pyramid", "dsopp_hip_window_add_semantic_observations",
+    "dsopp_hip_window_get_semantic_observations", "dsopp_hip_window_get_semantic_types", "dsopp_hip_pyramid_group_set_semantics",
+    "dsopp_hip_window_group_add_semantic_observations", "dsopp_hip_window_group_get_semantic_observations",
+    "dsopp_hip_window_group_get_semantic_types",
 ]
 
 _lib = None
@@ -192,6 +197,39 @@ class Undistorter:
         _chk(lib().dsopp_hip_undistorter_undistort_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
 
 
+class Semantics:
+    """The per-camera constants of semantic segmentation (dsopp_hip_semantics): static_mask (height, width) uint8 or None = all 255,
+    is_filtered 256 bytes (non-zero = the class leaves the mask) or None = nothing is filtered, undistorter None = class images
+    arrive undistorted.  width and height must be divisible by 2^(levels - 1)."""
+
+    def __init__(self, width, height, levels, static_mask=None, is_filtered=None, undistorter: "Undistorter | None" = None, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.levels, self.device = int(width), int(height), int(levels), device
+        self._undistorter = undistorter  # borrowed by the handle: kept alive here
+        m = _u8(static_mask)
+        assert m is None or m.shape == (self.height, self.width), m.shape
+        f = _u8(is_filtered)
+        assert f is None or f.shape == (256,), f.shape
+        _chk(lib().dsopp_hip_semantics_create(int(device), C.c_void_p(stream or 0), self.width, self.height, self.levels, _p(m, np.uint8),
+                                              _p(f, np.uint8), undistorter._h if undistorter is not None else None, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_semantics_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def class_image_shape(self):
+        """(rows, cols) of the class image set_semantics takes: the undistorter's input, else the pyramid's size"""
+        u = self._undistorter
+        return (u.in_size[1], u.in_size[0]) if u is not None else (self.height, self.width)
+
+
 class Pyramid:
     """Device-resident image pyramid of one frame (dsopp_hip_pyramid)."""
 
@@ -236,6 +274,26 @@ class Pyramid:
 
     def set_mask(self, level, mask):
         _chk(lib().dsopp_hip_pyramid_set_mask(self._h, int(level), _p(_u8(mask), np.uint8)))
+
+    def set_semantics(self, semantics: "Semantics", class_image):
+        """the frame's class image (None = no semantic data) and the masks of all levels; only enqueues"""
+        c = _u8(class_image)
+        assert c is None or c.shape == semantics.class_image_shape(), c.shape
+        _chk(lib().dsopp_hip_pyramid_set_semantics(self._h, semantics._h, _p(c, np.uint8)))
+
+    def get_semantics(self):
+        """the undistorted class image the pyramid keeps, or None"""
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        present = C.c_int()
+        _chk(lib().dsopp_hip_pyramid_get_semantics(self._h, _p(out, np.uint8), C.byref(present)))
+        return out if present.value else None
+
+    def get_mask(self, level):
+        """the mask lane of a level's texels: 1 = valid, 0 = masked"""
+        w, h = self.level_size(level)
+        out = np.zeros((h, w), dtype=np.uint8)
+        _chk(lib().dsopp_hip_pyramid_get_mask(self._h, int(level), _p(out, np.uint8)))
+        return out
 
     def level_size(self, level):
         w, h = C.c_int(), C.c_int()
@@ -618,6 +676,25 @@ class HipWindow:
         _chk(lib().dsopp_hip_window_get_covariance(self._h, int(ref_id), int(tgt_id), _p(cov)))
         return cov
 
+    def add_semantic_observations(self, marginalized_frame_ids):
+        """addSemanticObservations for the listed frames against every frame that is neither listed nor flagged marginalised"""
+        ids = np.ascontiguousarray(marginalized_frame_ids, dtype=np.int32)
+        _chk(lib().dsopp_hip_window_add_semantic_observations(self._h, len(ids), ids.ctypes.data_as(C.c_void_p)))
+
+    def get_semantic_observations(self, frame_id):
+        """(n_landmarks, 256) uint8: semantic_type_observations_ of every landmark of the frame"""
+        hist = np.zeros((self.num_landmarks(frame_id), 256), dtype=np.uint8)
+        _chk(lib().dsopp_hip_window_get_semantic_observations(self._h, int(frame_id), _p(hist, np.uint8)))
+        return hist
+
+    def get_semantic_types(self, frame_id, weights=None):
+        """semanticTypeId of every landmark; weights = SemanticLegend::weights_ (256 integers) or None = no legend"""
+        t = np.zeros(self.num_landmarks(frame_id), dtype=np.uint8)
+        wt = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        assert wt is None or wt.shape == (256,), wt.shape
+        _chk(lib().dsopp_hip_window_get_semantic_types(self._h, int(frame_id), _p(wt, np.uint64), _p(t, np.uint8)))
+        return t
+
 
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_LOCAL, TRANSPORT_P2P = 0, 1, 2, 3
@@ -652,6 +729,12 @@ class PyramidGroup:
 
     def set_mask(self, level, mask):
         _chk(lib().dsopp_hip_pyramid_group_set_mask(self._h, int(level), _p(_u8(mask), np.uint8)))
+
+    def set_semantics(self, semantics: "Semantics", class_image):
+        """Pyramid.set_semantics on every pyramid of the group (all on the semantics object's device)"""
+        c = _u8(class_image)
+        assert c is None or c.shape == semantics.class_image_shape(), c.shape
+        _chk(lib().dsopp_hip_pyramid_group_set_semantics(self._h, semantics._h, _p(c, np.uint8)))
 
 
 class HipWindowGroup:
@@ -880,6 +963,25 @@ class HipWindowGroup:
         _chk(lib().dsopp_hip_window_group_get_covariance(self._h, int(ref_id), int(tgt_id), _p(cov)))
         return cov
 
+    def add_semantic_observations(self, marginalized_frame_ids):
+        """addSemanticObservations for the listed frames against every frame that is neither listed nor flagged marginalised"""
+        ids = np.ascontiguousarray(marginalized_frame_ids, dtype=np.int32)
+        _chk(lib().dsopp_hip_window_group_add_semantic_observations(self._h, len(ids), ids.ctypes.data_as(C.c_void_p)))
+
+    def get_semantic_observations(self, frame_id):
+        """(n_landmarks, 256) uint8: semantic_type_observations_ of every landmark of the frame"""
+        hist = np.zeros((self.num_landmarks(frame_id), 256), dtype=np.uint8)
+        _chk(lib().dsopp_hip_window_group_get_semantic_observations(self._h, int(frame_id), _p(hist, np.uint8)))
+        return hist
+
+    def get_semantic_types(self, frame_id, weights=None):
+        """semanticTypeId of every landmark; weights = SemanticLegend::weights_ (256 integers) or None = no legend"""
+        t = np.zeros(self.num_landmarks(frame_id), dtype=np.uint8)
+        wt = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        assert wt is None or wt.shape == (256,), wt.shape
+        _chk(lib().dsopp_hip_window_group_get_semantic_types(self._h, int(frame_id), _p(wt, np.uint64), _p(t, np.uint8)))
+        return t
+
     def create_reference_depth_maps(self, levels: int) -> DepthMaps:
         h = C.c_void_p()
         _chk(lib().dsopp_hip_window_group_create_reference_depth_maps(self._h, int(levels), C.byref(h)))
@@ -1029,6 +1131,12 @@ class FeatureExtractor:
         _chk(lib().dsopp_hip_feature_extractor_set_mask(self._h, _p(m, np.uint8)))
         self._mask = None if m is None else m.copy()
 
+    def set_mask_from_pyramid(self, pyramid: Pyramid):
+        """the level-0 mask `pyramid` kept from its last set_semantics, eroded on the device; only enqueues.  The extract() wrappers
+        compare their `mask` argument with the last set_mask: pass keep_mask=True to them after this call."""
+        _chk(lib().dsopp_hip_feature_extractor_set_mask_from_pyramid(self._h, pyramid._h))
+        self._mask = None
+
     def extract_raw(self, image, capacity):
         """one dsopp_hip_feature_extractor_extract call: (return code, xy (n, 2) or None, n)"""
         img = _u8(image)
@@ -1038,9 +1146,10 @@ class FeatureExtractor:
         rc = lib().dsopp_hip_feature_extractor_extract(self._h, _p(img, np.uint8), int(capacity), _p(xy), C.byref(n))
         return rc, (xy[:n.value].copy() if rc == 0 else None), n.value
 
-    def extract(self, image, mask=None):
-        """TrackingFeaturesExtractor::extract(image, mask) -> (n, 2) float64 (x, y); mask None = all pixels valid"""
-        if (mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask)):
+    def extract(self, image, mask=None, keep_mask=False):
+        """TrackingFeaturesExtractor::extract(image, mask) -> (n, 2) float64 (x, y); mask None = all pixels valid; keep_mask = the
+        extractor's mask stays what the last set_mask / set_mask_from_pyramid made it"""
+        if not keep_mask and ((mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask))):
             self.set_mask(mask)
         rc, xy, n = self.extract_raw(image, self._capacity)
         if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: the state is unchanged, run again with the room reported
@@ -1056,9 +1165,9 @@ class FeatureExtractor:
         rc = lib().dsopp_hip_feature_extractor_extract_from_pyramid(self._h, pyramid._h, int(capacity), _p(xy), C.byref(n))
         return rc, (xy[:n.value].copy() if rc == 0 else None), n.value
 
-    def extract_from_pyramid(self, pyramid: Pyramid, mask=None):
+    def extract_from_pyramid(self, pyramid: Pyramid, mask=None, keep_mask=False):
         """extract(image, mask) of the undistorted image `pyramid` kept from its last build_undistorted"""
-        if (mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask)):
+        if not keep_mask and ((mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask))):
             self.set_mask(mask)
         rc, xy, n = self.extract_from_pyramid_raw(pyramid, self._capacity)
         if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: the state is unchanged, run again with the room reported

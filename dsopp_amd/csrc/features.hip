@@ -338,6 +338,28 @@ int dsopp_hip_feature_extractor_set_mask(dsopp_hip_feature_extractor *ex, const 
   });
 }
 
+int dsopp_hip_feature_extractor_set_mask_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p) {
+  return guarded([&] {
+    if (!ex || !p) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->has_mask0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the pyramid keeps no level-0 mask: it never had dsopp_hip_pyramid_set_semantics");
+    if (p->width != ex->width || p->height != ex->height)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "pyramid is %d x %d, the extractor %d x %d", p->width, p->height, ex->width, ex->height);
+    if (p->sr.device != ex->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "extractor / pyramid live on another device");
+    ex->sr.use();
+    hipStream_t st = ex->sr.stream;
+    const int W = ex->width, H = ex->height;
+    const size_t n = static_cast<size_t>(W) * H;
+    ex->d_mask.reserve(n, 0, st);
+    ex->d_valid.reserve(n, 0, st);
+    p->waitReady(st);  // the masks are written in front of the event
+    // rows from the pyramid's bytes, columns from the row result: the eroded mask lands in d_valid without a copy of the input
+    erodeKernel<true><<<gridFor(static_cast<long>(n)), kBlock, 0, st>>>(p->mask0_u8.get(), W, H, ex->d_mask.ptr);
+    erodeKernel<false><<<gridFor(static_cast<long>(n)), kBlock, 0, st>>>(ex->d_mask.ptr, W, H, ex->d_valid.ptr);
+    HIP_CHECK(hipGetLastError());
+    ex->has_mask = true;
+  });
+}
+
 int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const uint8_t *image_host, int32_t capacity, double *xy, int32_t *n) {
   return guarded([&] {
     if (!ex || !image_host || !n || capacity < 0 || (capacity > 0 && !xy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");

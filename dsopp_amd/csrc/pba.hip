@@ -20,6 +20,7 @@
 #include "depth_maps.hpp"
 #include "activation_kernels.hpp"
 #include "immature_set.hpp"
+#include "semantic_observation_kernels.hpp"
 
 namespace dsopp_hip {
 namespace {
@@ -63,6 +64,9 @@ struct HostFrame {
   std::vector<int> batch_end;
   DeviceBuffer<int> d_to_internal;          // the caller -> device map on the device (export kernels un-permute there)
   bool permuted() const { return !to_internal.empty(); }
+  // class observations (dsopp_hip_window_add_semantic_observations): 256 counters per landmark, rows in the CALLER's order — no internal
+  // re-ordering moves them —, allocated by the first add that reaches this frame; rows past the landmarks counted so far are zero
+  DeviceBuffer<uint8_t> sem_hist;
   int internalOf(int caller) const { return to_internal.empty() ? caller : to_internal[static_cast<size_t>(caller)]; }
 };
 
@@ -191,6 +195,7 @@ struct dsopp_hip_window {
   // landmark arrays and 12 connection tables of 5 arrays each — about 70 hipMallocs (0.5 ms) when allocated afresh
   std::vector<std::unique_ptr<HostFrame>> frame_pool;
   std::vector<std::unique_ptr<ResidualTable>> table_pool;
+  DeviceBuffer<uint8_t> d_sem_args;  // job and partner tables of dsopp_hip_window_add_semantic_observations
   DeviceBuffer<double> dm_tmp;  // undilated reference depth maps, all levels (temporaries of createReferenceDepthMaps)
   std::vector<dsopp_hip_depth_maps *> live_maps;          // maps this window produced and that still borrow its stream
   struct ActivationScratch {            // work buffers of dsopp_hip_window_activate_landmarks
@@ -2349,6 +2354,7 @@ int dsopp_hip_window_push_frame(dsopp_hip_window *w, int32_t frame_id, int64_t t
       f->to_caller.clear();
       f->batch_end.clear();
       f->to_marginalize = false;
+      f->sem_hist.release();  // (the counters of the keyframe that left)
     } else {
       f = std::make_unique<HostFrame>();
     }
@@ -3076,6 +3082,140 @@ int dsopp_hip_window_get_residuals(dsopp_hip_window *w, int32_t reference_id, in
     if (status) rt.status.download(status, static_cast<size_t>(n), 0, st);
     if (candidate) rt.cand.download(candidate, static_cast<size_t>(n), 0, st);
     if (energy) rt.energy.download(energy, static_cast<size_t>(n), 0, st);
+    w->sr.sync();
+  });
+}
+
+namespace {
+/** the frame's counters hold a (zero) row for every landmark it has now */
+void ensureSemanticRows(W &w, HostFrame &f) {
+  f.sem_hist.reserve(static_cast<size_t>(f.n) * kSemClasses, f.sem_hist.capacity, w.sr.stream);
+}
+}  // namespace
+
+int dsopp_hip_window_add_semantic_observations(dsopp_hip_window *w, int32_t n, const int32_t *marginalized_frame_ids) {
+  return guarded([&] {
+    if (!w || n < 0 || (n && !marginalized_frame_ids)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    w->sr.use();
+    flushAppends(*w);
+    const int F = w->F();
+    std::vector<char> listed(static_cast<size_t>(F), 0);
+    for (int i = 0; i < n; ++i) {
+      const int s = w->slotOf(marginalized_frame_ids[i]);
+      if (s < 0) fail(DSOPP_HIP_ERR_NOT_FOUND, "frame %d is not in the window", marginalized_frame_ids[i]);
+      listed[static_cast<size_t>(s)] = 1;
+    }
+    downloadState(*w);
+    hipStream_t st = w->sr.stream;
+    std::vector<SemJob> jobs;
+    std::vector<SemPartner> partners;
+    int blocks = 0;
+    for (int r = 0; r < F; ++r) {
+      HostFrame &fr = *w->frames[static_cast<size_t>(r)];
+      if (!listed[static_cast<size_t>(r)] && fr.is_marginalized) continue;  // a frame marginalised earlier takes no part (:298-300)
+      const int first = static_cast<int>(partners.size());
+      for (int t = 0; t < F; ++t) {
+        // a listed frame pairs with every frame that is neither listed nor flagged, such a frame with every listed one
+        HostFrame &ft = *w->frames[static_cast<size_t>(t)];
+        if (t == r || listed[static_cast<size_t>(t)] == listed[static_cast<size_t>(r)]) continue;
+        if (!listed[static_cast<size_t>(t)] && ft.is_marginalized) continue;
+        if (!ft.pyramid->has_semantics) continue;  // semanticsData(0) == nullptr (:268-269)
+        auto it = fr.residuals.find(ft.id);
+        if (it == fr.residuals.end() || it->second->n <= 0) continue;
+        if (fr.level != 0 || ft.level != 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "class observations need frames pushed with level 0");
+        const Rigid T = rigidMul(rigidInverse(poseOf(*w, t)), poseOf(*w, r));
+        SemPartner pt{};
+        const double ifx = 1.0 / fr.intr[0], ify = 1.0 / fr.intr[1], k02 = -fr.intr[2] / fr.intr[0], k12 = -fr.intr[3] / fr.intr[1];
+        double U[12];
+        for (int i = 0; i < 3; ++i) {  // ArrayReprojector ctor (camera_reproject.hpp:244-258), as buildProjectionMatrices
+          U[4 * i + 0] = T.R[3 * i + 0] * ifx;
+          U[4 * i + 1] = T.R[3 * i + 1] * ify;
+          U[4 * i + 2] = T.R[3 * i + 0] * k02 + T.R[3 * i + 1] * k12 + T.R[3 * i + 2];
+          U[4 * i + 3] = T.t[i];
+        }
+        for (int c = 0; c < 4; ++c) {
+          pt.M[0 + c] = ft.intr[0] * U[0 + c] + ft.intr[2] * U[8 + c];
+          pt.M[4 + c] = ft.intr[1] * U[4 + c] + ft.intr[3] * U[8 + c];
+          pt.M[8 + c] = U[8 + c];
+        }
+        pt.status = hbm(it->second->status.ptr);
+        pt.n_res = it->second->n;
+        pt.cls = hbm(ft.pyramid->semantics_u8.get());
+        pt.width = ft.pyramid->width;
+        pt.height = ft.pyramid->height;
+        ft.pyramid->waitReady(st);  // the class image is written on the pyramid's stream
+        partners.push_back(pt);
+      }
+      const int count = static_cast<int>(partners.size()) - first;
+      if (!count || fr.n <= 0) {
+        partners.resize(static_cast<size_t>(first));
+        continue;
+      }
+      ensureSemanticRows(*w, fr);
+      SemJob job{};
+      job.uv = hbm(fr.uv.ptr);
+      job.idepth = hbm(fr.idepth.ptr);
+      job.to_internal = fr.permuted() ? hbm(fr.d_to_internal.ptr) : nullptr;
+      job.hist = hbm(fr.sem_hist.ptr);
+      job.n = fr.n;
+      job.first_block = blocks;
+      job.first_partner = first;
+      job.n_partners = count;
+      job.width = fr.pyramid->width;
+      job.height = fr.pyramid->height;
+      blocks += (fr.n + kSemBlock - 1) / kSemBlock;
+      jobs.push_back(job);
+    }
+    if (jobs.empty()) return;
+    const size_t job_bytes = (jobs.size() * sizeof(SemJob) + 15) & ~static_cast<size_t>(15), partner_bytes = partners.size() * sizeof(SemPartner);
+    w->d_sem_args.reserve(job_bytes + partner_bytes, 0, st);
+    uint8_t *h = static_cast<uint8_t *>(stageAcquire(*w, job_bytes + partner_bytes));
+    std::memcpy(h, jobs.data(), jobs.size() * sizeof(SemJob));
+    std::memcpy(h + job_bytes, partners.data(), partner_bytes);
+    HIP_CHECK(hipMemcpyAsync(w->d_sem_args.ptr, h, job_bytes + partner_bytes, hipMemcpyHostToDevice, st));
+    semanticObservationsKernel<<<static_cast<unsigned>(blocks), kSemBlock, 0, st>>>(reinterpret_cast<const SemJob *>(w->d_sem_args.ptr), static_cast<int>(jobs.size()),
+                                                                                 reinterpret_cast<const SemPartner *>(w->d_sem_args.ptr + job_bytes));
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int dsopp_hip_window_get_semantic_observations(dsopp_hip_window *w, int32_t frame_id, uint8_t *hist) {
+  return guarded([&] {
+    if (!w || !hist) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    w->sr.use();
+    HostFrame &f = w->frameById(frame_id);
+    const size_t bytes = static_cast<size_t>(f.n) * kSemClasses;
+    if (!bytes) return;
+    if (!f.sem_hist.ptr) {  // no add has reached this frame
+      std::memset(hist, 0, bytes);
+      return;
+    }
+    ensureSemanticRows(*w, f);
+    f.sem_hist.download(hist, bytes, 0, w->sr.stream);
+    w->sr.sync();
+  });
+}
+
+int dsopp_hip_window_get_semantic_types(dsopp_hip_window *w, int32_t frame_id, const uint64_t *weights256, uint8_t *type) {
+  return guarded([&] {
+    if (!w || !type) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    w->sr.use();
+    HostFrame &f = w->frameById(frame_id);
+    if (f.n <= 0) return;
+    if (!f.sem_hist.ptr) {  // all counts zero: max_element is element 0, every product is 0
+      std::memset(type, 0, static_cast<size_t>(f.n));
+      return;
+    }
+    hipStream_t st = w->sr.stream;
+    ensureSemanticRows(*w, f);
+    DeviceMem<uint8_t> tmp;  // [weights 2048 bytes | types n]
+    tmp.alloc(kSemClasses * sizeof(uint64_t) + static_cast<size_t>(f.n));
+    if (weights256) HIP_CHECK(hipMemcpyAsync(tmp.get(), weights256, kSemClasses * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    uint8_t *type_dev = tmp.get() + kSemClasses * sizeof(uint64_t);
+    semanticTypesKernel<<<static_cast<unsigned>((f.n + kSemBlock - 1) / kSemBlock), kSemBlock, 0, st>>>(
+        f.sem_hist.ptr, f.n, weights256 ? reinterpret_cast<const unsigned long long *>(tmp.get()) : nullptr, type_dev);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(type, type_dev, static_cast<size_t>(f.n), hipMemcpyDeviceToHost, st));
     w->sr.sync();
   });
 }

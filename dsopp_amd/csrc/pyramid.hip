@@ -434,7 +434,9 @@ int dsopp_hip_pyramid_build_device(dsopp_hip_pyramid *p, const void *image_dev, 
   });
 }
 
-namespace {
+}  // extern "C"
+
+namespace dsopp_hip {
 /** the caller's image into this pyramid's pinned buffer with non-temporal stores: the destination is read next by the DMA engine, not by
  *  the host, so the copy neither reads the old lines of the buffer first (write-allocate) nor leaves 1.3 MB of them in the caches —
  *  memcpy() takes 67 us for a 1280 x 1024 image on the tracker's per-frame path */
@@ -457,7 +459,11 @@ void copyToPinned(uint8_t *dst, const uint8_t *src, size_t n) {
 #endif
   std::memcpy(dst, src, n);
 }
+}  // namespace dsopp_hip
 
+extern "C" {
+
+namespace {
 /** the caller's 8-bit image of n bytes through the pyramid's pinned buffer into dst_dev, enqueued on the pyramid's stream */
 void uploadImage(dsopp_hip_pyramid *p, uint8_t *dst_dev, const uint8_t *image_host, size_t n) {
   HIP_CHECK(hipStreamSynchronize(p->sr.stream));  // (free when the stream is idle — the usual case; guards a rebuild while the last upload is in flight)

@@ -75,6 +75,9 @@ __device__ __forceinline__ Texel<S> loadTexel(const Texel<S> *p) {  // a generic
 }
 #endif
 
+/** `n` bytes of a caller's image into pinned memory with non-temporal stores (pyramid.hip) */
+void copyToPinned(uint8_t *dst, const uint8_t *src, size_t n);
+
 struct LevelView {
   const void *texels;  // Texel<S>*
   int width, height;
@@ -97,6 +100,15 @@ struct dsopp_hip_pyramid {
   dsopp_hip::DeviceMem<uint8_t> distorted_u8, undistorted_u8;
   size_t distorted_bytes = 0;
   bool has_undistorted = false;
+  // dsopp_hip_pyramid_set_semantics (semantics.hip): the frame's class image as uploaded (only with an undistorter; sized by the first
+  // call) and undistorted (semanticsData of the frame: the window's class observations read it), and the level-0 mask as bytes
+  // (dsopp_hip_feature_extractor_set_mask_from_pyramid erodes it).  All read behind waitReady().  The class image leaves from a pinned
+  // buffer of its own, so that a set_semantics behind a build need not wait for the build's upload; semantics_uploaded guards its reuse.
+  dsopp_hip::DeviceMem<uint8_t> semantics_in_u8, semantics_u8, mask0_u8;
+  size_t semantics_in_bytes = 0;
+  bool has_semantics = false, has_mask0 = false;
+  dsopp_hip::PinnedMem<uint8_t> h_semantics;
+  dsopp_hip::Event semantics_uploaded;
   // Recorded on the pyramid's stream behind every write of the texels (build / build_device / set_level / set_mask).  A
   // consumer that reads the texels on another stream orders itself behind it with waitReady(): build_device only ENQUEUES
   // work, so without this a solve on the aligner's or the window's own stream could sample a half-built image.

@@ -727,6 +727,10 @@ int dsopp_hip_pyramid_group_set_level(dsopp_hip_pyramid_group *pg, int level, co
 int dsopp_hip_pyramid_group_set_mask(dsopp_hip_pyramid_group *pg, int level, const uint8_t *mask_host) {
   DSOPP_PYRAMID_GROUP_FORALL(dsopp_hip_pyramid_set_mask(p, level, mask_host));
 }
+int dsopp_hip_pyramid_group_set_semantics(dsopp_hip_pyramid_group *pg, const dsopp_hip_semantics *s, const uint8_t *class_image_host) {
+  // the class image is replicated with the pyramid: every pyramid undistorts it and writes its own masks
+  DSOPP_PYRAMID_GROUP_FORALL(dsopp_hip_pyramid_set_semantics(p, s, class_image_host));
+}
 int dsopp_hip_pyramid_group_get(dsopp_hip_pyramid_group *pg, int32_t shard, dsopp_hip_pyramid **pyramid) {
   return guarded([&] {
     if (!pg || !pyramid) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
@@ -962,6 +966,47 @@ int dsopp_hip_window_group_get_landmarks(dsopp_hip_window_group *g, int32_t fram
         if (flags_out) flags_out[j] = sc.u8[k];
         if (hpib) std::memcpy(hpib + j * K, sc.h.data() + k * K, K * sizeof(double));
       }
+      return static_cast<int>(DSOPP_HIP_OK);
+    });
+  });
+}
+
+// ---- class observations: every shard counts for its own landmarks (poses and class images are replicated) -----------------------------
+
+int dsopp_hip_window_group_add_semantic_observations(dsopp_hip_window_group *g, int32_t n, const int32_t *marginalized_frame_ids) {
+  DSOPP_GROUP_REPLICATED(dsopp_hip_window_add_semantic_observations(w, n, marginalized_frame_ids));
+}
+
+int dsopp_hip_window_group_get_semantic_observations(dsopp_hip_window_group *g, int32_t frame_id, uint8_t *hist) {
+  return guarded([&] {
+    checkGroup(g);
+    if (!hist) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    const int S = g->n;
+    fanOut(*g, [&](int s, dsopp_hip_window *w) {
+      int32_t ns = 0;
+      if (const int rc = dsopp_hip_window_num_landmarks(w, frame_id, &ns); rc != DSOPP_HIP_OK) return rc;
+      G::Scratch &sc = g->scratch[static_cast<size_t>(s)];
+      sc.u8.resize(std::max<size_t>(1, static_cast<size_t>(ns) * 256));
+      if (const int rc = dsopp_hip_window_get_semantic_observations(w, frame_id, sc.u8.data()); rc != DSOPP_HIP_OK) return rc;
+      for (size_t k = 0; k < static_cast<size_t>(ns); ++k)
+        std::memcpy(hist + (k * static_cast<size_t>(S) + static_cast<size_t>(s)) * 256, sc.u8.data() + k * 256, 256);
+      return static_cast<int>(DSOPP_HIP_OK);
+    });
+  });
+}
+
+int dsopp_hip_window_group_get_semantic_types(dsopp_hip_window_group *g, int32_t frame_id, const uint64_t *weights256, uint8_t *type) {
+  return guarded([&] {
+    checkGroup(g);
+    if (!type) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    const int S = g->n;
+    fanOut(*g, [&](int s, dsopp_hip_window *w) {
+      int32_t ns = 0;
+      if (const int rc = dsopp_hip_window_num_landmarks(w, frame_id, &ns); rc != DSOPP_HIP_OK) return rc;
+      G::Scratch &sc = g->scratch[static_cast<size_t>(s)];
+      sc.u8.resize(std::max<size_t>(1, static_cast<size_t>(ns)));
+      if (const int rc = dsopp_hip_window_get_semantic_types(w, frame_id, weights256, sc.u8.data()); rc != DSOPP_HIP_OK) return rc;
+      for (size_t k = 0; k < static_cast<size_t>(ns); ++k) type[k * static_cast<size_t>(S) + static_cast<size_t>(s)] = sc.u8[k];
       return static_cast<int>(DSOPP_HIP_OK);
     });
   });

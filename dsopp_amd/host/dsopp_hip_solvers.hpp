@@ -80,6 +80,25 @@ class HipUndistorter {
   int out_width_, out_height_;
 };
 
+/** The per-camera constants of the `segmentation:` block (camera_fabric.cpp:54-99,170-186) on the device: the static mask as the camera
+ *  keeps it (already undistorted, camera_fabric.cpp:164; nullptr = all valid), SemanticFilter::is_filtered_ (256 bytes; nullptr =
+ *  filterBySemantic() is false) and the undistorter the class images go through (nullptr = they arrive undistorted; it must outlive
+ *  this object).  width and height must be divisible by 2^(levels - 1). */
+class HipSemantics {
+ public:
+  HipSemantics(int width, int height, int levels, const uint8_t *static_mask, const uint8_t *is_filtered256, const HipUndistorter *undistorter = nullptr,
+               int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_semantics_create(device, stream, width, height, levels, static_mask, is_filtered256, undistorter ? undistorter->handle() : nullptr, &s_));
+  }
+  ~HipSemantics() { dsopp_hip_semantics_destroy(s_); }
+  HipSemantics(const HipSemantics &) = delete;
+  HipSemantics &operator=(const HipSemantics &) = delete;
+  const dsopp_hip_semantics *handle() const { return s_; }
+
+ private:
+  dsopp_hip_semantics *s_ = nullptr;
+};
+
 /** device-resident pyramid of one frame = features::PixelDataFrame / ActiveKeyframe::pyramids() + masks */
 class DevicePyramid {
  public:
@@ -102,6 +121,19 @@ class DevicePyramid {
   /** adopt a PixelMap<1> level built on the host by the reference */
   void setLevel(int level, const double *pixelinfo) { check(dsopp_hip_pyramid_set_level(p_, level, pixelinfo)); }
   void setMask(int level, const uint8_t *mask) { check(dsopp_hip_pyramid_set_mask(p_, level, mask)); }
+  /** the frame's semantics: the class image as the provider delivers it (nullptr = none for this frame) is undistorted and kept
+   *  (camera.cpp:57-65), filtered classes leave the camera mask (camera_mask.cpp:31-39) and the masks of all levels are written
+   *  (camera_features.cpp:71-84); only enqueues, in either order with build* */
+  void setSemantics(const HipSemantics &semantics, const uint8_t *class_image) {
+    check(dsopp_hip_pyramid_set_semantics(p_, semantics.handle(), class_image));
+  }
+  /** semanticsData(0) of the frame: false when it has none */
+  bool semantics(std::vector<uint8_t> &class_image, int width, int height) const {
+    int present = 0;
+    class_image.resize(static_cast<size_t>(width) * static_cast<size_t>(height));
+    check(dsopp_hip_pyramid_get_semantics(p_, class_image.data(), &present));
+    return present != 0;
+  }
   dsopp_hip_pyramid *handle() const { return p_; }
 
  private:
@@ -123,6 +155,10 @@ class DevicePyramidGroup {
   }
   void setLevel(int level, const double *pixelinfo) { check(dsopp_hip_pyramid_group_set_level(p_, level, pixelinfo)); }
   void setMask(int level, const uint8_t *mask) { check(dsopp_hip_pyramid_group_set_mask(p_, level, mask)); }
+  /** DevicePyramid::setSemantics on every device's copy (all on the semantics object's device) */
+  void setSemantics(const HipSemantics &semantics, const uint8_t *class_image) {
+    check(dsopp_hip_pyramid_group_set_semantics(p_, semantics.handle(), class_image));
+  }
   dsopp_hip_pyramid_group *handle() const { return p_; }
 
  private:
@@ -400,6 +436,29 @@ class HipPhotometricBundleAdjustment {
     check(dsopp_hip_window_group_get_pose(g_, it->second, nullptr, ab.data()));
     return ab;
   }
+  /** addSemanticObservations(track, marginalized_keyframes_ids, model) — monocular_tracker.cpp:263-305, called at :506 with the
+   *  keyframes the marginalisation just chose, after updateLocalFrame has flagged them: the class codes under every reprojected pattern
+   *  are counted on the device, from the class images the frames' pyramids keep */
+  void addSemanticObservations(const std::vector<int32_t> &marginalized_keyframe_ids) {
+    check(dsopp_hip_window_group_add_semantic_observations(g_, static_cast<int32_t>(marginalized_keyframe_ids.size()), marginalized_keyframe_ids.data()));
+  }
+  /** semantic_type_observations_ of every landmark of a keyframe (256 counters each), before the keyframe leaves the solver */
+  std::vector<uint8_t> semanticObservations(int32_t keyframe_id) {
+    int32_t n = 0;
+    check(dsopp_hip_window_group_num_landmarks(g_, keyframe_id, &n));
+    std::vector<uint8_t> hist(static_cast<size_t>(n) * 256);
+    if (n) check(dsopp_hip_window_group_get_semantic_observations(g_, keyframe_id, hist.data()));
+    return hist;
+  }
+  /** ActiveTrackingLandmark::semanticTypeId(legend) of every landmark of a keyframe; legend_weights256 = SemanticLegend::weights_,
+   *  nullptr = no legend */
+  std::vector<uint8_t> semanticTypes(int32_t keyframe_id, const uint64_t *legend_weights256 = nullptr) {
+    int32_t n = 0;
+    check(dsopp_hip_window_group_num_landmarks(g_, keyframe_id, &n));
+    std::vector<uint8_t> type(static_cast<size_t>(n));
+    if (n) check(dsopp_hip_window_group_get_semantic_types(g_, keyframe_id, legend_weights256, type.data()));
+    return type;
+  }
   /** the one device window of a single-device solver (nullptr for a multi-device one): what the device-resident landmark
    *  activation reads, which needs ALL active landmarks of the window on one device */
   dsopp_hip_window *handle() const { return w_; }
@@ -570,8 +629,9 @@ class HipTrackingFeaturesExtractor {
   ~HipTrackingFeaturesExtractor() { dsopp_hip_feature_extractor_destroy(ex_); }
   HipTrackingFeaturesExtractor(const HipTrackingFeaturesExtractor &) = delete;
   HipTrackingFeaturesExtractor &operator=(const HipTrackingFeaturesExtractor &) = delete;
-  /** image: W x H 8-bit grey (CameraFeatures::frame_data_); mask: the camera's level-0 CameraMask bytes, nullptr = all valid.  The mask
-   *  is a per-camera constant (CameraFeatures::pyramidOfMasks()[0]): it is eroded again only when a different array is passed. */
+  /** image: W x H 8-bit grey (CameraFeatures::frame_data_); mask: the camera's level-0 CameraMask bytes, nullptr = all valid.  Without
+   *  semantic filtering the mask is a per-camera constant (CameraFeatures::pyramidOfMasks()[0]): it is eroded again only when a
+   *  different array is passed.  With it the mask is the frame's: setMaskFromPyramid. */
   std::vector<Feature> extract(const uint8_t *image, const uint8_t *mask) {
     return run(mask, [&](int32_t capacity, int32_t *n) { return dsopp_hip_feature_extractor_extract(ex_, image, capacity, xy_.data(), n); });
   }
@@ -581,6 +641,15 @@ class HipTrackingFeaturesExtractor {
       return dsopp_hip_feature_extractor_extract_from_pyramid(ex_, pyramid.handle(), capacity, xy_.data(), n);
     });
   }
+  /** the frame's level-0 mask, which `pyramid` kept from its last setSemantics, eroded on the device with no host copy; it stays the
+   *  extractor's mask for the extractFromPyramid(pyramid) that follows and until another mask is passed */
+  void setMaskFromPyramid(const DevicePyramid &pyramid) {
+    check(dsopp_hip_feature_extractor_set_mask_from_pyramid(ex_, pyramid.handle()));
+    mask_ = &from_pyramid_;
+    mask_set_ = true;
+  }
+  /** extractFromPyramid with the mask the extractor holds (the last setMaskFromPyramid or extract) */
+  std::vector<Feature> extractFromPyramid(const DevicePyramid &pyramid) { return extractFromPyramid(pyramid, mask_set_ ? mask_ : nullptr); }
   const dsopp_hip_feature_extractor *handle() const { return ex_; }
 
  protected:
@@ -609,6 +678,7 @@ class HipTrackingFeaturesExtractor {
   }
   const uint8_t *mask_ = nullptr;
   bool mask_set_ = false;
+  uint8_t from_pyramid_ = 0;  // its address stands for "the mask came from a pyramid" in mask_
   std::vector<double> xy_ = std::vector<double>(2 * 4096);
 };
 

@@ -150,6 +150,42 @@ int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_un
                                         const uint8_t *vignetting_host);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
+ * image — src/sensors/camera/src/camera.cpp:57-65 —, CameraMask::filterSemanticObjects —
+ * src/sensors/camera_calibration/src/camera_mask.cpp:31-39 — and the mask pyramid of src/features/src/camera_features.cpp:71-84; the
+ * `segmentation:` block that configures them is read by src/sensors/sensors_builder/src/camera_fabric.cpp:54-99,170-186)
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_semantics dsopp_hip_semantics;
+/* The per-camera constants.  static_mask_host: the camera's W x H mask bytes, already undistorted as camera_fabric.cpp:164 keeps them
+ * (NULL = all 255).  is_filtered256: SemanticFilter::is_filtered_ (src/common/semantics/src/semantic_filter.cpp:5-14), one byte per class
+ * code, non-zero = pixels of that class leave the mask (NULL = filterBySemantic() is false: nothing is filtered).  undistorter: the
+ * remap every class image goes through (NULL = class images arrive undistorted, W x H); it is BORROWED and must outlive this object,
+ * live on `device` and write width x height.  levels in 1 .. DSOPP_HIP_MAX_LEVELS, and width and height must be divisible by
+ * 2^(levels - 1) — for other sizes the reference's own mask sizes (cvRound of the scaled size) differ from its image level sizes —
+ * else DSOPP_HIP_ERR_INVALID_ARGUMENT.  Both host arrays are copied before the call returns. */
+int dsopp_hip_semantics_create(int device, void *stream, int width, int height, int levels, const uint8_t *static_mask_host,
+                               const uint8_t *is_filtered256, const dsopp_hip_undistorter *undistorter, dsopp_hip_semantics **out);
+void dsopp_hip_semantics_destroy(dsopp_hip_semantics *s);
+/* The frame's class image and the masks of all its levels.  class_image_host: the distorted in_h x in_w class codes (W x H without an
+ * undistorter); it goes through a pinned buffer of the pyramid, is remapped on the pyramid's stream by the undistorter's kernel (the
+ * reference runs the same cv::remap(INTER_LINEAR) over class codes, camera.cpp:57-65: the integer arithmetic stated at
+ * dsopp_hip_undistorter_create applies unchanged) and is kept by the pyramid as the frame's semanticsData.  NULL = the frame has no
+ * semantic data.  Then ONE launch writes the mask lane of every level and the level-0 mask bytes, in exact integer arithmetic:
+ *   m0[y, x]  = is_filtered[c[y, x]] ? 0 : static[y, x]        (camera_mask.cpp:31-39; without a filter or a class image m0 = static,
+ *                                                                the copy of pyramid_of_static_masks_, camera_features.cpp:73)
+ *   m_l[y, x] = (m0[cy, cx] + m0[cy, cx + 1] + m0[cy + 1, cx] + m0[cy + 1, cx + 1] + 2) >> 2,  cx = 2^l x + 2^(l-1) - 1, cy alike
+ * — every level from level 0 directly, which is CameraMask::resize(1 / 2^l) = cv::resize(INTER_LINEAR) at these ratios
+ * (camera_features.cpp:76-82) — and a texel is valid iff m_l != 0.  The build kernels keep the mask lane, so build* and set_semantics
+ * work in either order.  The call only enqueues on the pyramid's stream and records the pyramid's ready event; it does not wait.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: another device, another size, or more levels than the semantics object was created for. */
+int dsopp_hip_pyramid_set_semantics(dsopp_hip_pyramid *p, const dsopp_hip_semantics *s, const uint8_t *class_image_host);
+/* the undistorted class image the pyramid keeps (W x H bytes; out_host may be NULL); *present = 0 when the last set_semantics had
+ * no class image or there was none: out_host is then left alone */
+int dsopp_hip_pyramid_get_semantics(dsopp_hip_pyramid *p, uint8_t *out_host, int *present);
+/* the mask lane of a level's texels as bytes: 1 = valid, 0 = masked (CameraMask::valid) */
+int dsopp_hip_pyramid_get_mask(dsopp_hip_pyramid *p, int level, uint8_t *out_host);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Sliding-window photometric bundle adjustment
  * (replaces EigenPhotometricBundleAdjustment<SE3, PinholeCamera, 8, PixelMap, true, true, true, 1>)
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -226,6 +262,35 @@ int dsopp_hip_window_get_residuals(dsopp_hip_window *w, int32_t reference_id, in
                                    uint8_t *candidate, double *energy);
 int dsopp_hip_window_get_marginalized(dsopp_hip_window *w, double *H, double *b, double *energy, int32_t *size);
 int dsopp_hip_window_get_covariance(dsopp_hip_window *w, int32_t reference_id, int32_t target_id, double cov[36]);
+
+/* ---- class observations of the landmarks (semantic segmentation) ----
+ * addSemanticObservations(track, marginalized_keyframes_ids, model) — src/tracker/tracker/src/monocular_tracker.cpp:263-305, called at
+ * :506 for the keyframes the marginalisation strategy just chose — on the window's own state.  For every listed frame M and every
+ * frame X of the window that is neither flagged marginalised nor listed (:298-300), both directions (reference M, target X) and
+ * (reference X, target M): for every landmark i of the reference whose connection status towards the target is kOk, the 8 pattern
+ * points are reprojected by the checked pinhole reprojector (validIdepth, reference and target insideCameraROI, z > 0 —
+ * src/energy/projector/include/energy/projector/camera_reproject.hpp:270-293) with the intrinsics the frames were pushed with (level 0,
+ * else DSOPP_HIP_ERR_INVALID_ARGUMENT), T_target^-1 * T_reference of the current estimates (dsopp_hip_window_get_pose) and the
+ * landmark's current inverse depth; on success hist[i][class_target[int(v_k), int(u_k)]] is incremented for the 8 points.  class_target
+ * is the class image the target's pyramid keeps (dsopp_hip_pyramid_set_semantics); a target without one is skipped (:268-269).  The
+ * counters are bytes and wrap modulo 256, as the reference's std::array<uint8_t, 256> does.  A landmark's 256 counters are written by
+ * the one work item that owns the landmark, which walks the partner frames itself: no atomics, bit-exact, independent of any order.
+ * One deviation: the reference reads the KEYFRAME's inverse depth, which for a landmark whose solved inverse depth went negative still
+ * holds the previous value (updateFrame marks it outlier instead of copying); the window uses its own value.  Such landmarks are
+ * outliers and are never exported.
+ * The counters live with the frame while it is in the window (read them before the push_frame that folds the frame out), follow their
+ * landmarks through every internal re-ordering and through appends (new landmarks start at zero), and are allocated by the first add:
+ * a window that never uses semantics pays nothing.  dsopp_hip_window_snapshot / _restore leave them alone. */
+int dsopp_hip_window_add_semantic_observations(dsopp_hip_window *w, int32_t n, const int32_t *marginalized_frame_ids);
+/* semantic_type_observations_ of every landmark of a frame: n_landmarks x 256 bytes in the caller's landmark order (all zero
+ * before the first add) */
+int dsopp_hip_window_get_semantic_observations(dsopp_hip_window *w, int32_t frame_id, uint8_t *hist);
+/* ActiveTrackingLandmark::semanticTypeId(legend) (src/track/landmarks/src/active_tracking_landmark.cpp:71-88) for every landmark
+ * of a frame, on the device: weights256 = SemanticLegend::weights_ as 256 uint64 (std::array<size_t, 256> weights_ = {1}: only code 0 has a default weight,
+ * every other code the legend does not list weighs 0), NULL = no legend.
+ * Without weights the first maximal count; with weights the first i with the strictly largest count[i] * weight[i], the first
+ * maximal count when every product is 0.  type: n_landmarks bytes. */
+int dsopp_hip_window_get_semantic_types(dsopp_hip_window *w, int32_t frame_id, const uint64_t *weights256, uint8_t *type);
 
 /* multi-GPU: landmarks are sharded across ranks by the caller (each rank uploads only its shard; frames and images are
  * replicated).  The library calls `allreduce_sum` on its stream whenever partial sums over landmarks must be combined
@@ -341,6 +406,14 @@ int dsopp_hip_window_group_get_residuals(dsopp_hip_window_group *g, int32_t refe
                                          uint8_t *candidate, double *energy);
 int dsopp_hip_window_group_get_marginalized(dsopp_hip_window_group *g, double *H, double *b, double *energy, int32_t *size);
 int dsopp_hip_window_group_get_covariance(dsopp_hip_window_group *g, int32_t reference_id, int32_t target_id, double cov[36]);
+/* the class observations, as the dsopp_hip_window_ calls of the same name: every shard counts for its own landmarks, the getters
+ * interleave.  The class image is replicated with the pyramid: dsopp_hip_pyramid_group_set_semantics runs
+ * dsopp_hip_pyramid_set_semantics on every pyramid of the group, which must all live on the semantics object's device (a group over
+ * several devices sets each device's pyramid — dsopp_hip_pyramid_group_get — with that device's own object). */
+int dsopp_hip_pyramid_group_set_semantics(dsopp_hip_pyramid_group *pg, const dsopp_hip_semantics *s, const uint8_t *class_image_host);
+int dsopp_hip_window_group_add_semantic_observations(dsopp_hip_window_group *g, int32_t n, const int32_t *marginalized_frame_ids);
+int dsopp_hip_window_group_get_semantic_observations(dsopp_hip_window_group *g, int32_t frame_id, uint8_t *hist);
+int dsopp_hip_window_group_get_semantic_types(dsopp_hip_window_group *g, int32_t frame_id, const uint64_t *weights256, uint8_t *type);
 /* createReferenceDepthMaps over all shards: the level-0 splat planes are summed across the shards, the maps returned live on
  * device_ids[0] (where the tracker's aligner runs); refill needs maps this group created */
 int dsopp_hip_window_group_create_reference_depth_maps(dsopp_hip_window_group *g, int32_t levels, dsopp_hip_depth_maps **out);
@@ -388,7 +461,8 @@ int dsopp_hip_window_optimize_repeated(dsopp_hip_window *w, int32_t iterations_t
 
 /* device-side snapshot / restore of the mutable solver state (poses, affine, idepths, flags, connection statuses);
  * device-to-device copies only.  Lets a caller re-run a solve from the same starting point (benchmark loops, the
- * tracker's re-tracking tries) without re-uploading the window. */
+ * tracker's re-tracking tries) without re-uploading the window.  The class observations of
+ * dsopp_hip_window_add_semantic_observations are not part of it: neither call touches them. */
 int dsopp_hip_window_snapshot(dsopp_hip_window *w);
 int dsopp_hip_window_restore(dsopp_hip_window *w);
 
@@ -539,6 +613,11 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
  * the extractor's. */
 int dsopp_hip_feature_extractor_extract_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p, int32_t capacity, double *xy,
                                                      int32_t *n);
+/* The extractor's mask from the level-0 mask bytes that `p` kept from its last dsopp_hip_pyramid_set_semantics (the per-frame camera
+ * mask the reference hands to extract(), camera_features.cpp:36-41,71-74): eroded on the device for both kinds of extractor, behind
+ * the pyramid's ready event, with no host copy; the call only enqueues.  DSOPP_HIP_ERR_INVALID_ARGUMENT when the pyramid never had
+ * set_semantics, or its size or device is not the extractor's. */
+int dsopp_hip_feature_extractor_set_mask_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p);
 /* the extractor's state after the last extract (any pointer may be NULL): initialized_, grad_norm_threshold_, current_potential_
  * (the window size), point_density_for_detector_ (lowered by the first call when the window would be below one pixel), and the
  * number of windows with a hit before the truncation */
