@@ -256,17 +256,21 @@ __device__ __forceinline__ void alignDecide(AlignControl &c, const double *tot, 
   }
 }
 
-/** sample the reference intensities of the points: PatternPatch::getIntensities with PatternSize 1 (local_frame.hpp:384-388) */
+/** sample the reference intensities of the points: PatternPatch::getIntensities with PatternSize 1 (local_frame.hpp:384-388).  A point
+ *  outside the reference camera's ROI (a caller's explicit point; the depth-map scans only produce inside ones) gets intensity 0 and
+ *  reads no texel of its own: referenceSampleSite */
 template <typename S>
-__global__ void sampleReferenceKernel(const Texel<S> *__restrict__ img, int W, const double *__restrict__ u, const double *__restrict__ v,
+__global__ void sampleReferenceKernel(const Texel<S> *__restrict__ img, int W, int H, const double *__restrict__ u, const double *__restrict__ v,
                                       double *__restrict__ intensity, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const S x = static_cast<S>(u[i]), y = static_cast<S>(v[i]);
-  const int ix = static_cast<int>(x), iy = static_cast<int>(y);
-  const S dx = x - static_cast<S>(ix), dy = y - static_cast<S>(iy), dxdy = dx * dy;
+  int ix, iy;
+  S dx, dy;
+  const bool inside = referenceSampleSite(static_cast<S>(u[i]), static_cast<S>(v[i]), W, H, ix, iy, dx, dy);
+  const S dxdy = dx * dy;
   const Texel<S> *p = img + static_cast<size_t>(iy) * W + ix;
-  intensity[i] = static_cast<double>(dxdy * p[W + 1].I + (dy - dxdy) * p[W].I + (dx - dxdy) * p[1].I + (S(1) - dx - dy + dxdy) * p[0].I);
+  const S s = dxdy * p[W + 1].I + (dy - dxdy) * p[W].I + (dx - dxdy) * p[1].I + (S(1) - dx - dy + dxdy) * p[0].I;
+  intensity[i] = inside ? static_cast<double>(s) : 0.0;
 }
 
 /** per-pass constants of the sweep: reprojection matrices of the candidate pose, photometric parameters */
@@ -331,6 +335,10 @@ __device__ __forceinline__ void alignSweepSetup(AlignSweepCtx<S> &x, const Align
 template <typename S>
 __device__ __forceinline__ void alignPointEval(const AlignSweepCtx<S> &x, S u, S v, S idepth, S iref, bool present, double (&d)[8], double &r_out,
                                                double &wgt_out, double &energy_out, double &valid_out) {
+  // a product and a sum are fused where they stand in ONE expression and nowhere else: left to the optimiser, which fuses across statements as
+  // it sees fit, the three kernels this is inlined into rounded differently (float: per-level rmse of the persistent launch and of the
+  // launch-per-iteration path 5e-7 apart; double: equal only by accident)
+#pragma clang fp contract(on)
   const S *M = x.M, *U = x.U;
   // reproject (checked) — camera_reproject.hpp:270-293
   bool good = present && validIdepth(idepth) && insideROI(u, v, x.Wr, x.Hr);
@@ -1122,9 +1130,9 @@ void sampleReferenceIntensitiesImpl(hipStream_t st, const dsopp_hip_pyramid *pyr
   const LevelView lv = pyr->view(level);
   const unsigned grid = static_cast<unsigned>((n + 255) / 256);
   if (pyr->dtype == DSOPP_HIP_F64)
-    sampleReferenceKernel<double><<<grid, 256, 0, st>>>(static_cast<const Texel<double> *>(lv.texels), lv.width, u, v, out, static_cast<int>(n));
+    sampleReferenceKernel<double><<<grid, 256, 0, st>>>(static_cast<const Texel<double> *>(lv.texels), lv.width, lv.height, u, v, out, static_cast<int>(n));
   else
-    sampleReferenceKernel<float><<<grid, 256, 0, st>>>(static_cast<const Texel<float> *>(lv.texels), lv.width, u, v, out, static_cast<int>(n));
+    sampleReferenceKernel<float><<<grid, 256, 0, st>>>(static_cast<const Texel<float> *>(lv.texels), lv.width, lv.height, u, v, out, static_cast<int>(n));
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1380,6 +1388,9 @@ int dsopp_hip_aligner_push_reference_points(dsopp_hip_aligner *a, int64_t timest
       fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
     checkPyramid(a, pyramid, level);
     if (a->have_ref || a->have_tgt) fail(DSOPP_HIP_ERR_ORDER, "the reference frame must be pushed first after reset()");
+    for (int32_t i = 0; i < n; ++i)
+      if (!referencePointFinite(u[i], v[i], idepth[i]))
+        fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "reference point %d (%g, %g, idepth %g) is not finite", i, u[i], v[i], idepth[i]);
     a->sr.use();
     setFrame(a->ref, pyramid, level, intrinsics, exposure_time, affine_brightness);
     a->T_w_ref = rigidFromParams(T_world_agent);

@@ -698,7 +698,9 @@ int dsopp_hip_aligner_push_reference_depth_map(dsopp_hip_aligner *a, int64_t tim
 int dsopp_hip_aligner_push_reference_depth_maps(dsopp_hip_aligner *a, int64_t timestamp, const double T_world_agent[7],
                                                 const dsopp_hip_pyramid *pyramid, int level, const double intrinsics[4],
                                                 const dsopp_hip_depth_maps *maps, double exposure_time, const double affine_brightness[2]);
-/* same with an explicit point list (u, v, idepth); intensity sampled on the device */
+/* same with an explicit point list (u, v, idepth); intensity sampled on the device.  A point outside the reference camera's ROI
+ * (4 <= u <= width - 5, 4 <= v <= height - 5) is kept in the list, never contributes (as in the reference) and is not sampled: its
+ * intensity is 0.  A coordinate or inverse depth that is not finite, or beyond 1e15 in magnitude: DSOPP_HIP_ERR_INVALID_ARGUMENT. */
 int dsopp_hip_aligner_push_reference_points(dsopp_hip_aligner *a, int64_t timestamp, const double T_world_agent[7],
                                             const dsopp_hip_pyramid *pyramid, int level, const double intrinsics[4], int32_t n,
                                             const double *u, const double *v, const double *idepth, double exposure_time,
