@@ -74,6 +74,9 @@ SYMBOLS = [
     "dsopp_hip_window_get_semantic_observations", "dsopp_hip_window_get_semantic_types", "dsopp_hip_pyramid_group_set_semantics",
     "dsopp_hip_window_group_add_semantic_observations", "dsopp_hip_window_group_get_semantic_observations",
     "dsopp_hip_window_group_get_semantic_types",
+    "dsopp_hip_transformer_create", "dsopp_hip_transformer_destroy", "dsopp_hip_transformer_sizes", "dsopp_hip_transform_calibration",
+    "dsopp_hip_transformer_transform_image", "dsopp_hip_transformer_transform_mask", "dsopp_hip_transformer_transform_device",
+    "dsopp_hip_pyramid_build_transformed", "dsopp_hip_semantics_create_transformed",
 ]
 
 _lib = None
@@ -197,21 +200,99 @@ class Undistorter:
         _chk(lib().dsopp_hip_undistorter_undistort_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
 
 
+LINEAR, NEAREST = 0, 1
+
+
+def transform_calibration(in_size, resize_ratio=1.0, crop_levels=4, intrinsics=None):
+    """transformCalibration of a resizer and a cropper on a pinhole calibration, no device needed: in_size = (width, height),
+    intrinsics = (fx, fy, cx, cy) or None -> (image_size (2 doubles), intrinsics (4 doubles) or None, (out_width, out_height))"""
+    k = None if intrinsics is None else _f64(intrinsics)
+    assert k is None or k.shape == (4,), k.shape
+    size, k_out, w, h = np.zeros(2), np.zeros(4), C.c_int(), C.c_int()
+    _chk(lib().dsopp_hip_transform_calibration(int(in_size[0]), int(in_size[1]), C.c_double(resize_ratio), int(crop_levels), _p(k), _p(size),
+                                               _p(k_out), C.byref(w), C.byref(h)))
+    return size, (None if k is None else k_out), (w.value, h.value)
+
+
+class Transformer:
+    """The camera's image transformers on the device (dsopp_hip_transformer): CameraResizer at resize_ratio (1.0 = none), then ImageCropper
+    down to a multiple of 2^crop_levels (0 = none).  in_size / resized_size / out_size = (width, height)."""
+
+    def __init__(self, in_size, resize_ratio=1.0, crop_levels=4, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.in_size, self.device = (int(in_size[0]), int(in_size[1])), device
+        _chk(lib().dsopp_hip_transformer_create(int(device), C.c_void_p(stream or 0), self.in_size[0], self.in_size[1], C.c_double(resize_ratio),
+                                                int(crop_levels), C.byref(self._h)))
+        _, self.resized_size, self.out_size = self.sizes()
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_transformer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sizes(self):
+        """((in_width, in_height), (resized_width, resized_height), (out_width, out_height)) as the handle reports them"""
+        v = [C.c_int() for _ in range(6)]
+        _chk(lib().dsopp_hip_transformer_sizes(self._h, *[C.byref(x) for x in v]))
+        return (v[0].value, v[1].value), (v[2].value, v[3].value), (v[4].value, v[5].value)
+
+    def _transform(self, entry, image):
+        img = _u8(image)
+        assert img.shape == (self.in_size[1], self.in_size[0]), img.shape
+        out = np.zeros((self.out_size[1], self.out_size[0]), dtype=np.uint8)
+        _chk(entry(self._h, _p(img, np.uint8), _p(out, np.uint8)))
+        return out
+
+    def transform_image(self, image):
+        """runImageTransformers(image): linear resize and crop, (in_height, in_width) uint8 -> (out_height, out_width) uint8, blocking"""
+        return self._transform(lib().dsopp_hip_transformer_transform_image, image)
+
+    def transform_mask(self, mask):
+        """runMaskTransformers(mask): nearest resize and crop, blocking"""
+        return self._transform(lib().dsopp_hip_transformer_transform_mask, mask)
+
+    def transform_device(self, in_ptr, out_ptr, interpolation=LINEAR, stream=None):
+        """the same between two device buffers (addresses as integers): enqueues on `stream`, None = the transformer's own"""
+        _chk(lib().dsopp_hip_transformer_transform_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(interpolation),
+                                                          C.c_void_p(stream or 0)))
+
+
 class Semantics:
     """The per-camera constants of semantic segmentation (dsopp_hip_semantics): static_mask (height, width) uint8 or None = all 255,
     is_filtered 256 bytes (non-zero = the class leaves the mask) or None = nothing is filtered, undistorter None = class images
-    arrive undistorted.  width and height must be divisible by 2^(levels - 1)."""
+    arrive undistorted.  width and height must be divisible by 2^(levels - 1).  Semantics.transformed() is the form for a camera
+    with image transformers."""
 
-    def __init__(self, width, height, levels, static_mask=None, is_filtered=None, undistorter: "Undistorter | None" = None, device=0, stream=None):
+    def __init__(self, width, height, levels, static_mask=None, is_filtered=None, undistorter: "Undistorter | None" = None, device=0, stream=None,
+                 transformer: "Transformer | None" = None):
         self._h = C.c_void_p()
         self.width, self.height, self.levels, self.device = int(width), int(height), int(levels), device
-        self._undistorter = undistorter  # borrowed by the handle: kept alive here
+        self._undistorter, self._transformer = undistorter, transformer  # borrowed by the handle: kept alive here
         m = _u8(static_mask)
         assert m is None or m.shape == (self.height, self.width), m.shape
         f = _u8(is_filtered)
         assert f is None or f.shape == (256,), f.shape
-        _chk(lib().dsopp_hip_semantics_create(int(device), C.c_void_p(stream or 0), self.width, self.height, self.levels, _p(m, np.uint8),
-                                              _p(f, np.uint8), undistorter._h if undistorter is not None else None, C.byref(self._h)))
+        u = undistorter._h if undistorter is not None else None
+        if transformer is not None:
+            assert (self.width, self.height) == transformer.out_size, transformer.out_size
+            _chk(lib().dsopp_hip_semantics_create_transformed(int(device), C.c_void_p(stream or 0), self.levels, _p(m, np.uint8), _p(f, np.uint8), u,
+                                                              transformer._h, C.byref(self._h)))
+        else:
+            _chk(lib().dsopp_hip_semantics_create(int(device), C.c_void_p(stream or 0), self.width, self.height, self.levels, _p(m, np.uint8),
+                                                  _p(f, np.uint8), u, C.byref(self._h)))
+
+    @classmethod
+    def transformed(cls, transformer: "Transformer", levels, static_mask=None, is_filtered=None, undistorter: "Undistorter | None" = None, device=0,
+                    stream=None):
+        """dsopp_hip_semantics_create_transformed: the size is the transformer's output, static_mask = transformer.transform_mask(undistorted
+        mask); set_semantics takes the class image as the camera delivers it, remaps it, resizes it (nearest) and crops it"""
+        return cls(transformer.out_size[0], transformer.out_size[1], levels, static_mask, is_filtered, undistorter, device, stream, transformer)
 
     def close(self):
         if self._h:
@@ -225,9 +306,11 @@ class Semantics:
             pass
 
     def class_image_shape(self):
-        """(rows, cols) of the class image set_semantics takes: the undistorter's input, else the pyramid's size"""
-        u = self._undistorter
-        return (u.in_size[1], u.in_size[0]) if u is not None else (self.height, self.width)
+        """(rows, cols) of the class image set_semantics takes: the undistorter's input, else the transformer's, else the pyramid's size"""
+        u, t = self._undistorter, self._transformer
+        if u is not None:
+            return (u.in_size[1], u.in_size[0])
+        return (t.in_size[1], t.in_size[0]) if t is not None else (self.height, self.width)
 
 
 class Pyramid:
@@ -264,6 +347,17 @@ class Pyramid:
         assert vig is None or vig.shape == (self.height, self.width)
         _chk(lib().dsopp_hip_pyramid_build_undistorted(self._h, undistorter._h, _p(img, np.uint8), _p(None if lut is None else _f64(lut)),
                                                        _p(vig, np.uint8)))
+
+    def build_transformed(self, undistorter: "Undistorter | None", transformer: "Transformer", image, lut=None, vignetting=None):
+        """build(transformer.transform_image(undistorter.undistort(image))) without the host round trips (undistorter None = the image
+        arrives undistorted); vignetting is the vignette already undistorted and transformed"""
+        img = _u8(image)
+        in_size = undistorter.in_size if undistorter is not None else transformer.in_size
+        assert img.shape == (in_size[1], in_size[0]), img.shape
+        vig = _u8(vignetting)
+        assert vig is None or vig.shape == (self.height, self.width)
+        _chk(lib().dsopp_hip_pyramid_build_transformed(self._h, undistorter._h if undistorter is not None else None, transformer._h,
+                                                       _p(img, np.uint8), _p(None if lut is None else _f64(lut)), _p(vig, np.uint8)))
 
     def build_device(self, image_dev_ptr, lut=None, vignetting_dev_ptr=None, vignetting_max=0.0):
         _chk(lib().dsopp_hip_pyramid_build_device(self._h, C.c_void_p(image_dev_ptr), _p(None if lut is None else _f64(lut)),
@@ -1166,7 +1260,7 @@ class FeatureExtractor:
         return rc, (xy[:n.value].copy() if rc == 0 else None), n.value
 
     def extract_from_pyramid(self, pyramid: Pyramid, mask=None, keep_mask=False):
-        """extract(image, mask) of the undistorted image `pyramid` kept from its last build_undistorted"""
+        """extract(image, mask) of the 8-bit image `pyramid` kept from its last build_undistorted or build_transformed"""
         if not keep_mask and ((mask is None) != (self._mask is None) or (mask is not None and not np.array_equal(_u8(mask), self._mask))):
             self.set_mask(mask)
         rc, xy, n = self.extract_from_pyramid_raw(pyramid, self._capacity)

@@ -377,7 +377,7 @@ int dsopp_hip_feature_extractor_extract(dsopp_hip_feature_extractor *ex, const u
 int dsopp_hip_feature_extractor_extract_from_pyramid(dsopp_hip_feature_extractor *ex, const dsopp_hip_pyramid *p, int32_t capacity, double *xy, int32_t *n) {
   return guarded([&] {
     if (!ex || !p || !n || capacity < 0 || (capacity > 0 && !xy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    if (!p->has_undistorted) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the pyramid keeps no 8-bit image: it was not built by dsopp_hip_pyramid_build_undistorted");
+    if (!p->has_undistorted) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the pyramid keeps no 8-bit image: it was not built by dsopp_hip_pyramid_build_undistorted or _build_transformed");
     if (p->width != ex->width || p->height != ex->height)
       fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "pyramid is %d x %d, the extractor %d x %d", p->width, p->height, ex->width, ex->height);
     if (p->sr.device != ex->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "extractor / pyramid live on another device");

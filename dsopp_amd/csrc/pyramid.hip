@@ -9,6 +9,7 @@
 // each thread regenerates from the parent plane (u8 + LUT at level 0, 2x2 means above) — reads are coalesced rows that
 // hit L2, writes are one full 16/32-byte texel per lane.  HBM-bound by construction: ~(1 + 4*sizeof(S)) bytes per pixel.
 #include "pyramid.hpp"
+#include "transform.hpp"
 #include "undistort.hpp"
 
 #include <memory>
@@ -489,6 +490,26 @@ double uploadVignette(dsopp_hip_pyramid *p, const uint8_t *vignetting_host, size
   }
   return vmax;
 }
+
+/** the levels from the 8-bit image the pyramid keeps (undistorted_u8), behind whatever was enqueued to write it; sets has_undistorted */
+void buildFromKeptImage(dsopp_hip_pyramid *p, const double *lut256, const uint8_t *vignetting_host) {
+  hipStream_t st = p->sr.stream;
+  // the vignette went through the same stages once, as the reference keeps it (undistorted_vignetting_)
+  const double vmax = uploadVignette(p, vignetting_host, static_cast<size_t>(p->width) * p->height);
+  const double *lut_dev = nullptr;
+  if (lut256) {
+    HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, st));
+    lut_dev = p->lut_dev.get();
+  }
+  const uint8_t *vig_dev = vignetting_host ? p->staging_vig.get() : nullptr;
+  if (p->dtype == DSOPP_HIP_F64)
+    buildTyped<double>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
+  else
+    buildTyped<float>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
+  p->markReady();
+  p->has_undistorted = true;
+  if (lut256 || vignetting_host) p->sr.sync();  // (as in build: those two are read straight from the caller's arrays)
+}
 }  // namespace
 
 int dsopp_hip_pyramid_build(dsopp_hip_pyramid *p, const uint8_t *image_host, const double *lut256, const uint8_t *vignetting_host) {
@@ -529,20 +550,35 @@ int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_un
     p->has_undistorted = false;
     uploadImage(p, p->distorted_u8.get(), distorted_host, n_in);
     enqueueUndistort(u, p->distorted_u8.get(), p->undistorted_u8.get(), st);
-    const double vmax = uploadVignette(p, vignetting_host, n);  // already undistorted, as the reference keeps it (undistorted_vignetting_)
-    const double *lut_dev = nullptr;
-    if (lut256) {
-      HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, st));
-      lut_dev = p->lut_dev.get();
-    }
-    const uint8_t *vig_dev = vignetting_host ? p->staging_vig.get() : nullptr;
-    if (p->dtype == DSOPP_HIP_F64)
-      buildTyped<double>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
-    else
-      buildTyped<float>(p, p->undistorted_u8.get(), vig_dev, lut_dev, vmax);
-    p->markReady();
-    p->has_undistorted = true;
-    if (lut256 || vignetting_host) p->sr.sync();  // (as in build: those two are read straight from the caller's arrays)
+    buildFromKeptImage(p, lut256, vignetting_host);
+  });
+}
+
+int dsopp_hip_pyramid_build_transformed(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const dsopp_hip_transformer *t, const uint8_t *frame_host,
+                                        const double *lut256, const uint8_t *vignetting_host) {
+  return guarded([&] {
+    if (!p || !t || !frame_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (u && u->sr.device != p->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter lives on device %d, the pyramid on %d", u->sr.device, p->sr.device);
+    if (t->sr.device != p->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the transformer lives on device %d, the pyramid on %d", t->sr.device, p->sr.device);
+    if (u && (u->out_w != t->in_w || u->out_h != t->in_h))
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the transformer reads %d x %d", u->out_w, u->out_h, t->in_w, t->in_h);
+    if (t->out_w != p->width || t->out_h != p->height)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the transformer writes %d x %d, the pyramid is %d x %d", t->out_w, t->out_h, p->width, p->height);
+    p->sr.use();
+    hipStream_t st = p->sr.stream;
+    const size_t n_frame = u ? static_cast<size_t>(u->in_w) * u->in_h : static_cast<size_t>(t->in_w) * t->in_h;
+    const size_t n_untransformed = static_cast<size_t>(t->in_w) * t->in_h, n = static_cast<size_t>(p->width) * p->height;
+    // frame -> [remap] -> [resize + crop] -> the kept image; a stage that is not there hands its buffer on (nothing to do: as build_undistorted)
+    uint8_t *frame_dev = u ? reserveImage(p->distorted_u8, p->distorted_bytes, n_frame, st) : nullptr;
+    uint8_t *untransformed_dev = t->identity() ? nullptr : reserveImage(p->untransformed_u8, p->untransformed_bytes, n_untransformed, st);
+    if (!p->undistorted_u8) p->undistorted_u8.alloc(n);
+    if (!untransformed_dev) untransformed_dev = p->undistorted_u8.get();
+    if (!frame_dev) frame_dev = untransformed_dev;
+    p->has_undistorted = false;
+    uploadImage(p, frame_dev, frame_host, n_frame);
+    if (u) enqueueUndistort(u, frame_dev, untransformed_dev, st);
+    enqueueTransform(t, untransformed_dev, p->undistorted_u8.get(), kTransformLinear, st);
+    buildFromKeptImage(p, lut256, vignetting_host);
   });
 }
 

@@ -78,6 +78,17 @@ __device__ __forceinline__ Texel<S> loadTexel(const Texel<S> *p) {  // a generic
 /** `n` bytes of a caller's image into pinned memory with non-temporal stores (pyramid.hip) */
 void copyToPinned(uint8_t *dst, const uint8_t *src, size_t n);
 
+/** a device image of at least `n` bytes in `mem` (`bytes` = its size), replaced by a larger one when it is too small: `stream`, whose
+ *  work may still read the old one, is waited for first */
+inline uint8_t *reserveImage(DeviceMem<uint8_t> &mem, size_t &bytes, size_t n, hipStream_t stream) {
+  if (bytes < n) {
+    HIP_CHECK(hipStreamSynchronize(stream));
+    mem.alloc(n);
+    bytes = n;
+  }
+  return mem.get();
+}
+
 struct LevelView {
   const void *texels;  // Texel<S>*
   int width, height;
@@ -97,15 +108,20 @@ struct dsopp_hip_pyramid {
   // dsopp_hip_pyramid_build_undistorted: the distorted image as uploaded (sized by its first call) and its remap, the 8-bit image the
   // levels are built from.  The remap is kept for dsopp_hip_feature_extractor_extract_from_pyramid, which reads it behind waitReady();
   // every other rewrite of the image (build, build_device, set_level) clears has_undistorted.
-  dsopp_hip::DeviceMem<uint8_t> distorted_u8, undistorted_u8;
-  size_t distorted_bytes = 0;
+  // dsopp_hip_pyramid_build_transformed keeps its resized and cropped image in undistorted_u8 as well and sets the same flag: it is the
+  // image the reference extracts from.  untransformed_u8 is what its transformer reads (the remap's output, or the frame as uploaded when
+  // there is no undistorter), sized by its first call.
+  dsopp_hip::DeviceMem<uint8_t> distorted_u8, undistorted_u8, untransformed_u8;
+  size_t distorted_bytes = 0, untransformed_bytes = 0;
   bool has_undistorted = false;
   // dsopp_hip_pyramid_set_semantics (semantics.hip): the frame's class image as uploaded (only with an undistorter; sized by the first
   // call) and undistorted (semanticsData of the frame: the window's class observations read it), and the level-0 mask as bytes
   // (dsopp_hip_feature_extractor_set_mask_from_pyramid erodes it).  All read behind waitReady().  The class image leaves from a pinned
   // buffer of its own, so that a set_semantics behind a build need not wait for the build's upload; semantics_uploaded guards its reuse.
-  dsopp_hip::DeviceMem<uint8_t> semantics_in_u8, semantics_u8, mask0_u8;
-  size_t semantics_in_bytes = 0;
+  // With a transformer (dsopp_hip_semantics_create_transformed) semantics_u8 is the class image resized and cropped, and
+  // semantics_untransformed_u8 what the transformer reads, sized by the first call.
+  dsopp_hip::DeviceMem<uint8_t> semantics_in_u8, semantics_u8, mask0_u8, semantics_untransformed_u8;
+  size_t semantics_in_bytes = 0, semantics_untransformed_bytes = 0;
   bool has_semantics = false, has_mask0 = false;
   dsopp_hip::PinnedMem<uint8_t> h_semantics;
   dsopp_hip::Event semantics_uploaded;

@@ -6,7 +6,8 @@
 //   SemanticFilter::is_filtered_                   src/common/semantics/src/semantic_filter.cpp:5-14
 //
 // The class image takes the path of a camera image in dsopp_hip_pyramid_build_undistorted: pinned buffer, DMA, the undistorter's remap
-// kernel on the pyramid's stream.  Then ONE launch writes the mask lane of the texels of every level and the level-0 mask bytes.  Every
+// kernel on the pyramid's stream, and with a transformer (dsopp_hip_semantics_create_transformed) its nearest resize and crop behind
+// that (runMaskTransformers, camera.cpp:62).  Then ONE launch writes the mask lane of the texels of every level and the level-0 mask bytes.  Every
 // level is formed from level 0 directly (the reference resizes the finest mask to every size, it does not chain), so no level waits for
 // another: a thread of level l >= 1 filters its own four level-0 pixels.  All integer: m_l = (sum of the 2 x 2 block around the sample
 // point + 2) >> 2, which is cv::resize(INTER_LINEAR) at the ratio 2^-l — the sample point (x + 0.5) 2^l - 0.5 lies midway between two
@@ -15,6 +16,7 @@
 #include <memory>
 
 #include "pyramid.hpp"
+#include "transform.hpp"
 #include "undistort.hpp"
 
 struct dsopp_hip_semantics {
@@ -23,6 +25,7 @@ struct dsopp_hip_semantics {
   dsopp_hip::DeviceMem<uint8_t> static_mask;  // W x H bytes (all 255 without a static mask)
   dsopp_hip::DeviceMem<uint8_t> is_filtered;  // 256 bytes; null = filterBySemantic() is false
   const dsopp_hip_undistorter *undistorter = nullptr;  // borrowed; null = class images arrive undistorted
+  const dsopp_hip_transformer *transformer = nullptr;  // borrowed; null = class images are neither resized nor cropped
 };
 
 namespace dsopp_hip {
@@ -125,6 +128,38 @@ void launchMasks(dsopp_hip_pyramid *p, const dsopp_hip_semantics *s, const uint8
   HIP_CHECK(hipGetLastError());
 }
 
+/** what both creators share; the sizes of `undistorter` and `transformer` are the caller's to check */
+void createSemantics(int device, void *stream, int width, int height, int levels, const uint8_t *static_mask_host, const uint8_t *is_filtered256,
+                     const dsopp_hip_undistorter *undistorter, const dsopp_hip_transformer *transformer, dsopp_hip_semantics **out) {
+  if (!out || width <= 0 || height <= 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "bad semantics dimensions");
+  if (levels < 1 || levels > DSOPP_HIP_MAX_LEVELS) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d levels: 1 .. %d", levels, DSOPP_HIP_MAX_LEVELS);
+  const int step = 1 << (levels - 1);
+  if (width % step || height % step)
+    fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d x %d is not divisible by %d: the masks of %d levels would not have the sizes of the image levels", width,
+         height, step, levels);
+  if (undistorter && undistorter->sr.device != device)
+    fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter lives on device %d, not %d", undistorter->sr.device, device);
+  auto s = std::make_unique<dsopp_hip_semantics>();
+  s->sr.init(device, stream);
+  s->width = width;
+  s->height = height;
+  s->levels = levels;
+  s->undistorter = undistorter;
+  s->transformer = transformer;
+  const size_t n = static_cast<size_t>(width) * height;
+  s->static_mask.alloc(n);
+  if (static_mask_host)
+    HIP_CHECK(hipMemcpyAsync(s->static_mask.get(), static_mask_host, n, hipMemcpyHostToDevice, s->sr.stream));
+  else
+    HIP_CHECK(hipMemsetAsync(s->static_mask.get(), 255, n, s->sr.stream));  // CameraMask(rows, cols)
+  if (is_filtered256) {
+    s->is_filtered.alloc(256);
+    HIP_CHECK(hipMemcpyAsync(s->is_filtered.get(), is_filtered256, 256, hipMemcpyHostToDevice, s->sr.stream));
+  }
+  s->sr.sync();
+  *out = s.release();
+}
+
 }  // namespace
 }  // namespace dsopp_hip
 
@@ -135,34 +170,22 @@ extern "C" {
 int dsopp_hip_semantics_create(int device, void *stream, int width, int height, int levels, const uint8_t *static_mask_host,
                                const uint8_t *is_filtered256, const dsopp_hip_undistorter *undistorter, dsopp_hip_semantics **out) {
   return guarded([&] {
-    if (!out || width <= 0 || height <= 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "bad semantics dimensions");
-    if (levels < 1 || levels > DSOPP_HIP_MAX_LEVELS) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d levels: 1 .. %d", levels, DSOPP_HIP_MAX_LEVELS);
-    const int step = 1 << (levels - 1);
-    if (width % step || height % step)
-      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d x %d is not divisible by %d: the masks of %d levels would not have the sizes of the image levels", width,
-           height, step, levels);
     if (undistorter && (undistorter->out_w != width || undistorter->out_h != height))
       fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the masks are %d x %d", undistorter->out_w, undistorter->out_h, width, height);
-    if (undistorter && undistorter->sr.device != device)
-      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter lives on device %d, not %d", undistorter->sr.device, device);
-    auto s = std::make_unique<dsopp_hip_semantics>();
-    s->sr.init(device, stream);
-    s->width = width;
-    s->height = height;
-    s->levels = levels;
-    s->undistorter = undistorter;
-    const size_t n = static_cast<size_t>(width) * height;
-    s->static_mask.alloc(n);
-    if (static_mask_host)
-      HIP_CHECK(hipMemcpyAsync(s->static_mask.get(), static_mask_host, n, hipMemcpyHostToDevice, s->sr.stream));
-    else
-      HIP_CHECK(hipMemsetAsync(s->static_mask.get(), 255, n, s->sr.stream));  // CameraMask(rows, cols)
-    if (is_filtered256) {
-      s->is_filtered.alloc(256);
-      HIP_CHECK(hipMemcpyAsync(s->is_filtered.get(), is_filtered256, 256, hipMemcpyHostToDevice, s->sr.stream));
-    }
-    s->sr.sync();
-    *out = s.release();
+    createSemantics(device, stream, width, height, levels, static_mask_host, is_filtered256, undistorter, nullptr, out);
+  });
+}
+
+int dsopp_hip_semantics_create_transformed(int device, void *stream, int levels, const uint8_t *static_mask_host, const uint8_t *is_filtered256,
+                                           const dsopp_hip_undistorter *undistorter, const dsopp_hip_transformer *transformer,
+                                           dsopp_hip_semantics **out) {
+  return guarded([&] {
+    if (!transformer) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null transformer");
+    if (undistorter && (undistorter->out_w != transformer->in_w || undistorter->out_h != transformer->in_h))
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the transformer reads %d x %d", undistorter->out_w, undistorter->out_h,
+           transformer->in_w, transformer->in_h);
+    if (transformer->sr.device != device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the transformer lives on device %d, not %d", transformer->sr.device, device);
+    createSemantics(device, stream, transformer->out_w, transformer->out_h, levels, static_mask_host, is_filtered256, undistorter, transformer, out);
   });
 }
 
@@ -189,18 +212,20 @@ int dsopp_hip_pyramid_set_semantics(dsopp_hip_pyramid *p, const dsopp_hip_semant
     if (class_image_host) {
       if (!p->semantics_u8) p->semantics_u8.alloc(n);
       const dsopp_hip_undistorter *u = s->undistorter;
+      const dsopp_hip_transformer *t = s->transformer && !s->transformer->identity() ? s->transformer : nullptr;
+      // class image -> [remap] -> [nearest resize + crop] -> semantics_u8 (camera.cpp:57-65); a stage that is not there hands its buffer on
+      uint8_t *untransformed_dev = p->semantics_u8.get();
+      if (t)
+        untransformed_dev = reserveImage(p->semantics_untransformed_u8, p->semantics_untransformed_bytes, static_cast<size_t>(t->in_w) * t->in_h, st);
       if (u) {
         const size_t n_in = static_cast<size_t>(u->in_w) * u->in_h;
-        if (p->semantics_in_bytes < n_in) {
-          HIP_CHECK(hipStreamSynchronize(st));  // (the buffer that is replaced may still be read)
-          p->semantics_in_u8.alloc(n_in);
-          p->semantics_in_bytes = n_in;
-        }
+        reserveImage(p->semantics_in_u8, p->semantics_in_bytes, n_in, st);
         uploadClassImage(p, p->semantics_in_u8.get(), class_image_host, n_in);
-        enqueueUndistort(u, p->semantics_in_u8.get(), p->semantics_u8.get(), st);
+        enqueueUndistort(u, p->semantics_in_u8.get(), untransformed_dev, st);
       } else {
-        uploadClassImage(p, p->semantics_u8.get(), class_image_host, n);
+        uploadClassImage(p, untransformed_dev, class_image_host, t ? static_cast<size_t>(t->in_w) * t->in_h : n);
       }
+      if (t) enqueueTransform(t, untransformed_dev, p->semantics_u8.get(), kTransformNearest, st);
       cls_dev = p->semantics_u8.get();
     }
     if (p->dtype == DSOPP_HIP_F64)

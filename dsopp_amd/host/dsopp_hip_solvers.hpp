@@ -80,6 +80,52 @@ class HipUndistorter {
   int out_width_, out_height_;
 };
 
+/** The camera's image transformers (camera_transformers/fabric.cpp:12-31) on the device: a CameraResizer at `resize_ratio` (1.0 = the YAML
+ *  has no resize_transformer) followed by the ImageCropper down to a multiple of 2^crop_levels (the reference: kNumberOfPyramidLevels = 4).
+ *  Runs behind the undistorter on every frame, class image, static mask and vignette; the integer arithmetic is stated at
+ *  dsopp_hip_transformer_create. */
+class HipImageTransformer {
+ public:
+  HipImageTransformer(int in_width, int in_height, double resize_ratio = 1.0, int crop_levels = 4, int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_transformer_create(device, stream, in_width, in_height, resize_ratio, crop_levels, &t_));
+    check(dsopp_hip_transformer_sizes(t_, nullptr, nullptr, nullptr, nullptr, &out_width_, &out_height_));
+  }
+  ~HipImageTransformer() { dsopp_hip_transformer_destroy(t_); }
+  HipImageTransformer(const HipImageTransformer &) = delete;
+  HipImageTransformer &operator=(const HipImageTransformer &) = delete;
+  int outWidth() const { return out_width_; }
+  int outHeight() const { return out_height_; }
+  /** transformCalibration of both transformers on a pinhole calibration (camera_fabric.cpp:157-159); needs no device */
+  static PinholeModel transformCalibration(int in_width, int in_height, double resize_ratio, int crop_levels, const PinholeModel &model,
+                                           double image_size[2]) {
+    const double in[4] = {model.fx, model.fy, model.cx, model.cy};
+    double out[4];
+    check(dsopp_hip_transform_calibration(in_width, in_height, resize_ratio, crop_levels, in, image_size, out, nullptr, nullptr));
+    return PinholeModel{out[0], out[1], out[2], out[3]};
+  }
+  /** runImageTransformers (linear) of an 8-bit single-channel image, blocking: the undistorted vignette (camera_fabric.cpp:167) */
+  std::vector<uint8_t> transformImage(const uint8_t *image) const {
+    std::vector<uint8_t> out(static_cast<size_t>(out_width_) * static_cast<size_t>(out_height_));
+    check(dsopp_hip_transformer_transform_image(t_, image, out.data()));
+    return out;
+  }
+  /** runMaskTransformers (nearest), blocking: the undistorted static mask (camera_fabric.cpp:164) */
+  std::vector<uint8_t> transformMask(const uint8_t *mask) const {
+    std::vector<uint8_t> out(static_cast<size_t>(out_width_) * static_cast<size_t>(out_height_));
+    check(dsopp_hip_transformer_transform_mask(t_, mask, out.data()));
+    return out;
+  }
+  /** either between two 4-byte aligned device images (interpolation 0 = linear, 1 = nearest); only enqueues on `stream` */
+  void transformDevice(const void *in_dev, void *out_dev, int interpolation, void *stream = nullptr) const {
+    check(dsopp_hip_transformer_transform_device(t_, in_dev, out_dev, interpolation, stream));
+  }
+  const dsopp_hip_transformer *handle() const { return t_; }
+
+ private:
+  dsopp_hip_transformer *t_ = nullptr;
+  int out_width_ = 0, out_height_ = 0;
+};
+
 /** The per-camera constants of the `segmentation:` block (camera_fabric.cpp:54-99,170-186) on the device: the static mask as the camera
  *  keeps it (already undistorted, camera_fabric.cpp:164; nullptr = all valid), SemanticFilter::is_filtered_ (256 bytes; nullptr =
  *  filterBySemantic() is false) and the undistorter the class images go through (nullptr = they arrive undistorted; it must outlive
@@ -89,6 +135,13 @@ class HipSemantics {
   HipSemantics(int width, int height, int levels, const uint8_t *static_mask, const uint8_t *is_filtered256, const HipUndistorter *undistorter = nullptr,
                int device = 0, void *stream = nullptr) {
     check(dsopp_hip_semantics_create(device, stream, width, height, levels, static_mask, is_filtered256, undistorter ? undistorter->handle() : nullptr, &s_));
+  }
+  /** for a camera with image transformers: the size is the transformer's output, static_mask already undistorted and transformed
+   *  (HipImageTransformer::transformMask), class images are remapped, resized (nearest) and cropped; both helpers must outlive this object */
+  HipSemantics(const HipImageTransformer &transformer, int levels, const uint8_t *static_mask, const uint8_t *is_filtered256,
+               const HipUndistorter *undistorter = nullptr, int device = 0, void *stream = nullptr) {
+    check(dsopp_hip_semantics_create_transformed(device, stream, levels, static_mask, is_filtered256, undistorter ? undistorter->handle() : nullptr,
+                                                 transformer.handle(), &s_));
   }
   ~HipSemantics() { dsopp_hip_semantics_destroy(s_); }
   HipSemantics(const HipSemantics &) = delete;
@@ -117,6 +170,13 @@ class DevicePyramid {
   void buildUndistorted(const HipUndistorter &undistorter, const uint8_t *distorted_image, const double *photometric_calibration256 = nullptr,
                         const uint8_t *undistorted_vignetting = nullptr) {
     check(dsopp_hip_pyramid_build_undistorted(p_, undistorter.handle(), distorted_image, photometric_calibration256, undistorted_vignetting));
+  }
+  /** PixelDataFrame(runImageTransformers(transformers, undistorter.undistort(frame)), ...) — camera.cpp:70 in full: remap (nullptr =
+   *  the frame arrives undistorted), resize and crop on the device, the vignette already undistorted and transformed */
+  void buildTransformed(const HipUndistorter *undistorter, const HipImageTransformer &transformer, const uint8_t *frame,
+                        const double *photometric_calibration256 = nullptr, const uint8_t *transformed_vignetting = nullptr) {
+    check(dsopp_hip_pyramid_build_transformed(p_, undistorter ? undistorter->handle() : nullptr, transformer.handle(), frame,
+                                              photometric_calibration256, transformed_vignetting));
   }
   /** adopt a PixelMap<1> level built on the host by the reference */
   void setLevel(int level, const double *pixelinfo) { check(dsopp_hip_pyramid_set_level(p_, level, pixelinfo)); }

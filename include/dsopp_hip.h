@@ -150,6 +150,62 @@ int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_un
                                         const uint8_t *vignetting_host);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Image transformers: the resize and the crop behind the undistortion (replaces CameraResizer — src/sensors/camera_transformers/src/
+ * camera_resizer.cpp:7-20 — and ImageCropper — src/sensors/camera_transformers/src/image_cropper.cpp:7-18 —, the list that
+ * src/sensors/camera_transformers/src/fabric.cpp:12-31 builds for every camera: a resizer when the YAML has a `resize_transformer`,
+ * then always the cropper.  src/sensors/camera/src/camera.cpp:57-70 runs it on every frame and every class image,
+ * src/sensors/sensors_builder/src/camera_fabric.cpp:157-167 once on the calibration, the static mask and the vignette)
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_transformer dsopp_hip_transformer;
+/* resize_ratio: CameraResizer's new_to_old_size_ratio (1.0 = no resizer configured); crop_levels: the ImageCropper's shift (the
+ * reference: kNumberOfPyramidLevels = 4; 0 = no crop).  Sizes, per axis (camera_resizer.cpp:9-10, camera_image_crop.hpp:16-20):
+ *   resized = (int)((double)in * resize_ratio), truncated;  out = (resized >> crop_levels) << crop_levels.
+ * The arithmetic of every later transform is integer and fixed here, for a single-channel 8-bit image.
+ * Linear (the camera image and the vignette; cv::resize INTER_LINEAR, camera_resizer.cpp:12), per axis n_in -> n_resized:
+ *   scale = 1.0 / ((double)n_resized / n_in);  for the output index d:  f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s
+ *   in float;  s < 0: s = 0, f = 0;  s >= n_in - 1: s = n_in - 1, f = 0 (the second tap then has weight 0 and is not read outside
+ *   the image);  weights w1 = rint(f * 2048.0f), w0 = rint((1.0f - f) * 2048.0f), both half to even.
+ *   With (sx, a0, a1) of column x and (sy, b0, b1) of row y:  r(v) = a0 * S[v, sx] + a1 * S[v, sx + 1],
+ *   out[y, x] = (((b0 * (r(sy) >> 4)) >> 16) + ((b1 * (r(sy + 1) >> 4)) >> 16) + 2) >> 2, always within 0 .. 255.
+ *   So ratio 1 is the identity and ratio 0.5 of an even size is (a + b + c + d + 2) >> 2 of every 2 x 2 block.
+ * Nearest (the static mask and the class image; INTER_NEAREST, camera_resizer.cpp:16): s = min(floor(d * scale), n_in - 1), out = S[sy, sx].
+ * The crop keeps rows [0, out_h) and columns [0, out_w) of the resized image (image_cropper.cpp:12); only those are computed.
+ * Both axes are folded into device tables of out_w + out_h entries before the call returns.  With nothing to do (resized == out ==
+ * in) no kernel is ever launched.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: a ratio that is not finite or not positive, in_w or in_h < 1, crop_levels outside 0 .. 8, an
+ * output axis of 0 pixels, an input or resized image of more than INT_MAX pixels. */
+int dsopp_hip_transformer_create(int device, void *stream, int in_w, int in_h, double resize_ratio, int crop_levels, dsopp_hip_transformer **out);
+void dsopp_hip_transformer_destroy(dsopp_hip_transformer *t);
+/* the three sizes above; any pointer may be NULL */
+int dsopp_hip_transformer_sizes(const dsopp_hip_transformer *t, int *in_w, int *in_h, int *resized_w, int *resized_h, int *out_w, int *out_h);
+/* transformCalibration of every transformer (camera_fabric.cpp:157-159) on a pinhole calibration; needs no device.
+ * CameraCalibration::resize (src/sensors/camera_calibration/src/camera_calibration.cpp:33-42): image_size = in * ratio, NOT truncated,
+ * and all four intrinsics (fx, fy, cx, cy) times the ratio — the reference shifts cx, cy by no half pixel, and neither does this.
+ * CameraCalibration::crop (:44-46): image_size = ((size_t)image_size >> crop_levels) << crop_levels; the origin stays at the top-left
+ * pixel, so the intrinsics do not change.  out_w / out_h are the transformer's output size.  (simple_radial scales only its first three
+ * intrinsics, :37-38: not built.)  Any output pointer may be NULL; intrinsics_out is written only with intrinsics_in.  The argument
+ * errors of dsopp_hip_transformer_create. */
+int dsopp_hip_transform_calibration(int in_w, int in_h, double resize_ratio, int crop_levels, const double intrinsics_in[4], double image_size_out[2],
+                                    double intrinsics_out[4], int *out_w, int *out_h);
+/* runImageTransformers (linear) and runMaskTransformers (nearest) of an in_h x in_w 8-bit image into out_h x out_w bytes, blocking:
+ * the once-per-camera forms for the vignette and the static mask (camera_fabric.cpp:164-167), behind dsopp_hip_undistorter_undistort */
+int dsopp_hip_transformer_transform_image(dsopp_hip_transformer *t, const uint8_t *image_host, uint8_t *out_host);
+int dsopp_hip_transformer_transform_mask(dsopp_hip_transformer *t, const uint8_t *mask_host, uint8_t *out_host);
+/* same, both images in HBM: the call only enqueues on `stream` (a hipStream_t; NULL = the transformer's own) one launch, or one copy
+ * when there is nothing to do.  interpolation: 0 = linear, 1 = nearest.  Both pointers must be 4-byte aligned, else
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+int dsopp_hip_transformer_transform_device(dsopp_hip_transformer *t, const void *in_dev, void *out_dev, int interpolation, void *stream);
+/* The per-frame path, camera.cpp:70 followed by the PixelDataFrame ctor: dsopp_hip_pyramid_build of
+ * runImageTransformers(undistort(frame_host)).  u = NULL: frames arrive undistorted (t's input size), else u's input size.  The frame
+ * goes through the pyramid's pinned buffer as in build_undistorted; on the pyramid's stream follow the remap (with u), the transformer's
+ * launch (unless it has nothing to do) and the level build; the call does not wait for them.  The pyramid keeps the transformed 8-bit
+ * image, the one the reference extracts features from: dsopp_hip_feature_extractor_extract_from_pyramid reads it as it reads
+ * build_undistorted's.  vignetting_host is the vignette already undistorted and transformed (camera_fabric.cpp:167).  f64 and f32
+ * pyramids.  DSOPP_HIP_ERR_INVALID_ARGUMENT unless all three live on one device, u writes t's input size and t writes the pyramid's. */
+int dsopp_hip_pyramid_build_transformed(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const dsopp_hip_transformer *t, const uint8_t *frame_host,
+                                        const double *lut256, const uint8_t *vignetting_host);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
  * image — src/sensors/camera/src/camera.cpp:57-65 —, CameraMask::filterSemanticObjects —
  * src/sensors/camera_calibration/src/camera_mask.cpp:31-39 — and the mask pyramid of src/features/src/camera_features.cpp:71-84; the
@@ -165,6 +221,16 @@ typedef struct dsopp_hip_semantics dsopp_hip_semantics;
  * else DSOPP_HIP_ERR_INVALID_ARGUMENT.  Both host arrays are copied before the call returns. */
 int dsopp_hip_semantics_create(int device, void *stream, int width, int height, int levels, const uint8_t *static_mask_host,
                                const uint8_t *is_filtered256, const dsopp_hip_undistorter *undistorter, dsopp_hip_semantics **out);
+/* The same for a camera with image transformers (camera.cpp:57-65: the class image is undistorted, then goes through
+ * runMaskTransformers).  Width and height are the transformer's output size; static_mask_host is the mask already undistorted and
+ * transformed (dsopp_hip_transformer_transform_mask, camera_fabric.cpp:164).  dsopp_hip_pyramid_set_semantics then takes the class
+ * image at the undistorter's input size (without one: the transformer's), remaps it, resizes it with INTER_NEAREST and crops it, and
+ * the pyramid keeps that as the frame's semanticsData.  Both are BORROWED, must outlive this object and live on `device`; the
+ * undistorter (may be NULL) must write the transformer's input size, and the output size must be divisible by 2^(levels - 1) — which
+ * the crop provides for crop_levels >= levels - 1 — else DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+int dsopp_hip_semantics_create_transformed(int device, void *stream, int levels, const uint8_t *static_mask_host, const uint8_t *is_filtered256,
+                                           const dsopp_hip_undistorter *undistorter, const dsopp_hip_transformer *transformer,
+                                           dsopp_hip_semantics **out);
 void dsopp_hip_semantics_destroy(dsopp_hip_semantics *s);
 /* The frame's class image and the masks of all its levels.  class_image_host: the distorted in_h x in_w class codes (W x H without an
  * undistorter); it goes through a pinned buffer of the pyramid, is remapped on the pyramid's stream by the undistorter's kernel (the
