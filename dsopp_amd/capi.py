@@ -77,6 +77,8 @@ SYMBOLS = [
     "dsopp_hip_transformer_create", "dsopp_hip_transformer_destroy", "dsopp_hip_transformer_sizes", "dsopp_hip_transform_calibration",
     "dsopp_hip_transformer_transform_image", "dsopp_hip_transformer_transform_mask", "dsopp_hip_transformer_transform_device",
     "dsopp_hip_pyramid_build_transformed", "dsopp_hip_semantics_create_transformed",
+    "dsopp_hip_undistorter_undistort_bgr_device", "dsopp_hip_transformer_transform_bgr_device", "dsopp_hip_pyramid_build_colour",
+    "dsopp_hip_pyramid_get_image",
 ]
 
 _lib = None
@@ -199,6 +201,12 @@ class Undistorter:
         """the same between two device buffers (addresses as integers): enqueues on `stream`, None = the undistorter's own"""
         _chk(lib().dsopp_hip_undistorter_undistort_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
 
+    def undistort_bgr_device(self, bgr_in_ptr, bgr_out_ptr=None, grey_out_ptr=None, stream=None):
+        """the remap of an interleaved 8-bit BGR image between device buffers (addresses as integers): the colour result, its grey
+        conversion, or both (None = not wanted); enqueues on `stream`, None = the undistorter's own"""
+        _chk(lib().dsopp_hip_undistorter_undistort_bgr_device(self._h, C.c_void_p(bgr_in_ptr or 0), C.c_void_p(bgr_out_ptr or 0),
+                                                              C.c_void_p(grey_out_ptr or 0), C.c_void_p(stream or 0)))
+
 
 LINEAR, NEAREST = 0, 1
 
@@ -261,6 +269,12 @@ class Transformer:
         """the same between two device buffers (addresses as integers): enqueues on `stream`, None = the transformer's own"""
         _chk(lib().dsopp_hip_transformer_transform_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(interpolation),
                                                           C.c_void_p(stream or 0)))
+
+    def transform_bgr_device(self, bgr_in_ptr, bgr_out_ptr=None, grey_out_ptr=None, stream=None):
+        """the linear resize and crop of an interleaved 8-bit BGR image between device buffers (addresses as integers): the colour
+        result, its grey conversion, or both (None = not wanted); enqueues on `stream`, None = the transformer's own"""
+        _chk(lib().dsopp_hip_transformer_transform_bgr_device(self._h, C.c_void_p(bgr_in_ptr or 0), C.c_void_p(bgr_out_ptr or 0),
+                                                              C.c_void_p(grey_out_ptr or 0), C.c_void_p(stream or 0)))
 
 
 class Semantics:
@@ -358,6 +372,29 @@ class Pyramid:
         assert vig is None or vig.shape == (self.height, self.width)
         _chk(lib().dsopp_hip_pyramid_build_transformed(self._h, undistorter._h if undistorter is not None else None, transformer._h,
                                                        _p(img, np.uint8), _p(None if lut is None else _f64(lut)), _p(vig, np.uint8)))
+
+    def build_colour(self, undistorter: "Undistorter | None", transformer: "Transformer | None", bgr, lut=None, vignetting=None,
+                     keep_colour=False):
+        """build(BGR2GRAY(transformer.transform(undistorter.undistort(bgr)))) of an (rows, cols, 3) uint8 BGR frame, all three channels
+        through both stages and the grey conversion last; either stage may be None.  vignetting is the single-channel vignette already
+        undistorted and transformed.  keep_colour: get_image(3) then returns the transformed colour image."""
+        img = _u8(bgr)
+        first = undistorter if undistorter is not None else transformer
+        in_size = first.in_size if first is not None else (self.width, self.height)
+        assert img.shape == (in_size[1], in_size[0], 3), img.shape
+        vig = _u8(vignetting)
+        assert vig is None or vig.shape == (self.height, self.width)
+        _chk(lib().dsopp_hip_pyramid_build_colour(self._h, undistorter._h if undistorter is not None else None,
+                                                  transformer._h if transformer is not None else None, _p(img, np.uint8),
+                                                  _p(None if lut is None else _f64(lut)), _p(vig, np.uint8), int(bool(keep_colour))))
+
+    def get_image(self, channels=1):
+        """the 8-bit image the pyramid keeps, or None: channels = 1 the grey image the levels were built from (height, width), 3 the
+        colour image of a build_colour with keep_colour (height, width, 3)"""
+        out = np.zeros((self.height, self.width) if channels == 1 else (self.height, self.width, max(int(channels), 1)), dtype=np.uint8)
+        present = C.c_int()
+        _chk(lib().dsopp_hip_pyramid_get_image(self._h, int(channels), _p(out, np.uint8), C.byref(present)))
+        return out if present.value else None
 
     def build_device(self, image_dev_ptr, lut=None, vignetting_dev_ptr=None, vignetting_max=0.0):
         _chk(lib().dsopp_hip_pyramid_build_device(self._h, C.c_void_p(image_dev_ptr), _p(None if lut is None else _f64(lut)),

@@ -14,7 +14,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno
 # updates with the reciprocal chains (profiles/r06/tracker_*: control step 1.76 -> see DESIGN.md section 4)
 FLAGS_align="${DSOPP_HIP_ALIGN_SCHED--mllvm -amdgpu-sched-strategy=max-ilp}"
 pids=()
-for src in pyramid undistort transform semantics pba align depth_estimation features features_eigen comm calibration window_group; do
+for src in pyramid undistort transform colour semantics pba align depth_estimation features features_eigen comm calibration window_group; do
   if [ -f "$HERE/$src.hip" ]; then
     extra="FLAGS_$src"
     $HIPCC $FLAGS ${!extra:-} -c "$HERE/$src.hip" -o "$OUT/$src.o" &
@@ -23,7 +23,7 @@ for src in pyramid undistort transform semantics pba align depth_estimation feat
 done
 for p in "${pids[@]}"; do wait "$p"; done
 objs=()
-for src in pyramid undistort transform semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
+for src in pyramid undistort transform colour semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$OUT/libdsopp_hip.so"
 # measurement aids that are not part of the product (gather kernels of known geometry for the counter calibration, scripts/pmc_target.py)
 [ -f "$OUT/calibration.o" ] && $HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/calibration.o" -o "$OUT/libdsopp_hip_tools.so"

@@ -9,6 +9,7 @@
 // each thread regenerates from the parent plane (u8 + LUT at level 0, 2x2 means above) — reads are coalesced rows that
 // hit L2, writes are one full 16/32-byte texel per lane.  HBM-bound by construction: ~(1 + 4*sizeof(S)) bytes per pixel.
 #include "pyramid.hpp"
+#include "colour.hpp"
 #include "transform.hpp"
 #include "undistort.hpp"
 
@@ -421,7 +422,7 @@ int dsopp_hip_pyramid_build_device(dsopp_hip_pyramid *p, const void *image_dev, 
   return guarded([&] {
     if (!p || !image_dev) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
     p->sr.use();
-    p->has_undistorted = false;
+    p->has_undistorted = p->has_colour = false;
     const double *lut_dev = nullptr;
     if (lut256) {
       HIP_CHECK(hipMemcpyAsync(p->lut_dev.get(), lut256, 256 * sizeof(double), hipMemcpyHostToDevice, p->sr.stream));
@@ -547,7 +548,7 @@ int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_un
       p->distorted_bytes = n_in;
     }
     if (!p->undistorted_u8) p->undistorted_u8.alloc(n);
-    p->has_undistorted = false;
+    p->has_undistorted = p->has_colour = false;
     uploadImage(p, p->distorted_u8.get(), distorted_host, n_in);
     enqueueUndistort(u, p->distorted_u8.get(), p->undistorted_u8.get(), st);
     buildFromKeptImage(p, lut256, vignetting_host);
@@ -574,11 +575,71 @@ int dsopp_hip_pyramid_build_transformed(dsopp_hip_pyramid *p, const dsopp_hip_un
     if (!p->undistorted_u8) p->undistorted_u8.alloc(n);
     if (!untransformed_dev) untransformed_dev = p->undistorted_u8.get();
     if (!frame_dev) frame_dev = untransformed_dev;
-    p->has_undistorted = false;
+    p->has_undistorted = p->has_colour = false;
     uploadImage(p, frame_dev, frame_host, n_frame);
     if (u) enqueueUndistort(u, frame_dev, untransformed_dev, st);
     enqueueTransform(t, untransformed_dev, p->undistorted_u8.get(), kTransformLinear, st);
     buildFromKeptImage(p, lut256, vignetting_host);
+  });
+}
+
+int dsopp_hip_pyramid_build_colour(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const dsopp_hip_transformer *t, const uint8_t *bgr_host,
+                                   const double *lut256, const uint8_t *vignetting_host, int keep_colour) {
+  return guarded([&] {
+    if (!p || !bgr_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (u && u->sr.device != p->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter lives on device %d, the pyramid on %d", u->sr.device, p->sr.device);
+    if (t && t->sr.device != p->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the transformer lives on device %d, the pyramid on %d", t->sr.device, p->sr.device);
+    if (u && t && (u->out_w != t->in_w || u->out_h != t->in_h))
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the transformer reads %d x %d", u->out_w, u->out_h, t->in_w, t->in_h);
+    if (t && (t->out_w != p->width || t->out_h != p->height))
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the transformer writes %d x %d, the pyramid is %d x %d", t->out_w, t->out_h, p->width, p->height);
+    if (u && !t && (u->out_w != p->width || u->out_h != p->height))
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the undistorter writes %d x %d, the pyramid is %d x %d", u->out_w, u->out_h, p->width, p->height);
+    p->sr.use();
+    hipStream_t st = p->sr.stream;
+    const bool transforms = t && !t->identity();
+    const size_t n = static_cast<size_t>(p->width) * p->height;
+    const size_t n_frame = u ? static_cast<size_t>(u->in_w) * u->in_h : transforms ? static_cast<size_t>(t->in_w) * t->in_h : n;
+    // frame -> [remap] -> [resize + crop] -> grey (+ colour): the last stage that is there converts in its epilogue; with none the frame is
+    // uploaded where the colour image is kept and the plain conversion reads it there
+    uint8_t *colour_dev = keep_colour || !(u || transforms) ? reserveImage(p->colour_u8, p->colour_bytes, 3 * n, st) : nullptr;
+    if (!p->undistorted_u8) p->undistorted_u8.alloc(n);
+    uint8_t *grey_dev = p->undistorted_u8.get();
+    p->has_undistorted = p->has_colour = false;
+    if (u && transforms) {
+      uint8_t *frame_dev = reserveImage(p->distorted_u8, p->distorted_bytes, 3 * n_frame, st);
+      uint8_t *untransformed_dev = reserveImage(p->untransformed_u8, p->untransformed_bytes, 3 * static_cast<size_t>(t->in_w) * t->in_h, st);
+      uploadImage(p, frame_dev, bgr_host, 3 * n_frame);
+      enqueueUndistortBgr(u, frame_dev, untransformed_dev, nullptr, st);
+      enqueueTransformBgr(t, untransformed_dev, colour_dev, grey_dev, st);
+    } else if (u) {
+      uint8_t *frame_dev = reserveImage(p->distorted_u8, p->distorted_bytes, 3 * n_frame, st);
+      uploadImage(p, frame_dev, bgr_host, 3 * n_frame);
+      enqueueUndistortBgr(u, frame_dev, colour_dev, grey_dev, st);
+    } else if (transforms) {
+      uint8_t *frame_dev = reserveImage(p->untransformed_u8, p->untransformed_bytes, 3 * n_frame, st);
+      uploadImage(p, frame_dev, bgr_host, 3 * n_frame);
+      enqueueTransformBgr(t, frame_dev, colour_dev, grey_dev, st);
+    } else {
+      uploadImage(p, colour_dev, bgr_host, 3 * n);
+      enqueueBgrToGrey(colour_dev, grey_dev, n, st);
+    }
+    buildFromKeptImage(p, lut256, vignetting_host);
+    p->has_colour = keep_colour != 0;
+  });
+}
+
+int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out_host, int *present) {
+  return guarded([&] {
+    if (!p) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null pyramid");
+    if (channels != 1 && channels != 3) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d channels: 1 = the grey image, 3 = the colour image", channels);
+    const bool has = channels == 1 ? p->has_undistorted : p->has_colour;
+    if (present) *present = has ? 1 : 0;
+    if (!has || !out_host) return;
+    p->sr.use();
+    const uint8_t *image_dev = channels == 1 ? p->undistorted_u8.get() : p->colour_u8.get();
+    HIP_CHECK(hipMemcpyAsync(out_host, image_dev, channels * static_cast<size_t>(p->width) * p->height, hipMemcpyDeviceToHost, p->sr.stream));
+    p->sr.sync();
   });
 }
 
@@ -587,7 +648,7 @@ int dsopp_hip_pyramid_set_level(dsopp_hip_pyramid *p, int level, const double *p
     checkLevel(p, level);
     if (!pixelinfo_host) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null pixelinfo");
     p->sr.use();
-    p->has_undistorted = false;
+    p->has_undistorted = p->has_colour = false;
     const size_t n = static_cast<size_t>(p->w(level)) * p->h(level);
     DeviceMem<double> tmp;
     tmp.alloc(n * 3 * sizeof(double));

@@ -114,6 +114,13 @@ struct dsopp_hip_pyramid {
   dsopp_hip::DeviceMem<uint8_t> distorted_u8, undistorted_u8, untransformed_u8;
   size_t distorted_bytes = 0, untransformed_bytes = 0;
   bool has_undistorted = false;
+  // dsopp_hip_pyramid_build_colour: the frame arrives as 8-bit BGR.  distorted_u8 and untransformed_u8 then hold three bytes per pixel (they
+  // only ever grow), the grey conversion of the last stage's output is kept in undistorted_u8 under has_undistorted as above, and colour_u8
+  // is that output itself, kept on request (CameraFeatures::image()): has_colour.  Without a stage colour_u8 is where the frame is uploaded.
+  // Every other rewrite of the image clears has_colour as it clears has_undistorted.
+  dsopp_hip::DeviceMem<uint8_t> colour_u8;
+  size_t colour_bytes = 0;
+  bool has_colour = false;
   // dsopp_hip_pyramid_set_semantics (semantics.hip): the frame's class image as uploaded (only with an undistorter; sized by the first
   // call) and undistorted (semanticsData of the frame: the window's class observations read it), and the level-0 mask as bytes
   // (dsopp_hip_feature_extractor_set_mask_from_pyramid erodes it).  All read behind waitReady().  The class image leaves from a pinned

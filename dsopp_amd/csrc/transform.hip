@@ -32,17 +32,14 @@ namespace dsopp_hip {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kCoefBits = 11;  // INTER_RESIZE_COEF_BITS
-constexpr int kCoefOne = 1 << kCoefBits;
-constexpr unsigned kWeightMask = 0xfffu, kFirstWeightShift = 12, kStep = 1u << 24;
 constexpr int kMaxCropLevels = 8;
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned transformPixel(GlobalPtr<const uint8_t> src, unsigned in_w, u32x2 col, u32x2 row) {
-  const int a1 = col.y & kWeightMask, a0 = (col.y >> kFirstWeightShift) & kWeightMask;
-  const int b1 = row.y & kWeightMask, b0 = (row.y >> kFirstWeightShift) & kWeightMask;
-  const unsigned dx = (col.y & kStep) ? 1u : 0u, dy = (row.y & kStep) ? in_w : 0u;
+  const int a1 = col.y & kResizeWeightMask, a0 = (col.y >> kResizeFirstWeightShift) & kResizeWeightMask;
+  const int b1 = row.y & kResizeWeightMask, b0 = (row.y >> kResizeFirstWeightShift) & kResizeWeightMask;
+  const unsigned dx = (col.y & kResizeStep) ? 1u : 0u, dy = (row.y & kResizeStep) ? in_w : 0u;
   GlobalPtr<const uint8_t> p = src + (row.x + col.x);
   const int p00 = p[0], p01 = p[dx], p10 = p[dy], p11 = p[dx + dy];
   const int r0 = a0 * p00 + a1 * p01, r1 = a0 * p10 + a1 * p11;
@@ -103,7 +100,7 @@ Sizes transformedSizes(int in_w, int in_h, double ratio, int crop_levels) {
 }
 
 uint32_t packWeights(int first, int second, bool step) {
-  return static_cast<uint32_t>(second) | (static_cast<uint32_t>(first) << kFirstWeightShift) | (step ? kStep : 0u);
+  return static_cast<uint32_t>(second) | (static_cast<uint32_t>(first) << kResizeFirstWeightShift) | (step ? kResizeStep : 0u);
 }
 
 /** the entries of the first n_out of n_resized output indices of one axis; `stride` = 1 for columns, in_w for rows */
@@ -111,7 +108,7 @@ void axisTable(int n_in, int n_resized, int n_out, int interpolation, uint32_t s
 #pragma clang fp contract(off)  // every product and sum below rounds on its own, as in cv::resize
   const double scale = 1.0 / (static_cast<double>(n_resized) / n_in);
   for (int d = 0; d < n_out; ++d) {
-    int s, first = kCoefOne, second = 0;
+    int s, first = kResizeCoefOne, second = 0;
     if (interpolation == kTransformNearest) {
       s = static_cast<int>(std::min<double>(std::floor(d * scale), n_in - 1));
     } else {

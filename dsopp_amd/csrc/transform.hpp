@@ -17,6 +17,10 @@ struct dsopp_hip_transformer {
 
 namespace dsopp_hip {
 constexpr int kTransformLinear = 0, kTransformNearest = 1;
+// the table entry's second word (transform.hip: the entry's layout), shared with the colour kernels of colour.hip
+constexpr int kResizeCoefBits = 11;  // INTER_RESIZE_COEF_BITS
+constexpr int kResizeCoefOne = 1 << kResizeCoefBits;
+constexpr unsigned kResizeWeightMask = 0xfffu, kResizeFirstWeightShift = 12, kResizeStep = 1u << 24;
 /** enqueue resize + crop of `in_dev` (in_w x in_h bytes) into `out_dev` (out_w x out_h bytes) on `stream`; both 4-byte aligned.  The
  *  identity is a device-to-device copy (none at all when in_dev == out_dev). */
 void enqueueTransform(const dsopp_hip_transformer *t, const uint8_t *in_dev, uint8_t *out_dev, int interpolation, hipStream_t stream);

@@ -30,22 +30,19 @@ namespace dsopp_hip {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kFractionBits = 5;  // INTER_BITS
-constexpr int kOne = 1 << kFractionBits;
-constexpr unsigned kFyShift = 8, kFlipX = 1u << 16, kFlipY = 1u << 17;
 constexpr float kMaxCoordinate = 1048576.0f;  // 2^20: 32 * coordinate stays far inside int32
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned remapPixel(GlobalPtr<const uint8_t> src, int in_w, unsigned offset, unsigned bits) {
-  const int fx = bits & (kOne - 1), fy = (bits >> kFyShift) & (kOne - 1);
-  const int dx = (bits & kFlipX) ? -1 : 1;
-  const int dy = (bits & kFlipY) ? -in_w : in_w;
+  const int fx = bits & (kRemapOne - 1), fy = (bits >> kRemapFyShift) & (kRemapOne - 1);
+  const int dx = (bits & kRemapFlipX) ? -1 : 1;
+  const int dy = (bits & kRemapFlipY) ? -in_w : in_w;
   GlobalPtr<const uint8_t> p = src + offset;
   const int p00 = p[0], p01 = p[dx], p10 = p[dy], p11 = p[dx + dy];
-  const int gx = kOne - fx, gy = kOne - fy;
-  const int sum = gx * gy * kOne * p00 + fx * gy * kOne * p01 + gx * fy * kOne * p10 + fx * fy * kOne * p11;
+  const int gx = kRemapOne - fx, gy = kRemapOne - fy;
+  const int sum = gx * gy * kRemapOne * p00 + fx * gy * kRemapOne * p01 + gx * fy * kRemapOne * p10 + fx * fy * kRemapOne * p11;
   return static_cast<unsigned>((sum + 16384) >> 15);
 }
 
@@ -79,8 +76,8 @@ int reflect101(long c, int n) {
 /** one map coordinate -> the two reflected tap coordinates and the 5-bit fraction */
 void splitCoordinate(float c, int n, int &c0, int &c1, int &fraction) {
   const long s = std::lrintf(c * 32.0f);  // exact product, rounded half to even (cvRound)
-  const long i = s >> kFractionBits;       // arithmetic shift: the floor, also below zero
-  fraction = static_cast<int>(s & (kOne - 1));
+  const long i = s >> kRemapFractionBits;       // arithmetic shift: the floor, also below zero
+  fraction = static_cast<int>(s & (kRemapOne - 1));
   c0 = reflect101(i, n);
   c1 = reflect101(i + 1, n);
 }
@@ -131,7 +128,7 @@ int dsopp_hip_undistorter_create(int device, void *stream, int in_w, int in_h, i
       splitCoordinate(cx, in_w, x0, x1, fx);
       splitCoordinate(cy, in_h, y0, y1, fy);
       table[2 * i] = static_cast<uint32_t>(y0) * static_cast<uint32_t>(in_w) + static_cast<uint32_t>(x0);
-      table[2 * i + 1] = static_cast<uint32_t>(fx) | (static_cast<uint32_t>(fy) << kFyShift) | (x1 < x0 ? kFlipX : 0u) | (y1 < y0 ? kFlipY : 0u);
+      table[2 * i + 1] = static_cast<uint32_t>(fx) | (static_cast<uint32_t>(fy) << kRemapFyShift) | (x1 < x0 ? kRemapFlipX : 0u) | (y1 < y0 ? kRemapFlipY : 0u);
     }
     auto u = std::make_unique<dsopp_hip_undistorter>();
     u->sr.init(device, stream);

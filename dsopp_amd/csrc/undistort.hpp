@@ -12,6 +12,10 @@ struct dsopp_hip_undistorter {
 };
 
 namespace dsopp_hip {
+// the table entry's second word (undistort.hip: the entry's layout), shared with the colour kernels of colour.hip
+constexpr int kRemapFractionBits = 5;  // INTER_BITS
+constexpr int kRemapOne = 1 << kRemapFractionBits;
+constexpr unsigned kRemapFyShift = 8, kRemapFlipX = 1u << 16, kRemapFlipY = 1u << 17;
 /** enqueue the remap of `in_dev` (in_w x in_h bytes) into `out_dev` (out_w x out_h bytes, 4-byte aligned) on `stream` */
 void enqueueUndistort(const dsopp_hip_undistorter *u, const uint8_t *in_dev, uint8_t *out_dev, hipStream_t stream);
 }  // namespace dsopp_hip

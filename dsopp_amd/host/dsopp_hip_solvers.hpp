@@ -73,6 +73,11 @@ class HipUndistorter {
   void undistortDevice(const void *image_dev, void *out_dev, void *stream = nullptr) const {
     check(dsopp_hip_undistorter_undistort_device(u_, image_dev, out_dev, stream));
   }
+  /** undistort(img) of an 8-bit BGR frame (CV_8UC3, interleaved; any alignment) between device images, as camera.cpp:70 calls it: the
+   *  colour result, its grey conversion (camera_features.cpp:32), or both — nullptr = not wanted; outputs 4-byte aligned; only enqueues */
+  void undistortBgrDevice(const void *bgr_in_dev, void *bgr_out_dev, void *grey_out_dev, void *stream = nullptr) const {
+    check(dsopp_hip_undistorter_undistort_bgr_device(u_, bgr_in_dev, bgr_out_dev, grey_out_dev, stream));
+  }
   const dsopp_hip_undistorter *handle() const { return u_; }
 
  private:
@@ -118,6 +123,11 @@ class HipImageTransformer {
   /** either between two 4-byte aligned device images (interpolation 0 = linear, 1 = nearest); only enqueues on `stream` */
   void transformDevice(const void *in_dev, void *out_dev, int interpolation, void *stream = nullptr) const {
     check(dsopp_hip_transformer_transform_device(t_, in_dev, out_dev, interpolation, stream));
+  }
+  /** runImageTransformers (linear) of an 8-bit BGR frame (CV_8UC3, interleaved; any alignment) between device images: the colour result,
+   *  its grey conversion (camera_features.cpp:32), or both — nullptr = not wanted; outputs 4-byte aligned; only enqueues */
+  void transformBgrDevice(const void *bgr_in_dev, void *bgr_out_dev, void *grey_out_dev, void *stream = nullptr) const {
+    check(dsopp_hip_transformer_transform_bgr_device(t_, bgr_in_dev, bgr_out_dev, grey_out_dev, stream));
   }
   const dsopp_hip_transformer *handle() const { return t_; }
 
@@ -177,6 +187,26 @@ class DevicePyramid {
                         const double *photometric_calibration256 = nullptr, const uint8_t *transformed_vignetting = nullptr) {
     check(dsopp_hip_pyramid_build_transformed(p_, undistorter ? undistorter->handle() : nullptr, transformer.handle(), frame,
                                               photometric_calibration256, transformed_vignetting));
+  }
+  /** the same for the 8-bit BGR frame a colour provider delivers (camera_fabric.cpp:35): all three channels go through the remap and the
+   *  transformers (either may be nullptr) and the grey conversion of the CameraFeatures ctor comes last (camera_features.cpp:32);
+   *  keep_colour: the transformed colour image stays on the device for image(3, ...), as CameraFeatures::image() keeps it */
+  void buildColour(const HipUndistorter *undistorter, const HipImageTransformer *transformer, const uint8_t *bgr_frame,
+                   const double *photometric_calibration256 = nullptr, const uint8_t *transformed_vignetting = nullptr, bool keep_colour = false) {
+    check(dsopp_hip_pyramid_build_colour(p_, undistorter ? undistorter->handle() : nullptr, transformer ? transformer->handle() : nullptr, bgr_frame,
+                                         photometric_calibration256, transformed_vignetting, keep_colour ? 1 : 0));
+  }
+  /** the 8-bit image the pyramid keeps: channels = 1 CameraFeatures::frameData() (behind buildUndistorted, buildTransformed and
+   *  buildColour), channels = 3 CameraFeatures::image() (behind buildColour with keep_colour); false, and `out` untouched, when it keeps
+   *  none.  Blocking. */
+  bool image(int channels, std::vector<uint8_t> &out) const {
+    int present = 0, width = 0, height = 0;
+    check(dsopp_hip_pyramid_get_image(p_, channels, nullptr, &present));
+    if (!present) return false;
+    check(dsopp_hip_pyramid_level_size(p_, 0, &width, &height));
+    out.resize(static_cast<size_t>(channels) * static_cast<size_t>(width) * static_cast<size_t>(height));
+    check(dsopp_hip_pyramid_get_image(p_, channels, out.data(), &present));
+    return present != 0;
   }
   /** adopt a PixelMap<1> level built on the host by the reference */
   void setLevel(int level, const double *pixelinfo) { check(dsopp_hip_pyramid_set_level(p_, level, pixelinfo)); }

@@ -58,6 +58,15 @@ bool trackerCallOrder(const std::vector<int> &devices, std::vector<double> *fina
     images.push_back(render(tx_gt));
     pyramids.push_back(std::make_unique<DevicePyramid>(W, H, 1));
     pyramids.back()->build(images.back().data());
+    if (i == 0) {
+      // the same frame as a colour provider delivers it (camera_fabric.cpp:35), here B = G = R: the grey image the pyramid keeps is the
+      // frame again, and the colour image stays with it as CameraFeatures::image() does
+      std::vector<uint8_t> bgr(3 * images.back().size()), grey, colour;
+      for (size_t k = 0; k < bgr.size(); ++k) bgr[k] = images.back()[k / 3];
+      DevicePyramid colour_pyramid(W, H, 1);
+      colour_pyramid.buildColour(nullptr, nullptr, bgr.data(), nullptr, nullptr, true);
+      ok = ok && colour_pyramid.image(1, grey) && grey == images.back() && colour_pyramid.image(3, colour) && colour == bgr;
+    }
     if (sharded) {
       pyramid_groups.push_back(std::make_unique<DevicePyramidGroup>(pba.group(), W, H, 1));
       pyramid_groups.back()->build(images.back().data());

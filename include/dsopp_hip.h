@@ -206,6 +206,55 @@ int dsopp_hip_pyramid_build_transformed(dsopp_hip_pyramid *p, const dsopp_hip_un
                                         const double *lut256, const uint8_t *vignetting_host);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Colour frames: the camera delivers 8-bit BGR (the image provider is created with read_grayscale = false —
+ * src/sensors/sensors_builder/src/camera_fabric.cpp:35 — so cv::imread and cv::VideoCapture::read hand over CV_8UC3), the frame is
+ * undistorted and transformed in colour (src/sensors/camera/src/camera.cpp:70) and converted to grey last, by the CameraFeatures ctor
+ * (cv::cvtColor(raw_image_, frame_data_, cv::COLOR_BGR2GRAY), src/features/src/camera_features.cpp:32); the colour image stays with the
+ * frame (CameraFeatures::image(), camera_features.cpp:49; src/tracker/tracker/src/monocular_tracker.cpp:63,460,493).
+ * An image here is a continuous CV_8UC3 Mat: 3 * w * h bytes, interleaved, channel c (0 = B, 1 = G, 2 = R) of pixel o at byte 3 * o + c.
+ * The arithmetic is integer and fixed here:
+ *   remap and resize + crop are the single-channel statements of dsopp_hip_undistorter_create and dsopp_hip_transformer_create (linear)
+ *   applied to B, G and R on their own — coordinates, reflection and weights are shared between the channels, as cv::remap and cv::resize
+ *   share them for CV_8UC3 — each rounded to 8 bits as stated there; the handles' device tables are used as they are;
+ *   grey = (3735 * B + 19235 * G + 9798 * R + 16384) >> 15 of the 8-bit result of the last stage (the 15-bit fixed point of OpenCV 4's
+ *   8-bit BGR2GRAY; the weights sum to 32768, so (v, v, v) -> v, and pure blue, green and red give 29, 150 and 76).  It is within 0.505
+ *   of 0.114 B + 0.587 G + 0.299 R.  The 14-bit form of OpenCV 3 (1868, 9617, 4899) is not built.
+ * Converting last is not converting first: after a resize about a quarter of the grey bytes differ by one level between the two orders.
+ * Not built: RGB, BGRA and planar layouts, 16-bit images, dsopp_hip_pyramid_group_* forms.  The class image, the static mask and the
+ * vignette are single-channel in the reference and stay on the entry points above.
+ * ---------------------------------------------------------------------------------------------------------------- */
+/* Undistorter::undistort of a CV_8UC3 frame (undistorter.cpp:7-18 as camera.cpp:70 calls it), both images in HBM: the call only
+ * enqueues one launch on `stream` (a hipStream_t; NULL = the undistorter's own).  bgr_out_dev (3 * out_w * out_h bytes) takes the
+ * remapped colour image, grey_out_dev (out_w * out_h bytes) its grey conversion (camera_features.cpp:32); either may be NULL, both NULL
+ * or a NULL input is DSOPP_HIP_ERR_INVALID_ARGUMENT, and so is an output that is not 4-byte aligned.  The input may have any alignment. */
+int dsopp_hip_undistorter_undistort_bgr_device(dsopp_hip_undistorter *u, const void *bgr_in_dev, void *bgr_out_dev, void *grey_out_dev, void *stream);
+/* runImageTransformers of a CV_8UC3 frame (camera.cpp:70; camera_resizer.cpp:12, image_cropper.cpp:12), linear interpolation only, with
+ * the same conventions.  A transformer with nothing to do enqueues the plain conversion for grey_out_dev and one copy for bgr_out_dev
+ * (none when it is the input). */
+int dsopp_hip_transformer_transform_bgr_device(dsopp_hip_transformer *t, const void *bgr_in_dev, void *bgr_out_dev, void *grey_out_dev, void *stream);
+/* The per-frame path for a colour camera, camera.cpp:70 followed by the CameraFeatures and PixelDataFrame ctors
+ * (camera_features.cpp:19-47): dsopp_hip_pyramid_build of BGR2GRAY(runImageTransformers(undistort(bgr_host))).  u and t may each be
+ * NULL (frames arrive undistorted / there is no transformer list); the frame has u's input size, else t's, else the pyramid's.  The
+ * 3 * w * h bytes go through the pyramid's pinned buffer in pieces as in build; on the pyramid's stream follow at most two launches —
+ * with u and a t that has work the remap BGR -> BGR and the resize + crop BGR -> grey; with one of them that stage BGR -> grey; with
+ * neither the plain conversion — and the level build.  The conversion is the last stage's epilogue, never a pass of its own behind a
+ * stage.  The call does not wait, unless lut256 or vignetting_host is given (they are read straight from the caller's arrays, as in
+ * build_transformed; vignetting_host is the single-channel vignette already undistorted and transformed).  The pyramid keeps the grey
+ * image as build_transformed keeps its image (dsopp_hip_feature_extractor_extract_from_pyramid and _set_mask_from_pyramid work
+ * unchanged) and, with keep_colour != 0, the transformed colour image too (without a stage that is the uploaded frame itself: no
+ * copy).  f64 and f32 pyramids.  DSOPP_HIP_ERR_INVALID_ARGUMENT: a NULL frame, handles on different devices, u not writing t's input
+ * size, the last stage not writing the pyramid's size. */
+int dsopp_hip_pyramid_build_colour(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const dsopp_hip_transformer *t, const uint8_t *bgr_host,
+                                   const double *lut256, const uint8_t *vignetting_host, int keep_colour);
+/* The 8-bit image the pyramid keeps, blocking.  channels = 1: the grey image the levels were built from (CameraFeatures::frameData(),
+ * camera_features.cpp:51), width * height bytes, kept by build_undistorted, build_transformed and build_colour.  channels = 3: the
+ * colour image (CameraFeatures::image(), camera_features.cpp:49), 3 * width * height bytes, kept by build_colour with keep_colour.
+ * *present = 0 and out_host untouched when the pyramid keeps no such image: after build, build_device, set_level — every other
+ * rewrite of the image drops both — and channels = 3 after any build but a build_colour with keep_colour.  Other values of channels
+ * are DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out_host, int *present);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
  * image — src/sensors/camera/src/camera.cpp:57-65 —, CameraMask::filterSemanticObjects —
  * src/sensors/camera_calibration/src/camera_mask.cpp:31-39 — and the mask pyramid of src/features/src/camera_features.cpp:71-84; the
