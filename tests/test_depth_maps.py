@@ -206,6 +206,22 @@ def test_gpu_depth_maps_and_device_scan():
         assert np.abs(wgt - ww).max() <= 1e-6 * np.abs(ww).max(), lvl   # weights carry H_dd^-1 of the GPU / CPU solves (1e-9 .. 1e-7 apart)
         assert np.abs(ids - wi).max() <= 1e-6 * np.abs(wi).max(), lvl
     assert (want[0][1] > 0).sum() > 300
+    # ... and against the NumPy statement fed with what the splat itself reads — landmarks, flags, variances, statuses and poses from the HIP
+    # window's own getters: no difference between two solves enters, only the order of the atomic additions is left
+    import depth_maps_model as dm
+    newest_id = win.frames[-1].frame_id
+    own = []
+    for f in win.frames[:-1]:
+        lm = g.get_landmarks(f.frame_id, with_hpib=False)
+        own.append(dict(T_w=g.get_pose(f.frame_id)[0], uv=f.uv, idepth=lm["idepth"], flags=lm["flags"], status=g.get_residuals(f.frame_id, newest_id)["status"],
+                        variance=lm["inv_hdd"] if g.options.estimate_uncertainty else dm.CONSTANT_VARIANCE))
+    exact, s = dm.depth_maps(own, g.get_pose(newest_id)[0], win.scene.intrinsics, W, H, L)
+    assert s.ambiguous == 0
+    for lvl in range(L):
+        ids, wgt = maps.get_level(lvl)
+        assert np.array_equal(wgt > 0, exact[lvl][1] > 0), lvl
+        assert np.abs(wgt - exact[lvl][1]).max() <= 1e-12 * np.abs(exact[lvl][1]).max(), lvl
+        assert np.abs(ids - exact[lvl][0]).max() <= 1e-12 * np.abs(exact[lvl][0]).max(), lvl
     # tracker side: device scan of a level == host scan of the same (downloaded) level
     newest = win.frames[-1]
     pyr = capi.Pyramid(W, H, L)
