@@ -79,6 +79,10 @@ SYMBOLS = [
     "dsopp_hip_pyramid_build_transformed", "dsopp_hip_semantics_create_transformed",
     "dsopp_hip_undistorter_undistort_bgr_device", "dsopp_hip_transformer_transform_bgr_device", "dsopp_hip_pyramid_build_colour",
     "dsopp_hip_pyramid_get_image",
+    "dsopp_hip_flow_tracker_create", "dsopp_hip_flow_tracker_destroy", "dsopp_hip_flow_tracker_num_levels",
+    "dsopp_hip_flow_tracker_set_reference", "dsopp_hip_flow_tracker_set_reference_device", "dsopp_hip_flow_tracker_set_reference_from_pyramid",
+    "dsopp_hip_flow_tracker_track", "dsopp_hip_flow_tracker_track_device", "dsopp_hip_flow_tracker_track_from_pyramid",
+    "dsopp_hip_flow_tracker_get_level",
 ]
 
 _lib = None
@@ -436,6 +440,90 @@ class Pyramid:
         out = np.zeros((h, w, 3))
         _chk(lib().dsopp_hip_pyramid_get_level(self._h, int(level), _p(out)))
         return out
+
+
+class OpticalFlowTracker:
+    """features::OpticalFlowMatch's cv::calcOpticalFlowPyrLK on the device (dsopp_hip_flow_tracker): the reference image's levels and
+    Scharr planes are kept, every track() builds the new frame's levels and tracks all points in one launch.  Images are (height, width)
+    uint8 arrays (any row stride), device addresses as integers, or a Pyramid that keeps its 8-bit grey image."""
+
+    def __init__(self, width, height, window=15, max_level=3, max_iterations=10, epsilon=0.01, min_eig_threshold=1e-4, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.window, self.device = int(width), int(height), int(window), device
+        _chk(lib().dsopp_hip_flow_tracker_create(int(width), int(height), int(window), int(max_level), int(max_iterations), C.c_double(epsilon),
+                                                 C.c_double(min_eig_threshold), int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+        n = C.c_int()
+        _chk(lib().dsopp_hip_flow_tracker_num_levels(self._h, C.byref(n)))
+        self.num_levels = n.value
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_flow_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _image(self, image):
+        """a host image as (pointer, row stride in bytes); rows must be contiguous"""
+        img = np.asarray(image)
+        assert img.dtype == np.uint8 and img.shape == (self.height, self.width), (img.dtype, img.shape)
+        if img.strides[1] != 1 or img.strides[0] < self.width:
+            img = np.ascontiguousarray(img)
+        return img, img.ctypes.data_as(C.c_void_p), C.c_size_t(img.strides[0])
+
+    def set_reference(self, image):
+        """image_from: builds and keeps its levels and derivative planes; only enqueues"""
+        if isinstance(image, Pyramid):
+            _chk(lib().dsopp_hip_flow_tracker_set_reference_from_pyramid(self._h, image._h))
+            return
+        img, ptr, stride = self._image(image)
+        _chk(lib().dsopp_hip_flow_tracker_set_reference(self._h, ptr, stride))
+
+    def set_reference_device(self, image_ptr, stride=None):
+        _chk(lib().dsopp_hip_flow_tracker_set_reference_device(self._h, C.c_void_p(image_ptr), C.c_size_t(self.width if stride is None else stride)))
+
+    def _outputs(self, points_from, with_iterations):
+        pts = np.ascontiguousarray(points_from, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        out = (np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.float32),
+               np.zeros((n, self.num_levels), np.int32) if with_iterations else None)
+        args = (n, _p(pts, np.float32), _p(out[0], np.float32), _p(out[1], np.uint8), _p(out[2], np.float32), _p(out[3], np.int32))
+        return pts, out, args
+
+    def track(self, image, points_from, with_iterations=False):
+        """calcOpticalFlowPyrLK(reference, image, points_from): (points_to (n, 2) float32, status (n,) uint8, err (n,) float32), and with
+        with_iterations the (n, num_levels) int32 passes per level; blocking"""
+        pts, out, args = self._outputs(points_from, with_iterations)
+        if isinstance(image, Pyramid):
+            _chk(lib().dsopp_hip_flow_tracker_track_from_pyramid(self._h, image._h, *args))
+        else:
+            img, ptr, stride = self._image(image)
+            _chk(lib().dsopp_hip_flow_tracker_track(self._h, ptr, stride, *args))
+        return out if with_iterations else out[:3]
+
+    def track_device(self, image_ptr, points_from, stride=None, with_iterations=False):
+        pts, out, args = self._outputs(points_from, with_iterations)
+        _chk(lib().dsopp_hip_flow_tracker_track_device(self._h, C.c_void_p(image_ptr), C.c_size_t(self.width if stride is None else stride), *args))
+        return out if with_iterations else out[:3]
+
+    def level_size(self, level):
+        w, h = self.width, self.height
+        for _ in range(level):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        return w, h
+
+    def get_level(self, which, level, with_derivatives=False):
+        """level `level` of the reference (which = 0) or of the last tracked frame (1): (h, w) uint8, and of the reference its
+        Scharr plane (h, w, 2) int16 (dx, dy)"""
+        w, h = self.level_size(level)
+        img = np.zeros((h, w), np.uint8)
+        der = np.zeros((h, w, 2), np.int16) if with_derivatives else None
+        _chk(lib().dsopp_hip_flow_tracker_get_level(self._h, int(which), int(level), _p(img, np.uint8), _p(der, np.int16)))
+        return (img, der) if with_derivatives else img
 
 
 class DepthMaps:

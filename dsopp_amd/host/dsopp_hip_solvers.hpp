@@ -972,4 +972,70 @@ class HipLandmarksActivator {
   dsopp_hip_activation_result last_{};
 };
 
+/** features::Correspondence (feature_based_slam/features/correspondence.hpp:12-19) */
+struct FlowCorrespondence {
+  bool is_inlier;
+  size_t idx_from, idx_to;
+};
+
+/** features::OpticalFlowMatch (src/feature_based_slam/features/src/optical_flow.cpp:11-42) on the device, its Lucas-Kanade half: the
+ *  features of frame_from tracked into image_to by cv::calcOpticalFlowPyrLK(..., Size(15, 15), 3, TermCriteria(COUNT + EPS, 10, 0.01)),
+ *  a feature and a correspondence {true, i, features.size() - 1} for every status != 0, in the order of frame_from.  image_from is the
+ *  first track frame for the whole bootstrap (monocular_initializer.cpp:47-51), so it is set once and its levels stay on the device.
+ *  The refill from a fresh ORB extraction (optical_flow.cpp:44-53) stays with the caller. */
+class HipOpticalFlowMatch {
+ public:
+  struct Result {
+    std::vector<std::array<float, 2>> features;  // DistinctFeature coordinates in image_to
+    std::vector<FlowCorrespondence> correspondences;
+  };
+  HipOpticalFlowMatch(int width, int height, int device = 0, void *stream = nullptr) : width_(width) {
+    check(dsopp_hip_flow_tracker_create(width, height, 15, 3, 10, 0.01, 1e-4, device, stream, &t_));
+  }
+  ~HipOpticalFlowMatch() { dsopp_hip_flow_tracker_destroy(t_); }
+  HipOpticalFlowMatch(const HipOpticalFlowMatch &) = delete;
+  HipOpticalFlowMatch &operator=(const HipOpticalFlowMatch &) = delete;
+  /** image_from as a continuous 8-bit Mat, or the grey image a pyramid keeps (CameraFeatures::frameData()) */
+  void setImageFrom(const uint8_t *image_from) { check(dsopp_hip_flow_tracker_set_reference(t_, image_from, static_cast<size_t>(width_))); }
+  void setImageFrom(const DevicePyramid &frame_from) { check(dsopp_hip_flow_tracker_set_reference_from_pyramid(t_, frame_from.handle())); }
+  /** features_from: (x, y) per feature of frame_from */
+  Result match(const std::vector<std::array<float, 2>> &features_from, const uint8_t *image_to) {
+    prepare(features_from.size());
+    check(dsopp_hip_flow_tracker_track(t_, image_to, static_cast<size_t>(width_), static_cast<int>(features_from.size()), flat(features_from),
+                                       to_.data(), status_.data(), err_.data(), nullptr));
+    return collect(features_from.size());
+  }
+  Result match(const std::vector<std::array<float, 2>> &features_from, const DevicePyramid &frame_to) {
+    prepare(features_from.size());
+    check(dsopp_hip_flow_tracker_track_from_pyramid(t_, frame_to.handle(), static_cast<int>(features_from.size()), flat(features_from), to_.data(),
+                                                    status_.data(), err_.data(), nullptr));
+    return collect(features_from.size());
+  }
+  /** status and err of the last match, per feature of frame_from */
+  const std::vector<uint8_t> &status() const { return status_; }
+  const std::vector<float> &error() const { return err_; }
+  dsopp_hip_flow_tracker *handle() const { return t_; }
+
+ private:
+  static const float *flat(const std::vector<std::array<float, 2>> &v) { return v.empty() ? nullptr : v.front().data(); }
+  void prepare(size_t n) {
+    to_.assign(2 * n, 0.0f);
+    status_.assign(n, 0);
+    err_.assign(n, 0.0f);
+  }
+  Result collect(size_t n) const {
+    Result r;
+    for (size_t i = 0; i < n; ++i) {
+      if (status_[i] == 0) continue;
+      r.features.push_back({to_[2 * i], to_[2 * i + 1]});
+      r.correspondences.push_back({true, i, r.features.size() - 1});
+    }
+    return r;
+  }
+  dsopp_hip_flow_tracker *t_ = nullptr;
+  int width_;
+  std::vector<float> to_, err_;
+  std::vector<uint8_t> status_;
+};
+
 }  // namespace dsopp_hip_host

@@ -255,6 +255,82 @@ int dsopp_hip_pyramid_build_colour(dsopp_hip_pyramid *p, const dsopp_hip_undisto
 int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out_host, int *present);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Optical flow of the bootstrap: pyramidal Lucas-Kanade tracking of the first frame's features into every new frame (replaces the
+ * cv::calcOpticalFlowPyrLK(image_from, image_to, pts_from, pts_to, status, err, Size(15, 15), 3, TermCriteria(COUNT + EPS, 10, 0.01))
+ * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
+ * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
+ * Not built: the refill of lost features from a fresh ORB extraction (optical_flow.cpp:44-53) and ORB itself, estimateSO3inlierCount,
+ * initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ *
+ * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
+ * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
+ * in float in raster order (its SIMD paths in other orders); the exact integer sums below are the order-free statement of those, so
+ * parity with OpenCV itself is not pinned.  win = the window side, half = (win - 1) * 0.5f, reflect = BORDER_REFLECT_101,
+ * DESCALE(x, n) = (x + (1 << (n - 1))) >> n (arithmetic), rn = round to nearest, ties to even; every float step is one IEEE binary32
+ * operation in the written order, never fused; division and square root are correctly rounded.
+ *   Levels: level 0 is the image; level l + 1 is ((w + 1) / 2) x ((h + 1) / 2), pyrDown of level l: r = s[2x-2] + s[2x+2] +
+ *     4 (s[2x-1] + s[2x+1]) + 6 s[2x] along rows, the same taps over rows 2y-2 .. 2y+2 of r, (sum + 128) >> 8, source indices reflected.
+ *     After level l the size is halved; a halved width or height <= win makes l the last level, and there are at most max_level + 1.
+ *   Scharr planes of the reference's levels, int16 pairs: t0 = (s[y-1][x] + s[y+1][x]) * 3 + s[y][x] * 10, t1 = s[y+1][x] - s[y-1][x],
+ *     dx = t0[x+1] - t0[x-1], dy = (t1[x+1] + t1[x-1]) * 3 + t1[x] * 10, neighbours reflected.
+ *   Window sample at integer origin (ix, iy) and f32 fractions (a, b): iw00 = rn((1-a)(1-b) * 16384), iw01 = rn(a (1-b) * 16384),
+ *     iw10 = rn((1-a) b * 16384), iw11 = 16384 - iw00 - iw01 - iw10; v = p[y][x] iw00 + p[y][x+1] iw01 + p[y+1][x] iw10 + p[y+1][x+1] iw11
+ *     for 0 <= x, y < win at (ix + x, iy + y); an image plane is read through reflect, a derivative plane reads 0 outside the level;
+ *     an intensity is DESCALE(v, 9) (5 fraction bits), a derivative DESCALE(v, 14).
+ *   Per point, from the top level down to 0, status = 1, err = 0, S = 2^-20:
+ *     1. prev = pt * 2^-level; next = prev at the top level, else 2 * the result of the level above; the result is next.
+ *     2. prev -= half, ip = floor(prev).  Range test: ip.x < -win || ip.x >= W_l || ip.y < -win || ip.y >= H_l: at level 0 status = 0,
+ *        err = 0; at any level go on with the next level.
+ *     3. I, Ix, Iy over the window at ip; A11, A12, A22 = (float)(the exact sum of Ix Ix, Ix Iy, Iy Iy) * S.
+ *     4. D = A11 A22 - A12 A12, minEig = (A22 + A11 - sqrt((A11 - A22)(A11 - A22) + 4 A12 A12)) / (float)(2 win win).
+ *        (double)minEig < min_eig_threshold || D < FLT_EPSILON: at level 0 status = 0; at any level go on with the next level.  D = 1 / D.
+ *     5. next -= half, prevDelta = 0; for j < max_iterations: in = floor(next); the range test on `in` (at level 0 status = 0) ends the
+ *        loop; diff = DESCALE(J sample at in, 9) - I; b1, b2 = (float)(the exact sum of diff Ix, diff Iy) * S;
+ *        delta = ((A12 b2 - A22 b1) D, (A12 b1 - A11 b2) D); next += delta; result = next + half;
+ *        (double)dx dx + (double)dy dy <= epsilon^2 (in double) ends the loop; so does, for j > 0, fabs(delta + prevDelta) < 0.01 on both
+ *        axes (the sums in float), after result -= delta * 0.5f; prevDelta = delta.
+ *     6. at level 0 with status 1: q = result - half; the range test on floor(q) gives status = 0, else
+ *        err = (float)(the exact sum of |DESCALE(J sample at q, 9) - I|) / (float)(32 win win).
+ *   A coordinate that is not finite fails the range test.  max_iterations is clamped to 0 .. 100 and epsilon to 0 .. 10, as OpenCV does.
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_flow_tracker dsopp_hip_flow_tracker;
+/* The tracker of one image size.  The reference's values (optical_flow.cpp:19-22 and OpenCV's default minEigThreshold): window 15,
+ * max_level 3, max_iterations 10, epsilon 0.01, min_eig_threshold 1e-4.  `stream` is a hipStream_t (NULL = a stream of its own); all
+ * work of the object runs on it.  DSOPP_HIP_ERR_INVALID_ARGUMENT: an even window or one outside 3 .. 15, width or height < 2, max_level
+ * outside 0 .. 5, a threshold that is not a number. */
+int dsopp_hip_flow_tracker_create(int width, int height, int window, int max_level, int max_iterations, double epsilon, double min_eig_threshold,
+                                  int device, void *stream, dsopp_hip_flow_tracker **out);
+void dsopp_hip_flow_tracker_destroy(dsopp_hip_flow_tracker *t);
+/* the number of levels the stop rule above leaves for this size (buildOpticalFlowPyramid) */
+int dsopp_hip_flow_tracker_num_levels(const dsopp_hip_flow_tracker *t, int *n);
+/* image_from (optical_flow.cpp:30; the first track frame, monocular_initializer.cpp:47-51): its levels and Scharr planes are built once
+ * and kept, so every later frame costs one pyramid and one tracking launch.  `stride` = bytes between rows, >= width.  The host image
+ * is copied before the call returns, which only enqueues. */
+int dsopp_hip_flow_tracker_set_reference(dsopp_hip_flow_tracker *t, const uint8_t *image_host, size_t stride);
+/* same, the image already in HBM (any alignment): it is read on the tracker's stream, and has been read when the call returns */
+int dsopp_hip_flow_tracker_set_reference_device(dsopp_hip_flow_tracker *t, const void *image_dev, size_t stride);
+/* same, the 8-bit grey image `pyramid` keeps (CameraFeatures::frameData(), the image dsopp_hip_pyramid_get_image(p, 1, ...) returns),
+ * read behind the pyramid's build with no host copy.  DSOPP_HIP_ERR_STATE when the pyramid keeps none, DSOPP_HIP_ERR_INVALID_ARGUMENT
+ * when its size or device is not the tracker's. */
+int dsopp_hip_flow_tracker_set_reference_from_pyramid(dsopp_hip_flow_tracker *t, const dsopp_hip_pyramid *pyramid);
+/* calcOpticalFlowPyrLK(reference, image, points_from, ...) (optical_flow.cpp:30-31), blocking: points_from / points_to are n x 2 floats
+ * (x, y), status n bytes (1 = tracked), err n floats, iterations n x num_levels int32 or NULL — the passes of step 5 per level, there
+ * so that a divergence from the stated arithmetic can be located.  The results come back through one pinned buffer with one wait.
+ * n = 0 builds the target's levels only.  DSOPP_HIP_ERR_STATE before a reference was set. */
+int dsopp_hip_flow_tracker_track(dsopp_hip_flow_tracker *t, const uint8_t *image_host, size_t stride, int n, const float *points_from, float *points_to,
+                                 uint8_t *status, float *err, int32_t *iterations);
+/* same, the image in HBM / the grey image a pyramid keeps, with the conventions and errors of the set_reference twins */
+int dsopp_hip_flow_tracker_track_device(dsopp_hip_flow_tracker *t, const void *image_dev, size_t stride, int n, const float *points_from, float *points_to,
+                                        uint8_t *status, float *err, int32_t *iterations);
+int dsopp_hip_flow_tracker_track_from_pyramid(dsopp_hip_flow_tracker *t, const dsopp_hip_pyramid *pyramid, int n, const float *points_from,
+                                              float *points_to, uint8_t *status, float *err, int32_t *iterations);
+/* For tests, blocking: level `level` of the reference (which = 0) or of the last tracked frame (which = 1) as w_l x h_l dense bytes,
+ * and of the reference its Scharr plane as w_l x h_l (dx, dy) int16 pairs.  Either pointer may be NULL; deriv_out with which = 1 is
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT; DSOPP_HIP_ERR_STATE when that image was never set. */
+int dsopp_hip_flow_tracker_get_level(dsopp_hip_flow_tracker *t, int which, int level, uint8_t *image_out, int16_t *deriv_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
  * image — src/sensors/camera/src/camera.cpp:57-65 —, CameraMask::filterSemanticObjects —
  * src/sensors/camera_calibration/src/camera_mask.cpp:31-39 — and the mask pyramid of src/features/src/camera_features.cpp:71-84; the
