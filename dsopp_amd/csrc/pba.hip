@@ -112,6 +112,7 @@ struct dsopp_hip_window {
   bool twoStage() const { return deterministic || n_schur_blocks > twoStageMinChunks(); }
   DeviceMem<unsigned> d_bs_flag;  // ticket counter + hand-over buffers of the back-substitution inside the solve launch (pba_solve_combined.hpp)
   unsigned bs_seq = 0, bs_ticket_base = 0;
+  unsigned arrive_base = 0;  // what the reducers' arrival counter of the fused reduce + solve launches reads before the next such launch
   PinnedMem<int> h_bs_fault;  // raised by a landmark workgroup of the solve launch whose bounded wait for the step ran out (checkSolveLaunchFault)
   DeviceMem<long long> dbg_stamps;
   DeviceMem<long long> dbg_sweep;
@@ -1042,16 +1043,9 @@ constexpr size_t kDecideSmemBytes = size_t((6 * (kSchurThreads + 2) + 6 * 72) * 
 
 /** arguments of the LM decision (fusedDecideApply + applyDecision) when it runs as the prologue of another kernel */
 void launchTwoStage(W &w, const LmControl *ctrl, int ublk_parity, double lambda, bool dense, double *group_sums);
-void launchReduceSchur(W &w, bool for_marg, const LmControl *ctrl, const FusedReduce *fused = nullptr, ReduceMode mode = ReduceMode::kFused) {
-  const int K = w.K(), F = w.F();
-  hipStream_t st = w.sr.stream;
-  if (!fused && !for_marg && !ctrl && w.deterministic) {
-    // stage API / host-driven loop under dsopp_hip_window_set_deterministic: the four dense arrays without atomics
-    launchTwoStage(w, nullptr, 0, 0.0, true, nullptr);
-    allreduceIfNeeded(w, w.d_reduce.ptr, w.reduceCount());
-    return;
-  }
-  ensureDynamicLds(reinterpret_cast<const void *>(reduceSchurKernel), w.sr.device, 96 * 1024);
+/** the reduction launch's arguments (launchReduceSchur; launchReduceSolveFused runs the same body in a launch it shares with the solve) */
+ReduceSchurArgs makeReduceSchurArgs(W &w, bool for_marg, const LmControl *ctrl, const FusedReduce *fused, ReduceMode mode) {
+  const int F = w.F();
   ReduceSchurArgs a;
   a.frames = w.d_frames.ptr;
   a.pc = w.d_pc.ptr;
@@ -1092,6 +1086,22 @@ void launchReduceSchur(W &w, bool for_marg, const LmControl *ctrl, const FusedRe
   if (fused && fused->scalars) a.scalars = fused->scalars;
   a.ctrl_host = fused ? fused->ctrl_host : nullptr;
   a.dbg = w.dbg_stamps ? w.dbg_stamps.get() + 24 : nullptr;
+  return a;
+}
+
+void launchReduceSchur(W &w, bool for_marg, const LmControl *ctrl, const FusedReduce *fused = nullptr, ReduceMode mode = ReduceMode::kFused) {
+  const int K = w.K(), F = w.F();
+  hipStream_t st = w.sr.stream;
+  if (!fused && !for_marg && !ctrl && w.deterministic) {
+    // stage API / host-driven loop under dsopp_hip_window_set_deterministic: the four dense arrays without atomics
+    launchTwoStage(w, nullptr, 0, 0.0, true, nullptr);
+    allreduceIfNeeded(w, w.d_reduce.ptr, w.reduceCount());
+    return;
+  }
+  ensureDynamicLds(reinterpret_cast<const void *>(reduceSchurKernel), w.sr.device, 96 * 1024);
+  const ReduceSchurArgs a = makeReduceSchurArgs(w, for_marg, ctrl, fused, mode);
+  const size_t reduce_count = (fused && fused->combined) ? w.combCount() : w.reduceCount();
+  const bool grouped_tail = mode == ReduceMode::kAccumulateOnly && w.allreduce != nullptr;
   const size_t decide_smem = kDecideSmemBytes;
   if (mode == ReduceMode::kDecideOnly) {
     timedLaunch(w, DSOPP_HIP_KERNEL_ACCEPT,
@@ -1240,11 +1250,15 @@ int solveResidentWorkgroups(W &w, bool wide) {
   return n;
 }
 
-void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *decide_from = nullptr, const LmParams *decide_prm = nullptr,
-                         bool decide_from_groups = false, bool backsub = false, int ublk_parity = 0) {
-  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<256>), w.sr.device, 150 * 1024);
-  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<256, kMaxCombCopies>), w.sr.device, 150 * 1024);
-  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<512>), w.sr.device, 150 * 1024);
+// the hand-over block of the solve launches (W::d_bs_flag): [ticket counter | pad] (16 bytes), two hand-over buffers of kBlk * kMaxFrames
+// doubles, and — on a 128-byte line of its own — the reducers' arrival counter of the fused reduce + solve launches
+constexpr size_t kBsHand = static_cast<size_t>(kBlk) * kMaxFrames;
+constexpr size_t kBsArriveOffset = (16 + 2 * kBsHand * sizeof(double) + 127) / 128 * 128;
+constexpr size_t kBsBlockBytes = kBsArriveOffset + 128;
+
+/** the solve launch's arguments (launchSolveCombined; launchReduceSolveFused) */
+SolveCombArgs makeSolveCombArgs(W &w, double lambda, LmControl *ctrl, const LmControl *decide_from, const LmParams *decide_prm, bool decide_from_groups,
+                                bool backsub, int ublk_parity) {
   SolveCombArgs a;
   if (decide_from) {
     // decision + accept / reject as the prologue of this launch (workgroups 1 ..: the landmarks), then calculateIdepths for the new step
@@ -1260,10 +1274,11 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
     if (backsub && a.dec_blocks > 0) {
       if (!w.d_bs_flag) {
         // [ticket counter | pad] + two hand-over buffers of kBlk * kMaxFrames doubles, both armed
-        constexpr size_t kHand = static_cast<size_t>(kBlk) * kMaxFrames;
-        w.d_bs_flag.alloc(16 + 2 * kHand * sizeof(double));
+        constexpr size_t kHand = kBsHand;
+        w.d_bs_flag.alloc(kBsBlockBytes);
         std::vector<double> arm(2 * kHand, kHandOverSentinel());
-        HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, 16, w.sr.stream));
+        HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, kBsBlockBytes, w.sr.stream));
+        w.arrive_base = 0;
         HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag.get()) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
         HIP_CHECK(hipStreamSynchronize(w.sr.stream));  // (`arm` is a pageable host buffer)
         w.h_bs_fault.reserve(sizeof(int));
@@ -1305,6 +1320,15 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
   a.fej = w.fej() ? 1 : 0;
   a.use_marginal = w.marg_nonzero ? 1 : 0;
   a.dbg_stamps = w.dbg_stamps.get();
+  return a;
+}
+
+void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *decide_from = nullptr, const LmParams *decide_prm = nullptr,
+                         bool decide_from_groups = false, bool backsub = false, int ublk_parity = 0) {
+  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<256>), w.sr.device, 150 * 1024);
+  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<256, kMaxCombCopies>), w.sr.device, 150 * 1024);
+  ensureDynamicLds(reinterpret_cast<const void *>(solveCombinedKernel<512>), w.sr.device, 150 * 1024);
+  const SolveCombArgs a = makeSolveCombArgs(w, lambda, ctrl, decide_from, decide_prm, decide_from_groups, backsub, ublk_parity);
   timedLaunch(w, DSOPP_HIP_KERNEL_ASSEMBLE_SOLVE,
               [&] {
                 if (w.F() > 8)
@@ -1332,6 +1356,71 @@ void launchSolveCombined(W &w, double lambda, LmControl *ctrl, const LmControl *
   }
 }
 
+/** K2 + K3 of the fused loop in ONE launch (reduceSolveFusedKernel, pba_solve_combined.hpp): the reducers of launchReduceSchur(kAccumulateOnly),
+ *  and behind them in the grid the solver and the landmark workgroups of launchSolveCombined, resident from the launch's first cycle.  The
+ *  solver does everything that does not need the combined system while the reducers build it, and picks it up behind their last arrival.
+ *  For the windows lmSolveFusedEnqueue finds eligible: unsharded, atomics path, one copy of the system, back-substitution in the solve launch. */
+constexpr int kFusedMaxLandmarkWorkgroups = 47;
+
+template <int THREADS>
+int fusedResidentWorkgroups(W &w, size_t smem) {
+  static std::map<std::pair<int, size_t>, int> cache;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_pair(w.sr.device, smem);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  int per_cu = 0, cus = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reduceSolveFusedKernel<THREADS>, kSchurThreads, smem));
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w.sr.device));
+  return cache[key] = per_cu * cus;
+}
+
+void launchReduceSolveFused(W &w, const LmControl *cin, LmControl *cout, const FusedReduce &fr) {
+  const int F = w.F(), K = w.K();
+  ensureDynamicLds(reinterpret_cast<const void *>(reduceSolveFusedKernel<256>), w.sr.device, 150 * 1024);
+  ensureDynamicLds(reinterpret_cast<const void *>(reduceSolveFusedKernel<kSchurThreads>), w.sr.device, 150 * 1024);
+  const ReduceSchurArgs ra = makeReduceSchurArgs(w, false, cin, &fr, ReduceMode::kAccumulateOnly);
+  SolveCombArgs sa = makeSolveCombArgs(w, 0.0, cout, cin, &fr.prm, false, /*backsub=*/true, fr.ublk_parity);
+  const size_t smem = std::max({schurSmemBytes(K), kDecideSmemBytes, solveSmemBytes(K)});
+  const bool wide = F > 8;
+  const int resident = wide ? fusedResidentWorkgroups<kSchurThreads>(w, smem) : fusedResidentWorkgroups<256>(w, smem);
+  // The workgroups of this launch that wait — the landmark workgroups and the solver — wait for reducers of the same launch.  What
+  // protects them is the order of dispatch: a kernel's workgroups are dispatched in block order, and the reducers have the lower
+  // indices, so by the time a waiting workgroup is resident its launch's reducers have been dispatched (they wait for nobody and finish).
+  // The cap below is a second line, not a guarantee: should an XCD ever hold back its share of the reducers behind other work, the
+  // waiting workgroups of a few concurrent fused launches (other streams, other processes on the card) must not be what fills it — a
+  // launch keeps at most 48 of them, six per XCD of 32 compute units (a grid is dealt round-robin over the XCDs).  How many launches run at
+  // once depends on the hardware queues in use and on the processes sharing the card, so no count makes this arithmetic exact; a wait
+  // that does run out is reported, not hung (bs_fault).  (Windows whose landmark workgroups then take more than the two passes whose rows
+  // wait in registers fetch the rest behind the step, as very large windows always have.)
+  sa.dec_blocks = std::min({sa.dec_blocks, kFusedMaxLandmarkWorkgroups, resident - 1});
+  if (sa.dec_blocks < 1 || !sa.bs_hand) fail(DSOPP_HIP_ERR_CAPACITY, "the fused reduce + solve launch does not fit on the device (%d resident workgroups)", resident);
+  sa.bs_ticket = nullptr;  // roles by block index: no ticket is drawn
+  const int n_reducers = ra.n_schur_blocks + F * F + 1;
+  sa.fused_first = n_reducers;
+  sa.arrive = reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(w.d_bs_flag.get()) + kBsArriveOffset);
+  sa.arrive_target = w.arrive_base + static_cast<unsigned>(n_reducers);
+  const unsigned grid = static_cast<unsigned>(n_reducers + 1 + sa.dec_blocks);
+  // (attributed to the solve's kernel class: it ends with the solve, and a profile of an eligible window shows no reduction launch)
+  timedLaunch(w, DSOPP_HIP_KERNEL_ASSEMBLE_SOLVE, [&] {
+    if (wide)
+      reduceSolveFusedKernel<kSchurThreads><<<grid, kSchurThreads, smem, w.sr.stream>>>(ra.ctrl, ra.schur_table, ra.pc, ra.partials, ra.pair_first_block,
+                                                                                        ra.pair_num_blocks, ra.n_schur_blocks, ra.F, ra, sa);
+    else
+      reduceSolveFusedKernel<256><<<grid, kSchurThreads, smem, w.sr.stream>>>(ra.ctrl, ra.schur_table, ra.pc, ra.partials, ra.pair_first_block,
+                                                                              ra.pair_num_blocks, ra.n_schur_blocks, ra.F, ra, sa);
+  });
+  HIP_CHECK(hipGetLastError());
+  // the launch was accepted (as in launchSolveCombined): every reducer adds one to the counter, every workgroup arms the other hand-over buffer
+  w.bs_seq++;
+  w.arrive_base += static_cast<unsigned>(n_reducers);
+  if (!w.fej()) {
+    pairSetupKernel<<<1, kMaxFrames * kMaxFrames, 0, w.sr.stream>>>(w.d_frames.ptr, w.d_state.ptr, w.d_pc.ptr, F, 0, nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
 /** behind a synchronisation of a fused solve: did a landmark workgroup of a solve launch give up waiting for the step?  Then the inverse
  *  depths of that round were not back-substituted and the solve's result is not the algorithm's: the hand-over state is rebuilt and the
  *  call fails (the window stays usable). */
@@ -1340,11 +1429,12 @@ void checkSolveLaunchFault(W &w) {
   *w.h_bs_fault.get() = 0;
   constexpr size_t kHand = static_cast<size_t>(kBlk) * kMaxFrames;
   std::vector<double> arm(2 * kHand, kHandOverSentinel());
-  HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, 16, w.sr.stream));
+  HIP_CHECK(hipMemsetAsync(w.d_bs_flag.get(), 0, kBsBlockBytes, w.sr.stream));
   HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(w.d_bs_flag.get()) + 16, arm.data(), arm.size() * sizeof(double), hipMemcpyHostToDevice, w.sr.stream));
   HIP_CHECK(hipStreamSynchronize(w.sr.stream));
   w.bs_seq = 0;
   w.bs_ticket_base = 0;
+  w.arrive_base = 0;
   fail(DSOPP_HIP_ERR_HIP, "a solve launch's landmark workgroups waited 2 s for the pose step (device shared with a kernel that never yields?): "
                           "the inverse depths of that iteration were not updated, the solve is void");
 }
@@ -1567,6 +1657,10 @@ void lmSolveFusedEnqueue(W &w) {
   // DSOPP_HIP_COMB_COPIES_MIN_CHUNKS (test aid): the window size, in chunks of 64 landmarks, from which the copies are used
   static const int comb_copies_min_chunks = std::getenv("DSOPP_HIP_COMB_COPIES_MIN_CHUNKS") ? std::atoi(std::getenv("DSOPP_HIP_COMB_COPIES_MIN_CHUNKS")) : 80;
   w.comb_copies_active = (!w.twoStage() && !w.allreduce && w.F() <= 7 && w.n_schur_blocks >= comb_copies_min_chunks) ? kMaxCombCopies : 1;
+  // K2 and K3 as one launch (launchReduceSolveFused) where the solve launch back-substitutes and reads ONE copy of a system built with atomics
+  // on this device alone.  DSOPP_HIP_FUSED_REDUCE_SOLVE=0 (test and A/B aid, read once per process) keeps the two launches.
+  static const bool fused_reduce_solve_on = !(std::getenv("DSOPP_HIP_FUSED_REDUCE_SOLVE") && std::atoi(std::getenv("DSOPP_HIP_FUSED_REDUCE_SOLVE")) == 0);
+  const bool fuse_reduce_solve = fused_reduce_solve_on && !w.allreduce && !w.twoStage() && k3_backsub && w.comb_copies_active == 1;
   struct CopiesReset {
     W &w;
     ~CopiesReset() { w.comb_copies_active = 1; }
@@ -1613,7 +1707,7 @@ void lmSolveFusedEnqueue(W &w) {
     fr.ctrl_out = cout;
     fr.prm = prm;
     fr.combined = true;  // (the sharded accumulate pass reads lambda from the incoming control block: constant, decrease = increase = 1)
-    bool decide_from_groups = false;
+    bool decide_from_groups = false, solve_launched = false;
     if (w.twoStage() && r + 1 < rounds) {
       // large windows / deterministic mode: the combined system without atomics (pba_schur_two_stage.hpp).  kScalarGroups extra
       // workgroups of the same launch sum the sweep's energy scalars in fixed groups behind the combined system's slot; the
@@ -1651,6 +1745,10 @@ void lmSolveFusedEnqueue(W &w) {
         fr.scalars = w.d_scalars.ptr + 16;
       }
       launchReduceSchur(w, false, cin, &fr, ReduceMode::kDecideOnly);
+    } else if (fuse_reduce_solve) {
+      // K2 + K3 in one launch: the solver is resident and armed while the reducers work (r + 1 < rounds holds on this branch)
+      launchReduceSolveFused(w, cin, cout, fr);
+      solve_launched = true;
     } else {
       // K2: the local systems accumulated with atomics + one extra workgroup that sums the sweep's four energy scalars behind them
       // (landmark shards: ONE collective over [system | scalars]); K3 then takes the decision — a function of those sums and the
@@ -1659,7 +1757,7 @@ void lmSolveFusedEnqueue(W &w) {
       launchReduceSchur(w, false, cin, &fr, ReduceMode::kAccumulateOnly);
       decide_from_groups = w.allreduce != nullptr;  // (shards: the grouped tail, see launchReduceSchur)
     }
-    if (r + 1 < rounds) launchSolveCombined(w, 0.0, cout, cin, &fr.prm, decide_from_groups, k3_backsub, fr.ublk_parity);  // K3: decision prologue + solve (+ calculateIdepths)
+    if (r + 1 < rounds && !solve_launched) launchSolveCombined(w, 0.0, cout, cin, &fr.prm, decide_from_groups, k3_backsub, fr.ublk_parity);  // K3: decision prologue + solve (+ calculateIdepths)
   }
   LmControl *cfin = ctrl + (rounds & 1);
   HIP_CHECK(hipGetLastError());

@@ -75,7 +75,32 @@ struct SolveCombArgs {
   // the solve with DSOPP_HIP_ERR_HIP.  (Until round 5 the waiter trapped, which takes the whole HIP context — every window, aligner and
   // group of the process — down with it.)
   int *bs_fault = nullptr;
+  // The fused reduce + solve launch (reduceSolveFusedKernel, below): the roles go by block index — block fused_first solves, the dec_blocks
+  // blocks behind it are the landmark workgroups — and both wait for the launch's reducers on `arrive`, a counter that every reducer
+  // workgroup of every fused launch of the window adds 1 to; arrive_target is what it reads once all reducers of THIS launch have arrived
+  // (the host counts the launches, as it does for bs_ticket_base: no kernel resets anything).
+  const unsigned *arrive = nullptr;
+  unsigned arrive_target = 0;
+  int fused_first = 0;
 };
+/** One lane waits until the reducers of its launch have all arrived (SolveCombArgs::arrive): relaxed agent-scope loads, `sleep` x 64 cycles
+ *  apart.  Bounded like the wait for the step: after 2 s it raises SolveCombArgs::bs_fault and returns false — everybody leaves, the host
+ *  fails the solve (checkSolveLaunchFault). */
+__device__ __forceinline__ bool waitForReducers(const unsigned *arrive, unsigned target, bool patient, int *fault) {
+  const long long t0 = wall_clock64();
+  for (;;) {
+    const unsigned v = __hip_atomic_load(glb(arrive), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (static_cast<int>(v - target) >= 0) return true;  // (wrap-safe: the counter runs on from launch to launch)
+    if (patient)
+      __builtin_amdgcn_s_sleep(24);  // the landmark workgroups: they have the whole factorisation to spare
+    else
+      __builtin_amdgcn_s_sleep(1);   // the solver: the last arrival is on the iteration's critical path
+    if (wall_clock64() - t0 > 200000000ll) {
+      if (fault) __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return false;
+    }
+  }
+}
 /** what an armed hand-over slot holds: a quiet NaN with a payload no arithmetic produces */
 __host__ __device__ inline double kHandOverSentinel() {
   union {
@@ -105,11 +130,19 @@ __device__ __forceinline__ void combBlockDecode(int b, int &bi, int &bj) {
  *  -amdgpu-kernarg-preload-count — but not the members of a by-value struct.  With them the ticket and the solver's first operand loads
  *  leave in the wave's first cycles, beside the rest of the argument block instead of behind it.) */
 /** COPIES: 1, or kMaxCombCopies for a system the reduction launch accumulated in several copies (SolveCombArgs::comb_copies of them are live) */
-template <int THREADS, int COPIES = 1>
-__global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_ticket_p, double *bs_hand_next_p, const LmControl *dec_in_p,
-                                                                  const double *dec_scalars_p, const double *comb_p, const FrameDev *frames_p,
-                                                                  WindowState *st_p, int F_p, SolveCombArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+/** The launch's body, shared by solveCombinedKernel and the fused reduce + solve launch (reduceSolveFusedKernel, below) and inlined into both.
+ *  FUSED: the workgroup runs in the same launch as the reducers that build `comb`.  Its role is its block index (SolveCombArgs::fused_first);
+ *  the solver takes the four sums of the sweep's scalars from t_fused (its own workgroup summed them, in the scalar workgroup's order) and
+ *  so runs its whole head — decision, frame states, control block, prior diagonal, right-hand-side inputs — while the reducers work; then one
+ *  lane polls SolveCombArgs::arrive, and only the combined system and its right-hand side are loaded behind the last arrival, at agent scope
+ *  (the atomics that built them executed at the memory side; this XCD's L2 may hold last iteration's lines).  The landmark workgroups wait
+ *  for the same counter BEFORE they decide: they read the scalar workgroup's sums and, per landmark, the record the Schur reducers stored at
+ *  agent scope (reduceSchurBody<true>) with agent-scope loads — the choice "reducers store, landmark workgroups read behind the counter", not
+ *  a recomputation.  No fence anywhere: a release wrote the whole L2 back and arrived 5 us late. */
+template <int THREADS, int COPIES, bool FUSED>
+__device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_ticket_p, double *bs_hand_next_p, const LmControl *dec_in_p,
+                                                  const double *dec_scalars_p, const double *comb_p, const FrameDev *frames_p, WindowState *st_p,
+                                                  int F_p, const SolveCombArgs &a, const double *t_fused) {
   const int F = F_p, K = kBlk * F;
   const int N = K + 1;   // augmented with the right-hand side row
   const int ld = N + 1;
@@ -133,12 +166,13 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
   // Workgroup 0 requests everything that does not depend on the decision — pair constants, frame flags, right-hand side, the first
   // batch of the combined system — BEFORE it takes the decision: the decision's own loads, its LDS tree and its scalar chain then
   // run under these loads' round trip instead of in front of it (the other workgroups only apply the decision and leave).
-  const bool ticketed = bs_ticket_p != nullptr;
+  const bool ticketed = FUSED || bs_ticket_p != nullptr;  // (the fused launch: roles by block index, no ticket is drawn)
+  const unsigned vblock_f = FUSED ? blockIdx.x - static_cast<unsigned>(a.fused_first) : 0u;
   // The ticket is drawn here and NOT looked at before the decision below: the returned value stays in its register, un-waited-for, under
   // everything requested in between.  (Until round 5 the base was subtracted right here — the compiler then waits for the atomic's
   // return, a device-scope round trip of 1 - 2 us, in front of every operand load of the solver.)
   unsigned ticket_raw = 0;
-  if (ticketed && tid == 0) {
+  if (!FUSED && ticketed && tid == 0) {
     // (the address is made opaque: for a wave-uniform address the compiler rewrites the add as a wave scan whose v_readfirstlane
     // consumes — and waits for — the returned value on the spot)
     auto tp = glb(bs_ticket_p);
@@ -154,7 +188,7 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
   const void DSOPP_CONSTANT *any_words = (const void DSOPP_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr();
   const LmControl DSOPP_CONSTANT *cin_src = dec_in_p ? (const LmControl DSOPP_CONSTANT *)dec_in_p : (const LmControl DSOPP_CONSTANT *)any_words;
   // (the stand-in has to cover every word read through it, and the field-by-field copy below every field: `*a.ctrl = cin` writes all of it)
-  static_assert(sizeof(a) >= sizeof(LmControl) && sizeof(a) >= 4 * sizeof(double), "the argument block stands in for an absent control block / scalar block");
+  static_assert(sizeof(SolveCombArgs) >= sizeof(LmControl) && sizeof(SolveCombArgs) >= 4 * sizeof(double), "the argument block stands in for an absent control block / scalar block");
   static_assert(sizeof(LmControl) == 6 * sizeof(double) + 8 * sizeof(int), "LmControl changed: extend the scalar copy below");
   LmControl cin;
   cin.lambda = cin_src->lambda;
@@ -171,7 +205,9 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
   cin.need_final_setup = cin_src->need_final_setup;
   cin.pending = cin_src->pending;
   cin.relin = cin_src->relin;
-  const double DSOPP_CONSTANT *t_src = dec_scalars_p ? (const double DSOPP_CONSTANT *)dec_scalars_p : (const double DSOPP_CONSTANT *)any_words;
+  // (the fused launch: the sums are being written by a workgroup of this launch — never read here, and never through the scalar cache)
+  const double DSOPP_CONSTANT *t_src =
+      (!FUSED && dec_scalars_p) ? (const double DSOPP_CONSTANT *)dec_scalars_p : (const double DSOPP_CONSTANT *)any_words;
   double t_early[4] = {t_src[0], t_src[1], t_src[2], t_src[3]};
   // Every other argument word the kernel's head reads is requested in ONE burst of scalar loads with one wait: left to itself the
   // compiler fetches each member where it is first used — a dozen s_load / s_waitcnt pairs in a row in front of the operand loads,
@@ -187,7 +223,12 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
                "s"(a.energy_marginalized));
   __shared__ unsigned s_vblock;
   // with tickets every workgroup requests the solver's operands (it does not know its role yet; the others drop them)
-  bool main_wg = ticketed || blockIdx.x == 0;
+  bool main_wg = FUSED ? vblock_f == 0 : (ticketed || blockIdx.x == 0);
+  // the predicate under which the reducers of a fused launch build (reduceSchurBody's gate, read from the same control block): only then
+  // does anybody wait for them.  (The device-driven loop only ever writes linear_system_valid as 0 — lmBeginKernel —, so inside it the predicate
+  // is `active`; the rounds behind a rejected step have `relin` set instead: there the reducers build and arrive, and the solver decides
+  // and leaves without waiting, further down.)
+  const bool reducers_build = FUSED && cin.active && !cin.linear_system_valid;
   struct {
     int valid;
     Rigid T0;
@@ -240,7 +281,7 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
     fixed_c = frames_p[f].fixed;
     tomarg_c = frames_p[f].to_marginalize;
     ab0_c = st_p->ab0[f][i < 6 ? 0 : i - 6];
-    rhs_c = comb_p[combBlockCount(F) * 64 + tid];
+    if (!FUSED) rhs_c = comb_p[combBlockCount(F) * 64 + tid];  // (fused: behind the reducers' arrival, below)
     if (COPIES > 1) {
       for (int cp = 1; cp < a.comb_copies; ++cp)
         rhs_c += comb_p[a.comb_copy_first + static_cast<size_t>(cp - 1) * a.comb_copy_stride + combBlockCount(F) * 64 + tid];
@@ -270,7 +311,11 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
       const int e = base + tid + THREADS * u;
-      hv[u] = comb_p[min(e, n_entries - 1)];  // clamped, unconditional (a select around a load makes hipcc branch per element)
+      // clamped, unconditional (a select around a load makes hipcc branch per element)
+      if (FUSED)
+        hv[u] = __hip_atomic_load(glb(comb_p) + min(e, n_entries - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else
+        hv[u] = comb_p[min(e, n_entries - 1)];
       hm[u] = 0;
     }
     // (the other copies of a system accumulated in several: all requested before the first is added)
@@ -296,7 +341,7 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
       for (int u = 0; u < kBatch; ++u) hm[u] = a.HmPacked[min(base + tid + THREADS * u, n_entries - 1)];
     }
   };
-  if (main_wg) loadBatch(0);
+  if (main_wg && !FUSED) loadBatch(0);
   if (decides) {
     __shared__ LmControl s_dec_out;
     __shared__ int s_dec_accept, s_dec_proceed;
@@ -328,15 +373,32 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
           t[e] = sacc;
         }
       }
-    } else {
+    } else if (!FUSED) {
       t[0] = t_early[0];
       t[1] = t_early[1];
       t[2] = t_early[2];
       t[3] = t_early[3];
     }
     if (!cin.active) {  // the loop has ended: the control block is handed on unchanged
-      if (tid == 0 && (ticketed ? ticket_raw == a.bs_ticket_base : blockIdx.x == 0)) *a.ctrl = cin;
+      if (tid == 0 && (FUSED ? main_wg : (ticketed ? ticket_raw == a.bs_ticket_base : blockIdx.x == 0))) *a.ctrl = cin;
       return;
+    }
+    __shared__ int s_arrive_failed;
+    if (FUSED && tid == 0) {
+      if (main_wg) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = t_fused[e];
+      } else {
+        // a landmark workgroup: everything it reads from here on that this launch's reducers write — the sums, its landmarks' reference
+        // blocks, b_d, inv_hdd, flags — is read behind their last arrival (this lane reads the sums itself; the other lanes read behind the
+        // barrier below, which this lane joins after its poll has matched)
+        const bool arrived = !reducers_build || waitForReducers(a.arrive, a.arrive_target, true, a.bs_fault);
+        s_arrive_failed = arrived ? 0 : 1;
+        if (arrived) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) t[e] = __hip_atomic_load(glb(a.dec_scalars) + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
     }
     SC_STAMP(8);
     if (tid == 0) {
@@ -346,10 +408,11 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
       s_dec_out = c;
       s_dec_accept = accept;
       s_dec_proceed = proceed;
-      s_vblock = ticketed ? ticket_raw - a.bs_ticket_base : blockIdx.x;
+      s_vblock = FUSED ? vblock_f : (ticketed ? ticket_raw - a.bs_ticket_base : blockIdx.x);
     }
     ldsBarrier();
     SC_STAMP(9);
+    if (FUSED && !main_wg && s_arrive_failed) return;  // (uniform: read after the barrier; the word is raised, the host fails the solve)
     dec_accept = s_dec_accept;
     const unsigned vblock = s_vblock;
     main_wg = vblock == 0;
@@ -358,7 +421,7 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
       // pass = CPP chunks of 64; workgroup b takes the passes b - 1, b - 1 + W, ...
       constexpr int LP = THREADS / 4, CPP = LP / kSchurLandmarks;
       static_assert(CPP >= 1, "a pass covers whole chunks");
-      const int W = gridDim.x - 1, n_pass = (a.dec_chunks + CPP - 1) / CPP;
+      const int W = FUSED ? a.dec_blocks : static_cast<int>(gridDim.x) - 1, n_pass = (a.dec_chunks + CPP - 1) / CPP;
       const int sub = tid & 3, grp = tid >> 2, l = grp & (kSchurLandmarks - 1), chunk_in_pass = grp / kSchurLandmarks;
       if (cin.pending) {
         // acceptStep / rejectStep of the landmarks (problem.hpp:364-402)
@@ -413,21 +476,34 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
         const SchurBlock &be = a.dec_table[chunk];
         const int i = be.offset + l;
         if (i >= be.n) return;
+        // (fused: what a Schur reducer of this launch stored for this landmark — the reference slot of its row with b_d and 1 / H_dd in the
+        // slot's spare entries, reduceSchurBody<true> — is read at agent scope, behind the arrival counter this workgroup waited for in front
+        // of its decision.  Of the flags byte, which that reducer rewrites with a plain store, only the marginalised bit is looked at: the
+        // reducer does not change it; "ill-conditioned" is 1 / H_dd == 0 in the record.)
         const uint8_t flg = be.flags[i];
-        if (flg & (kFlagMarginalized | kFlagIllConditioned)) return;
+        if (flg & (FUSED ? kFlagMarginalized : (kFlagMarginalized | kFlagIllConditioned))) return;
         const size_t plane = ublkPlane(be.cap);
         const hbm_f64 *base = be.ublk + static_cast<size_t>(a.bs_parity) * kMaxFrames * plane + static_cast<size_t>(i) * kUblk;
     #pragma unroll
         for (int q = 0; q < NS; ++q) {
           int t = sub + 4 * q;
           asm volatile("" : "+v"(t));  // (opaque: otherwise the per-slot masks 1 << t are hoisted out of the pass loop and held — two of them spilled)
-          if (t < F && (t == be.r || ((be.conn_mask >> t) & 1u))) {
+          if (FUSED && t < F && t == be.r) {  // the reference block: written by the reducer (the others: by the sweep, a launch ago)
+    #pragma unroll
+            for (int c = 0; c < kBlk; ++c) rw[q][c] = __hip_atomic_load(base + t * plane + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          } else if (t < F && (t == be.r || ((be.conn_mask >> t) & 1u))) {
     #pragma unroll
             for (int c = 0; c < kBlk; ++c) rw[q][c] = base[t * plane + c];
           }
         }
-        bd = be.b_d[i];
-        ih = be.inv_hdd[i];
+        if (FUSED) {
+          bd = __hip_atomic_load(base + be.r * plane + kBlk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ih = __hip_atomic_load(base + be.r * plane + kBlk + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (ih == 0) return;  // ill-conditioned: no step for this landmark (dst stays null)
+        } else {
+          bd = be.b_d[i];
+          ih = be.inv_hdd[i];
+        }
         dst = be.idepth_step + i;
       };
     #pragma unroll
@@ -537,6 +613,17 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
   ldsBarrier();  // keeps every load above; prior diagonal / eps visible
   SC_STAMP(10);
   if (!c_active || c_relin) return;
+  if (FUSED) {
+    // ---- the hand-over: everything above ran beside the reducers; what follows needs their result.  One lane polls; the others wait at
+    // the barrier it joins once its poll has matched, and every load of the system comes behind that barrier, at agent scope.
+    __shared__ int s_system_there;
+    if (tid == 0) s_system_there = (!reducers_build || waitForReducers(a.arrive, a.arrive_target, false, a.bs_fault)) ? 1 : 0;
+    ldsBarrier();
+    if (!s_system_there) return;  // (the landmark workgroups' wait for the step runs out in turn)
+    SC_STAMP(16);
+    if (tid < K) rhs_c = __hip_atomic_load(glb(comb_p) + combBlockCount(F) * 64 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    loadBatch(0);
+  }
   const double *prior_diag = Linv;
   // Where entry e = base + tid + THREADS * u goes: its block index (e >> 6) is the same for the whole wave (THREADS and base are multiples
   // of 64) and advances by THREADS / 64 per u; the position inside the block depends on the lane alone.  The block's row and column are
@@ -744,6 +831,72 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
     }
   }
   SC_STAMP(5);
+}
+
+template <int THREADS, int COPIES = 1>
+__global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_ticket_p, double *bs_hand_next_p, const LmControl *dec_in_p,
+                                                                  const double *dec_scalars_p, const double *comb_p, const FrameDev *frames_p,
+                                                                  WindowState *st_p, int F_p, SolveCombArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  solveCombinedBody<THREADS, COPIES, false>(smem_raw, bs_ticket_p, bs_hand_next_p, dec_in_p, dec_scalars_p, comb_p, frames_p, st_p, F_p, a, nullptr);
+}
+
+/**
+ * K2 + K3 of the fused loop as ONE launch (unsharded windows on the atomics path whose solve launch back-substitutes: pba.hip,
+ * launchReduceSolveFused).  kSchurThreads threads per workgroup, roles by block index:
+ *   [0, n_reducers)                       the reducers: reduceSchurBody — Schur chunks, pair blocks, the scalar workgroup.  They wait for nobody.
+ *                                         Each arrives exactly once on SolveCombArgs::arrive, on every path through the body: every wave drains
+ *                                         its atomics and stores (s_waitcnt vmcnt(0)), a workgroup barrier, then one relaxed agent-scope add by
+ *                                         one thread.  A launch whose gate is closed arrives too — nobody waits for it, and the counter then
+ *                                         advances by the same amount for every launch, which is what lets the host pass the target.
+ *   n_reducers                            the solver: solveCombinedBody<THREADS, 1, true>, armed from the launch's first cycle (see there)
+ *   (n_reducers, n_reducers + dec_blocks] the landmark workgroups of the solve launch
+ * THREADS = 256 (up to 8 frames): the upper four waves of the solver and of the landmark workgroups leave before the body starts.
+ * Only the solver and the landmark workgroups wait, for workgroups of the same launch that wait for nobody; dec_blocks + 1 workgroups fit
+ * on the device at once (launchReduceSolveFused), so a reducer that has not been dispatched yet is only ever delayed by them.
+ */
+template <int THREADS>
+__global__ void __launch_bounds__(kSchurThreads) reduceSolveFusedKernel(const LmControl *ctrl_p, const SchurBlock *table_p, const PairConst *pc_p,
+                                                                        const double *partials_p, const int *pair_first_p, const int *pair_num_p,
+                                                                        int n_schur_blocks_p, int F_p, ReduceSchurArgs ra, SolveCombArgs sa) {
+  static_assert(THREADS == 256 || THREADS == kSchurThreads, "the solve body's two instantiations");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  // (the role from the preloaded arguments alone — sa.fused_first is the same number, but a member of a by-value struct is a scalar load
+  // in front of the reducers' first loads: their head took 0.4 us longer than reduceSchurKernel's)
+  const int n_reducers = n_schur_blocks_p + F_p * F_p + 1;
+  if (static_cast<int>(blockIdx.x) < n_reducers) {
+    reduceSchurBody<true>(smem_raw, ctrl_p, table_p, pc_p, partials_p, pair_first_p, pair_num_p, n_schur_blocks_p, F_p, ra);
+    // the arrival: behind everything every wave of this workgroup sent to memory
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(glb(const_cast<unsigned *>(sa.arrive)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  __shared__ double s_sums[4];
+  if (static_cast<int>(blockIdx.x) == n_reducers) {
+    // the solver sums the sweep's four energy scalars for itself — the scalar workgroup's loop and tree, thread for thread, so both get the
+    // same bits — instead of waiting for that workgroup: its decision and everything that follows from it run beside the reducers
+    double *lds = reinterpret_cast<double *>(smem_raw);
+    double v[4] = {0, 0, 0, 0};
+    for (int b = threadIdx.x; b < ra.n_sweep_blocks; b += kSchurThreads) {
+      const double *p = partials_p + static_cast<size_t>(b) * kPartial + 44;
+      v[0] += p[0];
+      v[1] += p[1];
+      v[2] += p[2];
+      v[3] += p[3];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lds[e * (kSchurThreads + 2) + threadIdx.x] = v[e];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      double sacc = 0;
+      for (int j = 0; j < kSchurThreads; ++j) sacc += lds[threadIdx.x * (kSchurThreads + 2) + j];
+      s_sums[threadIdx.x] = sacc;
+    }
+    __syncthreads();
+  }
+  if (static_cast<int>(threadIdx.x) >= THREADS) return;
+  solveCombinedBody<THREADS, 1, true>(smem_raw, nullptr, sa.bs_hand_next, ctrl_p, nullptr, sa.comb, sa.frames, sa.st, F_p, sa, s_sums);
 }
 
 }  // namespace dsopp_hip

@@ -403,10 +403,16 @@ __device__ inline bool fusedDecideApply(const ReduceSchurArgs &a, double *lds, l
 /** (the leading arguments repeat members of `a`: the dispatcher preloads the first 16 argument words into scalar registers —
  *  build.sh: -amdgpu-kernarg-preload-count — but not the members of a by-value struct.  With them the control block and the descriptor
  *  are requested in the wave's first cycles, beside the rest of the argument block instead of behind it.) */
-__global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmControl *ctrl_p, const SchurBlock *table_p, const PairConst *pc_p,
-                                                                   const double *partials_p, const int *pair_first_p, const int *pair_num_p,
-                                                                   int n_schur_blocks_p, int F_p, ReduceSchurArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+/** The launch's body, shared by reduceSchurKernel and the fused reduce + solve launch (pba_solve_combined.hpp: reduceSolveFusedKernel), inlined
+ *  into both (a non-inlined call was measured slower: DESIGN.md section 4).  Every `return` below leaves the body only.
+ *  HANDOVER (the fused launch): what workgroups of the SAME launch read behind the reducers' arrival counter — the four scalar sums, and per
+ *  landmark the reference slot of the Schur row with b_d and 1 / H_dd in its two spare entries — is stored at agent scope (written through to
+ *  memory: the XCDs' L2s are not coherent with each other); the combined system itself is accumulated with atomics, which execute at the
+ *  memory side. */
+template <bool HANDOVER>
+__device__ __forceinline__ void reduceSchurBody(char *smem_raw, const LmControl *ctrl_p, const SchurBlock *table_p, const PairConst *pc_p,
+                                                const double *partials_p, const int *pair_first_p, const int *pair_num_p, int n_schur_blocks_p, int F_p,
+                                                ReduceSchurArgs &a) {
   a.ctrl = ctrl_p;
   a.schur_table = table_p;
   a.pc = pc_p;
@@ -492,7 +498,10 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmContr
     if (threadIdx.x < 4) {
       double sacc = 0;
       for (int j = 0; j < kSchurThreads; ++j) sacc += lds[threadIdx.x * (kSchurThreads + 2) + j];
-      a.scalars_out[threadIdx.x] = sacc;
+      if (HANDOVER)
+        __hip_atomic_store(glb(a.scalars_out) + threadIdx.x, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else
+        a.scalars_out[threadIdx.x] = sacc;
     } else if (static_cast<int>(threadIdx.x) < 4 * a.scalars_out_groups) {
       a.scalars_out[threadIdx.x] = 0;
     }
@@ -617,6 +626,9 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmContr
   }
   ldsBarrier();
   RS_STAMP(2);
+  // (HANDOVER: this lane's share of the landmark's hand-over record, stored at the end of the body)
+  double ho_first = 0, ho_second = 0;
+  double *ho_dst = nullptr;
   {
     double hr[kBlk];
 #pragma unroll
@@ -659,7 +671,7 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmContr
 #pragma unroll
         for (int c = 0; c < kBlk; ++c) {
           row[kBlk * r + c] = hr[c];
-          dst[c] = hr[c];
+          if (!HANDOVER) dst[c] = hr[c];  // (HANDOVER: below, by all eight lanes)
         }
         be.b_d[i] = bd;
         const double kIdepthNullSpaceThreshold = 1e-15;
@@ -677,6 +689,30 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmContr
       wgt[l] = inv;
       wbd[l] = ibd;
       if (bd_in_pad && take) row[K] = bd;
+    }
+    if (HANDOVER && take) {
+      // What the landmark workgroups of the same launch read of this landmark travels in ONE record, the reference slot of its Schur row:
+      // [0, 8) the reference block, [8] b_d, [9] 1 / H_dd — 0 for an ill-conditioned landmark (entries 8 and 9 of the reference slot are
+      // otherwise unused).  sum8 left every sum in all eight lanes of the landmark, so lane `sub` stores entry `sub` and the lanes 0, 1 the
+      // entries 8, 9: two store instructions per wave whose lanes write 64 and 16 contiguous bytes per landmark, at agent scope (written
+      // through: the next sweep reads the block from there too).  Stored entry by entry from lane 0 alone — eleven instructions of eight
+      // 8-byte fabric writes each — this phase took 1.1 us longer; the b_d / inv_hdd / flags arrays keep their plain stores (read by later
+      // launches only).  The two stores are issued at the END of the body, behind the atomics: their way to memory then runs beside the
+      // atomics' instead of in front of the matrix phase.
+      ho_dst = const_cast<double *>(ubase) + r * plane;
+      ho_first = hr[0];
+#pragma unroll
+      for (int c = 1; c < kBlk; ++c) ho_first = sub == c ? hr[c] : ho_first;
+      if (sub < 2) {
+        double inv_h = 0;  // (the expression of the lane-0 branch above: the same bits as inv_hdd)
+        const double kIdepthNullSpaceThreshold = 1e-15;
+        if (hdd > kIdepthNullSpaceThreshold) {
+          double hdd_r = hdd;
+          if (a.for_marginalized && be.fixed) hdd_r += 1e8;
+          inv_h = 1.0 / hdd_r;
+        }
+        ho_second = sub == 0 ? bd : inv_h;
+      }
     }
   }
   ldsBarrier();
@@ -741,6 +777,17 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmContr
     }
     RS_STAMP(5);
   }
+  if (HANDOVER && ho_dst) {
+    __hip_atomic_store(glb(ho_dst) + sub, ho_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sub < 2) __hip_atomic_store(glb(ho_dst) + kBlk + sub, ho_second, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ void __launch_bounds__(kSchurThreads) reduceSchurKernel(const LmControl *ctrl_p, const SchurBlock *table_p, const PairConst *pc_p,
+                                                                   const double *partials_p, const int *pair_first_p, const int *pair_num_p,
+                                                                   int n_schur_blocks_p, int F_p, ReduceSchurArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  reduceSchurBody<false>(smem_raw, ctrl_p, table_p, pc_p, partials_p, pair_first_p, pair_num_p, n_schur_blocks_p, F_p, a);
 }
 
 /** The LM decision for the pending candidate + its accept / reject as a kernel of its own: the closing round of a solve (nothing

@@ -41,7 +41,7 @@ struct FrameDev {
   hbm_f64 *inv_hdd, *b_d, *relative_baseline;
   hbm_i32 *n_inliers;
   hbm_u8 *flags;
-  hbm_f64 *ublk;  // [kMaxFrames][cap][kUblk]: slot t != r: {-u_pt (= h_p block t), hdd_pt, bd_pt}; slot r: {h_p block r, -, -}
+  hbm_f64 *ublk;  // [kMaxFrames][cap][kUblk]: slot t != r: {-u_pt (= h_p block t), hdd_pt, bd_pt}; slot r: {h_p block r, -, -} (the fused reduce + solve launch hands b_d and 1 / H_dd over in the two spare entries)
   hbm_u8 *status[kMaxFrames], *cand[kMaxFrames], *fej_valid[kMaxFrames];  // by target slot; nullptr = no connection
   hbm_f64 *energy[kMaxFrames];
   int n_res[kMaxFrames];
