@@ -34,6 +34,11 @@ class AlignResult(C.Structure):
                 ("H", C.c_double * 64)]
 
 
+class RotationRansacResult(C.Structure):
+    _fields_ = [("iterations_run", C.c_int32), ("best_iteration", C.c_int32), ("inlier_count", C.c_int32), ("matches", C.c_int32),
+                ("rotation", C.c_double * 9)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 # every symbol include/dsopp_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -83,6 +88,7 @@ SYMBOLS = [
     "dsopp_hip_flow_tracker_set_reference", "dsopp_hip_flow_tracker_set_reference_device", "dsopp_hip_flow_tracker_set_reference_from_pyramid",
     "dsopp_hip_flow_tracker_track", "dsopp_hip_flow_tracker_track_device", "dsopp_hip_flow_tracker_track_from_pyramid",
     "dsopp_hip_flow_tracker_get_level",
+    "dsopp_hip_rotation_ransac_create", "dsopp_hip_rotation_ransac_destroy", "dsopp_hip_rotation_ransac_estimate",
 ]
 
 _lib = None
@@ -524,6 +530,50 @@ class OpticalFlowTracker:
         der = np.zeros((h, w, 2), np.int16) if with_derivatives else None
         _chk(lib().dsopp_hip_flow_tracker_get_level(self._h, int(which), int(level), _p(img, np.uint8), _p(der, np.int16)))
         return (img, der) if with_derivatives else img
+
+
+class RotationRansac:
+    """estimateSO3inlierCount<3> on the device (dsopp_hip_rotation_ransac): the pure-rotation RANSAC of the bootstrap's standstill test,
+    every hypothesis scored in one launch.  points_a are the NEW frame's points, points_b the last bootstrap keyframe's; the rotation maps
+    bearings of points_a onto bearings of points_b.  The sample triples are the caller's."""
+
+    def __init__(self, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.device = device
+        _chk(lib().dsopp_hip_rotation_ransac_create(int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_rotation_ransac_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate(self, camera, points_a, points_b, samples, threshold=1.5, inliers_tolerance=0.95, with_hypotheses=False):
+        """camera = (fx, fy, cx, cy, width, height); points (n, 2) float64; samples (iterations, 3) int32.  Returns a dict: iterations_run,
+        best_iteration, inlier_count, matches, rotation (3, 3), inliers (ascending int32), and with with_hypotheses the per-hypothesis
+        hyp_counts (iterations,), hyp_rotations (iterations, 3, 3), hyp_valid (iterations,) uint8; blocking"""
+        fx, fy, cx, cy, width, height = camera
+        a = np.ascontiguousarray(points_a, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(points_b, dtype=np.float64).reshape(-1, 2)
+        s = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3)
+        assert a.shape == b.shape, (a.shape, b.shape)
+        n, m = len(a), len(s)
+        res = RotationRansacResult()
+        idx = np.zeros(n, np.int32)
+        hyp = (np.zeros(m, np.int32), np.zeros((m, 3, 3)), np.zeros(m, np.uint8)) if with_hypotheses else (None, None, None)
+        _chk(lib().dsopp_hip_rotation_ransac_estimate(self._h, C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(width), int(height),
+                                                      n, _p(a), _p(b), m, _p(s, np.int32), C.c_double(threshold), C.c_double(inliers_tolerance),
+                                                      C.byref(res), _p(idx, np.int32), _p(hyp[0], np.int32), _p(hyp[1]), _p(hyp[2], np.uint8)))
+        out = {"iterations_run": res.iterations_run, "best_iteration": res.best_iteration, "inlier_count": res.inlier_count,
+               "matches": res.matches, "rotation": np.array(res.rotation).reshape(3, 3), "inliers": idx[:res.inlier_count].copy()}
+        if with_hypotheses:
+            out.update(hyp_counts=hyp[0], hyp_rotations=hyp[1], hyp_valid=hyp[2])
+        return out
 
 
 class DepthMaps:

@@ -15,8 +15,10 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno
 FLAGS_align="${DSOPP_HIP_ALIGN_SCHED--mllvm -amdgpu-sched-strategy=max-ilp}"
 # optical_flow.hip: the tracker's float steps are single IEEE operations in a stated order (include/dsopp_hip.h): no product and sum may fuse
 FLAGS_optical_flow="-ffp-contract=off"
+# rotation_ransac.hip: the products and sums of the stated binary64 arithmetic stay unfused, as the NumPy model takes them
+FLAGS_rotation_ransac="-ffp-contract=off"
 pids=()
-for src in pyramid undistort transform colour optical_flow semantics pba align depth_estimation features features_eigen comm calibration window_group; do
+for src in pyramid undistort transform colour optical_flow rotation_ransac semantics pba align depth_estimation features features_eigen comm calibration window_group; do
   if [ -f "$HERE/$src.hip" ]; then
     extra="FLAGS_$src"
     $HIPCC $FLAGS ${!extra:-} -c "$HERE/$src.hip" -o "$OUT/$src.o" &
@@ -25,7 +27,7 @@ for src in pyramid undistort transform colour optical_flow semantics pba align d
 done
 for p in "${pids[@]}"; do wait "$p"; done
 objs=()
-for src in pyramid undistort transform colour optical_flow semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
+for src in pyramid undistort transform colour optical_flow rotation_ransac semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$OUT/libdsopp_hip.so"
 # measurement aids that are not part of the product (gather kernels of known geometry for the counter calibration, scripts/pmc_target.py)
 [ -f "$OUT/calibration.o" ] && $HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/calibration.o" -o "$OUT/libdsopp_hip_tools.so"

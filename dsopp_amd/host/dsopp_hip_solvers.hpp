@@ -18,6 +18,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1036,6 +1037,101 @@ class HipOpticalFlowMatch {
   int width_;
   std::vector<float> to_, err_;
   std::vector<uint8_t> status_;
+};
+
+/** FrameStatus of the initialiser's keyframe strategies (initialization_strategy/frame_status.hpp) */
+enum class FrameStatus { kDropFrame, kKeepFrame, kFinish };
+
+/** The bootstrap's standstill test on the device: estimateSO3inlierCount<3> (src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48),
+ *  that is ransac::ransac (ransac.hpp:27-56) over the three-point PureRorationSolver (pure_rotation_estimator.cpp:14-67), and the two
+ *  decisions that consume its counts.  The reference calls ransac(solver, target_points, reference_points, ...): points_new are the new
+ *  frame's points, points_keyframe the last bootstrap keyframe's, and the rotation maps bearings of the new frame onto bearings of the
+ *  keyframe (the reference stores it as rotation_t_r all the same).
+ *  One deviation: all sample triples are drawn ahead of the launch.  Given the same std::rand() state at entry the hypotheses examined and
+ *  the result equal the reference's; after an early stop the state of std::rand() left behind is not the reference's, which draws a
+ *  triple only for an iteration it runs. */
+class HipRotationStandstill {
+ public:
+  struct Result {
+    size_t inliers, matches;          // estimateSO3inlierCount's pair
+    std::array<double, 9> rotation;   // rotation_t_r, row-major
+    std::vector<int32_t> inlier_indices;
+    int iterations_run, best_iteration;
+  };
+  /** width, height: the image size of `model` (CameraModelBase::image_size), which bounds the ROI */
+  HipRotationStandstill(int width, int height, int device = 0, void *stream = nullptr) : width_(width), height_(height) {
+    check(dsopp_hip_rotation_ransac_create(device, stream, &r_));
+  }
+  ~HipRotationStandstill() { dsopp_hip_rotation_ransac_destroy(r_); }
+  HipRotationStandstill(const HipRotationStandstill &) = delete;
+  HipRotationStandstill &operator=(const HipRotationStandstill &) = delete;
+
+  /** generateRandomSequence<3>(n) (ransac/random_sequence_generator.hpp:17-34), `iterations` times: rand() % n, redrawn on a repeat */
+  static std::vector<int32_t> drawSamples(size_t n, size_t iterations) {
+    if (iterations > 0 && n < 3) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "fewer than 3 points: the reference's sampler never returns");
+    std::vector<int32_t> samples(3 * iterations);
+    for (size_t i = 0; i < iterations; ++i) {
+      size_t sequence[3];
+      sequence[0] = static_cast<size_t>(std::rand()) % n;
+      for (size_t k = 1; k < 3; ++k) {
+        size_t next = static_cast<size_t>(std::rand()) % n;
+        auto repeats = [&] {
+          for (size_t j = 0; j < k; ++j)
+            if (sequence[j] == next) return true;
+          return false;
+        };
+        while (repeats()) next = static_cast<size_t>(std::rand()) % n;
+        sequence[k] = next;
+      }
+      for (size_t k = 0; k < 3; ++k) samples[3 * i + k] = static_cast<int32_t>(sequence[k]);
+    }
+    return samples;
+  }
+
+  /** estimateSO3inlierCount<3>(keyframe, new frame, ...): the triples come from std::rand() */
+  Result estimate(const std::vector<Vector2> &points_new, const std::vector<Vector2> &points_keyframe, const PinholeModel &model,
+                  size_t iterations = 200, double threshold = 1.5) {
+    return estimate(points_new, points_keyframe, model, points_new.empty() ? std::vector<int32_t>() : drawSamples(points_new.size(), iterations),
+                    threshold);
+  }
+  /** the same over the caller's triples (3 indices per hypothesis) */
+  Result estimate(const std::vector<Vector2> &points_new, const std::vector<Vector2> &points_keyframe, const PinholeModel &model,
+                  const std::vector<int32_t> &samples, double threshold = 1.5, double inliers_tolerance = 0.95) {
+    if (points_new.size() != points_keyframe.size()) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the two point sets differ in size");
+    const size_t n = points_new.size();
+    Result out;
+    out.inlier_indices.assign(n, 0);
+    dsopp_hip_rotation_ransac_result res;
+    check(dsopp_hip_rotation_ransac_estimate(r_, model.fx, model.fy, model.cx, model.cy, width_, height_, static_cast<int>(n),
+                                             n ? points_new.front().data() : nullptr, n ? points_keyframe.front().data() : nullptr,
+                                             static_cast<int>(samples.size() / 3), samples.data(), threshold, inliers_tolerance, &res,
+                                             out.inlier_indices.data(), nullptr, nullptr, nullptr));
+    out.inlier_indices.resize(static_cast<size_t>(res.inlier_count));
+    out.inliers = static_cast<size_t>(res.inlier_count);
+    out.matches = static_cast<size_t>(res.matches);
+    for (int k = 0; k < 9; ++k) out.rotation[static_cast<size_t>(k)] = res.rotation[k];
+    out.iterations_run = res.iterations_run;
+    out.best_iteration = res.best_iteration;
+    return out;
+  }
+
+  /** WaitForMovementInitializerKeyframeStrategy::needNewFrame (wait_for_movement_keyframe_strategy.cpp:13-29) */
+  static FrameStatus needNewFrame(size_t previous_frames, size_t inliers, size_t matches, size_t sliding_window_length = 5,
+                                  double rotation_inlier_ratio = 0.7) {
+    if (previous_frames == 0) return FrameStatus::kKeepFrame;
+    if (inliers > static_cast<size_t>(rotation_inlier_ratio * static_cast<double>(matches))) return FrameStatus::kDropFrame;
+    if (sliding_window_length <= previous_frames + 1) return FrameStatus::kFinish;
+    return FrameStatus::kKeepFrame;
+  }
+  /** addNewFrame's standstill test (add_new_frame.cpp:36-45): the frame is attached to the last keyframe */
+  static bool isStandstill(size_t inliers, size_t matches, double max_ratio_of_so3_inliers = 0.7) {
+    return static_cast<double>(inliers) / static_cast<double>(matches) > max_ratio_of_so3_inliers;
+  }
+  dsopp_hip_rotation_ransac *handle() const { return r_; }
+
+ private:
+  dsopp_hip_rotation_ransac *r_ = nullptr;
+  int width_, height_;
 };
 
 }  // namespace dsopp_hip_host

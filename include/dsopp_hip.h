@@ -259,8 +259,8 @@ int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out
  * cv::calcOpticalFlowPyrLK(image_from, image_to, pts_from, pts_to, status, err, Size(15, 15), 3, TermCriteria(COUNT + EPS, 10, 0.01))
  * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
  * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
- * Not built: the refill of lost features from a fresh ORB extraction (optical_flow.cpp:44-53) and ORB itself, estimateSO3inlierCount,
- * initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ * Not built: the refill of lost features from a fresh ORB extraction (optical_flow.cpp:44-53) and ORB itself (estimateSO3inlierCount is
+ * dsopp_hip_rotation_ransac_* below), initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
  *
  * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
  * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
@@ -329,6 +329,60 @@ int dsopp_hip_flow_tracker_track_from_pyramid(dsopp_hip_flow_tracker *t, const d
  * and of the reference its Scharr plane as w_l x h_l (dx, dy) int16 pairs.  Either pointer may be NULL; deriv_out with which = 1 is
  * DSOPP_HIP_ERR_INVALID_ARGUMENT; DSOPP_HIP_ERR_STATE when that image was never set. */
 int dsopp_hip_flow_tracker_get_level(dsopp_hip_flow_tracker *t, int which, int level, uint8_t *image_out, int16_t *deriv_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The bootstrap's standstill test: the pure-rotation RANSAC over the matches of two frames (replaces estimateSO3inlierCount<3> —
+ * src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48 —, that is ransac::ransac — src/ransac/include/ransac/ransac.hpp:27-56 —
+ * over the three-point PureRorationSolver — src/energy/n_point_solvers/src/pure_rotation_estimator.cpp:14-67 —, which
+ * MonocularInitializer::tick — monocular_initializer.cpp:71-94 — and the feature-based tracker — add_new_frame.cpp:36-45 — run on every
+ * frame).  Not built: the essential-matrix and PnP RANSACs, triangulation, the refinement, ORB, the SimpleRadialCamera instantiation.
+ *
+ * The arithmetic is fixed here; tests/rotation_ransac_model.py is its NumPy form.  Everything is binary64 (the reference's Precision);
+ * float points of the flow tracker are widened by the caller.
+ *   Inputs: a pinhole camera fx, fy, cx, cy, width, height; n pairs A[j], B[j] (x, y); `iterations` sample triples S[i] = (s0, s1, s2) of
+ *     distinct indices < n, drawn by the caller; threshold in pixels (the reference's default 1.5); inliers_tolerance (0.95).
+ *   Roles: the reference calls ransac(solver, target_points, reference_points, ...): A is the NEW frame's points, B the last bootstrap
+ *     keyframe's, and the returned rotation maps bearings of A onto bearings of B.  The reference stores it under the name rotation_t_r
+ *     all the same; it is kept that way here.
+ *   roi(p) = 4 <= x <= width - 5 && 4 <= y <= height - 5 (camera_model_base.hpp:53-60); unproject(p) = ((x - cx) / fx, (y - cy) / fy, 1).
+ *   Hypothesis i (solve): invalid when any of its six sample points fails roi.  Otherwise a_k, b_k = the normalised bearings of
+ *     A[S[i][k]], B[S[i][k]]; H = sum_k a_k b_k^T / 9 (the reference divides by Matrix::size()); H = U S V^T; Q = V U^T;
+ *     R_i = det(Q) Q — the whole matrix flips, this is not Kabsch's diag(1, 1, d).  For a non-singular H, Q is the orthogonal polar
+ *     factor of H^T; any backward-stable route to it serves (the device: a one-sided Jacobi SVD).  With a vanishing smallest singular
+ *     value the result depends on the decomposition and is not pinned, but it is a rotation.
+ *   Score of R (findBest): point j is an inlier iff roi(A[j]) and, with (x, y, z) = R unproject(A[j]) and
+ *     q = (fx x / z + cx, fy y / z + cy), sqrt(|q - B[j]|^2) < threshold (strict; a NaN is no inlier).  No depth test, no roi test on q
+ *     or on B[j].  One deviation: for a point that fails roi(A[j]) the reference reads an uninitialised vector; here it is never an inlier.
+ *   An invalid hypothesis carries the rotation and the count of its nearest valid predecessor (the reference ignores solve's return value
+ *     and scores the solver's previous solution), and the identity and its count when no valid one precedes it.
+ *   Selection, the serial loop's meaning: walk i = 0, 1, ...; stop before i when (double)best / (double)n >= inliers_tolerance;
+ *     hypothesis i replaces the best iff its count is strictly greater.  best_iteration is -1 when no count exceeded 0: the rotation is
+ *     then the identity and there are no inliers, as with the reference's default-constructed Solution.
+ *   n = 0 runs no iteration (0 / 0 < 0.95 is false).  For n = 1, 2 the reference's sampler never returns: DSOPP_HIP_ERR_INVALID_ARGUMENT
+ *     when iterations > 0.
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_rotation_ransac dsopp_hip_rotation_ransac;
+typedef struct dsopp_hip_rotation_ransac_result {
+  int32_t iterations_run; /* hypotheses examined before the tolerance stopped the walk */
+  int32_t best_iteration; /* the winning hypothesis, -1 when no count exceeded 0 */
+  int32_t inlier_count;
+  int32_t matches;        /* n, the reference's matching number */
+  double rotation[9];     /* the winner's R, row-major */
+} dsopp_hip_rotation_ransac_result;
+/* `stream` is a hipStream_t (NULL = a stream of its own); all work of the object runs on it.  Its buffers grow with n and iterations. */
+int dsopp_hip_rotation_ransac_create(int device, void *stream, dsopp_hip_rotation_ransac **out);
+void dsopp_hip_rotation_ransac_destroy(dsopp_hip_rotation_ransac *r);
+/* One launch and one wait, blocking.  points_a / points_b: n x 2 doubles; samples: iterations x 3 int32; inlier_indices: room for n int32,
+ * the first result->inlier_count of which are written, ascending.  Optional (NULL) per-hypothesis outputs, there so that a divergence
+ * from the stated arithmetic can be located: hyp_counts (iterations int32), hyp_rotations (iterations x 9 doubles, row-major), hyp_valid
+ * (iterations bytes); they cover every hypothesis, also those behind an early stop.  DSOPP_HIP_ERR_INVALID_ARGUMENT: n < 0,
+ * iterations < 0, 0 < n < 3 with iterations > 0, a sample index outside 0 .. n - 1 or repeated within its triple, a threshold or
+ * inliers_tolerance that is not a number, a NULL required argument. */
+int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
+                                       const double *points_a, const double *points_b, int iterations, const int32_t *samples, double threshold,
+                                       double inliers_tolerance, dsopp_hip_rotation_ransac_result *result, int32_t *inlier_indices,
+                                       int32_t *hyp_counts, double *hyp_rotations, uint8_t *hyp_valid);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
