@@ -88,6 +88,9 @@ SYMBOLS = [
     "dsopp_hip_flow_tracker_set_reference", "dsopp_hip_flow_tracker_set_reference_device", "dsopp_hip_flow_tracker_set_reference_from_pyramid",
     "dsopp_hip_flow_tracker_track", "dsopp_hip_flow_tracker_track_device", "dsopp_hip_flow_tracker_track_from_pyramid",
     "dsopp_hip_flow_tracker_get_level",
+    "dsopp_hip_orb_features_per_level", "dsopp_hip_orb_detector_create", "dsopp_hip_orb_detector_destroy", "dsopp_hip_orb_detector_set_mask",
+    "dsopp_hip_orb_detector_set_mask_from_pyramid", "dsopp_hip_orb_detector_detect", "dsopp_hip_orb_detector_detect_device",
+    "dsopp_hip_orb_detector_detect_from_pyramid", "dsopp_hip_orb_detector_get_level",
     "dsopp_hip_rotation_ransac_create", "dsopp_hip_rotation_ransac_destroy", "dsopp_hip_rotation_ransac_estimate",
 ]
 
@@ -530,6 +533,91 @@ class OpticalFlowTracker:
         der = np.zeros((h, w, 2), np.int16) if with_derivatives else None
         _chk(lib().dsopp_hip_flow_tracker_get_level(self._h, int(which), int(level), _p(img, np.uint8), _p(der, np.int16)))
         return (img, der) if with_derivatives else img
+
+
+def orb_features_per_level(nfeatures, nlevels):
+    """the features cv::ORB grants each of its levels, (nlevels,) int32 (no device needed)"""
+    out = np.zeros(max(int(nlevels), 1), np.int32)
+    _chk(lib().dsopp_hip_orb_features_per_level(int(nfeatures), int(nlevels), _p(out, np.int32)))
+    return out
+
+
+class OrbDetector:
+    """DistinctFeaturesExtractorORB's cv::ORB detection on the device (dsopp_hip_orb_detector): keypoint positions with their level and
+    Harris response, in the canonical order (level, y, x).  Images are (height, width) uint8 arrays (any row stride), device addresses
+    as integers, or a Pyramid that keeps its 8-bit grey image."""
+
+    def __init__(self, width, height, nfeatures=500, nlevels=5, edge_threshold=31, fast_threshold=20, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.nfeatures, self.num_levels, self.device = int(width), int(height), int(nfeatures), int(nlevels), device
+        self._capacity = max(2 * self.nfeatures, 256)
+        _chk(lib().dsopp_hip_orb_detector_create(int(width), int(height), int(nfeatures), int(nlevels), int(edge_threshold), int(fast_threshold),
+                                                 int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_orb_detector_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_mask(self, mask):
+        """the mask bytes of every later detect ((height, width) uint8, 0 = masked), None = no mask; only enqueues"""
+        m = _u8(mask)
+        assert m is None or m.shape == (self.height, self.width)
+        _chk(lib().dsopp_hip_orb_detector_set_mask(self._h, _p(m, np.uint8)))
+
+    def set_mask_from_pyramid(self, pyramid: Pyramid):
+        """the level-0 mask `pyramid` kept from its last set_semantics, as validity (255 / 0); only enqueues"""
+        _chk(lib().dsopp_hip_orb_detector_set_mask_from_pyramid(self._h, pyramid._h))
+
+    def _image(self, image):
+        img = np.asarray(image)
+        assert img.dtype == np.uint8 and img.shape == (self.height, self.width), (img.dtype, img.shape)
+        if img.strides[1] != 1 or img.strides[0] < self.width:
+            img = np.ascontiguousarray(img)
+        return img, img.ctypes.data_as(C.c_void_p), C.c_size_t(img.strides[0])
+
+    def detect_raw(self, image, capacity, stride=None, outputs=None):
+        """one dsopp_hip_orb_detector_detect* call with room for `capacity`: (return code, n, xy, level, response), the arrays whole
+        (`outputs` = the caller's own three).  `image` is a host array, a Pyramid, or a device address with `stride`."""
+        cap = int(capacity)
+        xy, level, response = outputs or (np.zeros((max(cap, 1), 2), np.float32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32))
+        n = C.c_int32(-1)
+        args = (cap, _p(xy, np.float32), _p(level, np.int32), _p(response, np.float32), C.byref(n))
+        if isinstance(image, Pyramid):
+            rc = lib().dsopp_hip_orb_detector_detect_from_pyramid(self._h, image._h, *args)
+        elif isinstance(image, int):
+            rc = lib().dsopp_hip_orb_detector_detect_device(self._h, C.c_void_p(image), C.c_size_t(self.width if stride is None else stride), *args)
+        else:
+            img, ptr, row = self._image(image)
+            rc = lib().dsopp_hip_orb_detector_detect(self._h, ptr, row, *args)
+        return rc, n.value, xy, level, response
+
+    def detect(self, image, stride=None):
+        """(xy (n, 2) float32, level (n,) int32, response (n,) float32); blocking"""
+        rc, n, xy, level, response = self.detect_raw(image, self._capacity, stride)
+        if rc == -5:   # DSOPP_HIP_ERR_CAPACITY: run again with the room reported
+            self._capacity = n
+            rc, n, xy, level, response = self.detect_raw(image, self._capacity, stride)
+        _chk(rc)
+        return xy[:n].copy(), level[:n].copy(), response[:n].copy()
+
+    def level_size(self, level):
+        w, h = C.c_int(), C.c_int()
+        _chk(lib().dsopp_hip_orb_detector_get_level(self._h, int(level), None, None, None, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def get_level(self, level):
+        """(image, mask, FAST score plane) of level `level` after the last detect, each (h, w) uint8"""
+        w, h = self.level_size(level)
+        out = [np.zeros((h, w), np.uint8) for _ in range(3)]
+        _chk(lib().dsopp_hip_orb_detector_get_level(self._h, int(level), _p(out[0], np.uint8), _p(out[1], np.uint8), _p(out[2], np.uint8), None, None))
+        return tuple(out)
 
 
 class RotationRansac:

@@ -17,8 +17,10 @@ FLAGS_align="${DSOPP_HIP_ALIGN_SCHED--mllvm -amdgpu-sched-strategy=max-ilp}"
 FLAGS_optical_flow="-ffp-contract=off"
 # rotation_ransac.hip: the products and sums of the stated binary64 arithmetic stay unfused, as the NumPy model takes them
 FLAGS_rotation_ransac="-ffp-contract=off"
+# orb.hip: the Harris response is a chain of single IEEE binary32 steps in a stated order (include/dsopp_hip.h), as the NumPy model takes them
+FLAGS_orb="-ffp-contract=off"
 pids=()
-for src in pyramid undistort transform colour optical_flow rotation_ransac semantics pba align depth_estimation features features_eigen comm calibration window_group; do
+for src in pyramid undistort transform colour optical_flow rotation_ransac orb semantics pba align depth_estimation features features_eigen comm calibration window_group; do
   if [ -f "$HERE/$src.hip" ]; then
     extra="FLAGS_$src"
     $HIPCC $FLAGS ${!extra:-} -c "$HERE/$src.hip" -o "$OUT/$src.o" &
@@ -27,7 +29,7 @@ for src in pyramid undistort transform colour optical_flow rotation_ransac seman
 done
 for p in "${pids[@]}"; do wait "$p"; done
 objs=()
-for src in pyramid undistort transform colour optical_flow rotation_ransac semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
+for src in pyramid undistort transform colour optical_flow rotation_ransac orb semantics pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$OUT/libdsopp_hip.so"
 # measurement aids that are not part of the product (gather kernels of known geometry for the counter calibration, scripts/pmc_target.py)
 [ -f "$OUT/calibration.o" ] && $HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/calibration.o" -o "$OUT/libdsopp_hip_tools.so"

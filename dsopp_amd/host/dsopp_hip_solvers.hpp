@@ -983,7 +983,7 @@ struct FlowCorrespondence {
  *  features of frame_from tracked into image_to by cv::calcOpticalFlowPyrLK(..., Size(15, 15), 3, TermCriteria(COUNT + EPS, 10, 0.01)),
  *  a feature and a correspondence {true, i, features.size() - 1} for every status != 0, in the order of frame_from.  image_from is the
  *  first track frame for the whole bootstrap (monocular_initializer.cpp:47-51), so it is set once and its levels stay on the device.
- *  The refill from a fresh ORB extraction (optical_flow.cpp:44-53) stays with the caller. */
+ *  The refill from a fresh ORB detection (optical_flow.cpp:44-53) is HipFindCorrespondences below. */
 class HipOpticalFlowMatch {
  public:
   struct Result {
@@ -1037,6 +1037,115 @@ class HipOpticalFlowMatch {
   int width_;
   std::vector<float> to_, err_;
   std::vector<uint8_t> status_;
+};
+
+/** DistinctFeaturesExtractorORB (src/feature_based_slam/features/src/distinct_features_extractor_orb.cpp:11-38) on the device:
+ *  cv::ORB::create(number_of_features, 2.0f, 5)->detect, of which the reference uses keypoint.pt alone.  The detections come in the
+ *  canonical order of include/dsopp_hip.h (level, y, x), not in the order retainBest leaves them in; the set is the same. */
+class HipDistinctFeaturesExtractorORB {
+ public:
+  using Feature = std::array<float, 2>;
+  HipDistinctFeaturesExtractorORB(int width, int height, size_t number_of_features = 500, int device = 0, void *stream = nullptr, int levels = 5,
+                                  int edge_threshold = 31, int fast_threshold = 20)
+      : width_(width), number_of_features_(number_of_features) {
+    check(dsopp_hip_orb_detector_create(width, height, static_cast<int>(number_of_features), levels, edge_threshold, fast_threshold, device, stream, &d_));
+    reserve(2 * number_of_features + 256);
+  }
+  ~HipDistinctFeaturesExtractorORB() { dsopp_hip_orb_detector_destroy(d_); }
+  HipDistinctFeaturesExtractorORB(const HipDistinctFeaturesExtractorORB &) = delete;
+  HipDistinctFeaturesExtractorORB &operator=(const HipDistinctFeaturesExtractorORB &) = delete;
+  /** the CameraMask bytes every later extract honours (W x H, 0 = masked), nullptr = none; or the level-0 mask a pyramid keeps */
+  void setMask(const uint8_t *mask) { check(dsopp_hip_orb_detector_set_mask(d_, mask)); }
+  void setMaskFromPyramid(const DevicePyramid &pyramid) { check(dsopp_hip_orb_detector_set_mask_from_pyramid(d_, pyramid.handle())); }
+  /** extract(image, mask, ...) of a continuous 8-bit Mat, or of the grey image a pyramid keeps (CameraFeatures::frameData()) */
+  std::vector<Feature> extract(const uint8_t *image) {
+    return run([&](int32_t capacity, int32_t *n) {
+      return dsopp_hip_orb_detector_detect(d_, image, static_cast<size_t>(width_), capacity, xy_.data(), level_.data(), response_.data(), n);
+    });
+  }
+  std::vector<Feature> extract(const DevicePyramid &frame) {
+    return run([&](int32_t capacity, int32_t *n) {
+      return dsopp_hip_orb_detector_detect_from_pyramid(d_, frame.handle(), capacity, xy_.data(), level_.data(), response_.data(), n);
+    });
+  }
+  size_t featureCount() const { return number_of_features_; }
+  /** level and Harris response of the last extract, per feature */
+  const std::vector<int32_t> &levels() const { return level_; }
+  const std::vector<float> &responses() const { return response_; }
+  dsopp_hip_orb_detector *handle() const { return d_; }
+
+ private:
+  void reserve(size_t n) {
+    xy_.resize(2 * n);
+    level_.resize(n);
+    response_.resize(n);
+  }
+  /** `call(capacity, &n)`, once more with the room reported when the capacity was too small */
+  template <typename Call>
+  std::vector<Feature> run(Call call) {
+    reserve(capacity_ > level_.size() ? capacity_ : level_.size());
+    int32_t n = 0;
+    int rc = call(static_cast<int32_t>(level_.size()), &n);
+    if (rc == DSOPP_HIP_ERR_CAPACITY) {
+      capacity_ = static_cast<size_t>(n);
+      reserve(capacity_);
+      rc = call(static_cast<int32_t>(level_.size()), &n);
+    }
+    check(rc);
+    capacity_ = level_.size();
+    std::vector<Feature> out(static_cast<size_t>(n));
+    for (size_t i = 0; i < out.size(); ++i) out[i] = {xy_[2 * i], xy_[2 * i + 1]};
+    level_.resize(out.size());
+    response_.resize(out.size());
+    return out;
+  }
+  dsopp_hip_orb_detector *d_ = nullptr;
+  int width_;
+  size_t number_of_features_, capacity_ = 0;
+  std::vector<float> xy_, response_;
+  std::vector<int32_t> level_;
+};
+
+/** features::findCorrespondences (src/feature_based_slam/features/src/correspondences_finder.cpp:7-18) with features::OpticalFlowMatch
+ *  as its finder (optical_flow.cpp:11-56), whole, on the device: without features of a previous frame the detection of image_to and no
+ *  correspondences; otherwise the flow's feature and correspondence per status != 0, in the order of features_from, then a refill from
+ *  a fresh detection of image_to: new[indices[i]] while fewer than featureCount() are held, indices = the std::shuffle of 0 .. m - 1
+ *  under a default-constructed std::default_random_engine (dsopp_hip_features_shuffle_order).  No duplicate test, as in the reference.
+ *  image_from is set once (monocular_initializer.cpp:47-51).  The random subset a refill draws differs from the reference's because the
+ *  order of the detections does (HipDistinctFeaturesExtractorORB). */
+class HipFindCorrespondences {
+ public:
+  using Feature = std::array<float, 2>;
+  using Result = HipOpticalFlowMatch::Result;
+  HipFindCorrespondences(int width, int height, size_t number_of_features = 500, int device = 0, void *stream = nullptr, int levels = 5,
+                         int edge_threshold = 31, int fast_threshold = 20)
+      : flow_(width, height, device, stream), extractor_(width, height, number_of_features, device, stream, levels, edge_threshold, fast_threshold) {}
+  void setImageFrom(const uint8_t *image_from) { flow_.setImageFrom(image_from); }
+  void setImageFrom(const DevicePyramid &frame_from) { flow_.setImageFrom(frame_from); }
+  /** features_from == nullptr: the reference frame does not exist yet */
+  Result find(const std::vector<Feature> *features_from, const uint8_t *image_to) { return findIn(features_from, image_to); }
+  Result find(const std::vector<Feature> *features_from, const DevicePyramid &frame_to) { return findIn(features_from, frame_to); }
+  HipOpticalFlowMatch &flow() { return flow_; }
+  HipDistinctFeaturesExtractorORB &extractor() { return extractor_; }
+
+ private:
+  template <typename Image>
+  Result findIn(const std::vector<Feature> *features_from, const Image &image_to) {
+    if (!features_from) {
+      Result r;
+      r.features = extractor_.extract(image_to);
+      return r;
+    }
+    Result r = flow_.match(*features_from, image_to);
+    const std::vector<Feature> fresh = extractor_.extract(image_to);
+    std::vector<int32_t> indices(fresh.size());
+    if (!fresh.empty()) check(dsopp_hip_features_shuffle_order(static_cast<int32_t>(fresh.size()), indices.data()));
+    for (size_t i = 0; r.features.size() < extractor_.featureCount() && i < indices.size(); ++i)
+      r.features.push_back(fresh[static_cast<size_t>(indices[i])]);
+    return r;
+  }
+  HipOpticalFlowMatch flow_;
+  HipDistinctFeaturesExtractorORB extractor_;
 };
 
 /** FrameStatus of the initialiser's keyframe strategies (initialization_strategy/frame_status.hpp) */

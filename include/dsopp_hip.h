@@ -259,8 +259,8 @@ int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out
  * cv::calcOpticalFlowPyrLK(image_from, image_to, pts_from, pts_to, status, err, Size(15, 15), 3, TermCriteria(COUNT + EPS, 10, 0.01))
  * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
  * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
- * Not built: the refill of lost features from a fresh ORB extraction (optical_flow.cpp:44-53) and ORB itself (estimateSO3inlierCount is
- * dsopp_hip_rotation_ransac_* below), initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ * The refill of lost features from a fresh ORB detection (optical_flow.cpp:44-53) is dsopp_hip_orb_detector_* below, and
+ * estimateSO3inlierCount dsopp_hip_rotation_ransac_*.  Not built: initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
  *
  * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
  * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
@@ -331,11 +331,91 @@ int dsopp_hip_flow_tracker_track_from_pyramid(dsopp_hip_flow_tracker *t, const d
 int dsopp_hip_flow_tracker_get_level(dsopp_hip_flow_tracker *t, int which, int level, uint8_t *image_out, int16_t *deriv_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ORB keypoints of the bootstrap: the detection that gives the first frame its features and refills, on every later frame, the
+ * features the flow lost (replaces the cv::ORB::create(nfeatures, 2.0f, 5)->detect of DistinctFeaturesExtractorORB —
+ * src/feature_based_slam/features/src/distinct_features_extractor_orb.cpp:11-38 —, which features::OpticalFlowMatch —
+ * src/feature_based_slam/features/src/optical_flow.cpp:44-53 — and the first frame — correspondences_finder.cpp:12-15 — run;
+ * MonocularInitializer::tick — monocular_initializer.cpp:47-53 — and the feature-based tracker — add_new_frame.cpp:31 — go through
+ * them on every frame; ORB is the one extractor the factory knows, feature_based_slam/tracker/src/fabric.cpp:97-102)
+ * Only keypoint.pt is used by the reference, so only positions (with level and response) are computed.  Not built: descriptors and
+ * angles, scale factors other than 2, FAST_SCORE, a dsopp_hip_pyramid_group_* form, the ORB brute-force matcher (features/src/orb.cpp).
+ *
+ * The arithmetic is fixed here, a restatement of OpenCV 4's orb.cpp, fast.cpp and keypoint.cpp; tests/orb_model.py is its NumPy form
+ * and the device is held to it bit for bit.  Parity with OpenCV itself is not pinned.  All integers are exact; every float step is one
+ * IEEE binary32 operation in the written order, never fused; cvRound rounds to nearest, ties to even.  e = edge_threshold, t =
+ * fast_threshold.
+ *   1. Features per level: factor = 0.5f; nd = nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nlevels)) in float;
+ *      for l < nlevels - 1: n_l = cvRound(nd), nd *= factor; n_last = max(nfeatures - sum n_l, 0).  (500 over 5: 258, 129, 65, 32, 16.)
+ *   2. Levels: level 0 is the image; level l is cvRound(W / 2^l) x cvRound(H / 2^l), the linear resize of level l - 1 in the arithmetic
+ *      of dsopp_hip_transformer_create (cv::resize INTER_LINEAR, 11-bit weights); at a ratio of exactly 2 that is (a + b + c + d + 2) >> 2.
+ *      Deviation: OpenCV resizes these levels with INTER_LINEAR_EXACT; the two agree where every halving is exact (every shipped
+ *      configuration: ImageCropper leaves multiples of 2^4) and may differ by a grey level elsewhere.
+ *   3. Masks: level 0 is the mask bytes; level l the same resize of level l - 1's bytes followed by m > 254 ? m : 0
+ *      (threshold(254, THRESH_TOZERO)).  A point is masked where the byte at its pixel is 0.
+ *   4. FAST-9/16 per level, centres 3 <= x < w - 3, 3 <= y < h - 3, ring (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3)
+ *      (-1,-3) (-2,-2) (-3,-1) (-3,0) (-3,1) (-2,2) (-1,3): m = the maximum, over the 16 circular arcs of 9 ring pixels and both signs
+ *      s, of the arc's minimum of s (p_k - v).  A corner iff m > t, its score m - 1; every other pixel scores 0.
+ *   5. Non-maximum suppression: a corner survives iff its score is strictly greater than the scores of its 8 neighbours (masked
+ *      corners take part).
+ *   6. Filters: survivors on a masked pixel are dropped, and so are those outside e <= x < w - e, e <= y < h - e (a level with
+ *      w <= 2 e or h <= 2 e keeps nothing).
+ *   7. First cut, retainBest(2 n_l): when more than 2 n_l remain, n_l = 0 keeps none, else every point whose score is >= the
+ *      2 n_l-th largest score stays (ties at the boundary all stay).
+ *   8. Harris response at (x, y) of the level image p, over the 7 x 7 block centred there:
+ *      Ix = 2 (p[y][x+1] - p[y][x-1]) + (p[y-1][x+1] - p[y-1][x-1]) + (p[y+1][x+1] - p[y+1][x-1]), Iy its transpose;
+ *      a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy in int32; scale = 1.f / (4 * 7 * 255.f), s4 = scale * scale * scale * scale (left to
+ *      right); r = (((float)a (float)b - (float)c (float)c) - (0.04f ((float)a + (float)b)) ((float)a + (float)b)) s4.
+ *   9. Second cut, retainBest(n_l) on r by the rule of 7 (float ties all stay; -0 equals +0).
+ *  10. Output (x 2^l, y 2^l) as floats with l and r, in the canonical order: levels ascending, within a level ascending y, then x.
+ *      Deviation: the reference's order is what std::nth_element and std::partition leave inside retainBest; the set is the same, the
+ *      random subset a refill draws from it is not.
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_orb_detector dsopp_hip_orb_detector;
+/* step 1 (orb.cpp's computeKeyPoints; distinct_features_extractor_orb.cpp:13), out = nlevels int32: host arithmetic, the one entry
+ * point of this section that needs no device.  DSOPP_HIP_ERR_INVALID_ARGUMENT: nfeatures < 0, nlevels outside 1 .. 8. */
+int dsopp_hip_orb_features_per_level(int nfeatures, int nlevels, int32_t *out);
+/* The detector of one image size (DistinctFeaturesExtractorORB's constructor, distinct_features_extractor_orb.cpp:11-14).  The
+ * reference's values: nfeatures 500 (YAML number_of_features, fabric.cpp:97-102), nlevels 5, edge_threshold 31, fast_threshold 20.
+ * `stream` is a hipStream_t (NULL = a stream of its own); all work of the object runs on it.  Its internal lists hold ceil(w / 2) *
+ * ceil(h / 2) survivors per level, the most step 5 can leave: no input overflows them.  DSOPP_HIP_ERR_INVALID_ARGUMENT: nlevels
+ * outside 1 .. 8, edge_threshold < 4 (the Harris block must stay inside the level), fast_threshold outside 0 .. 255, nfeatures < 0,
+ * width or height outside 1 .. 65535, a size whose last level would be empty. */
+int dsopp_hip_orb_detector_create(int width, int height, int nfeatures, int nlevels, int edge_threshold, int fast_threshold, int device, void *stream,
+                                  dsopp_hip_orb_detector **out);
+void dsopp_hip_orb_detector_destroy(dsopp_hip_orb_detector *d);
+/* The mask of every later detect (the `mask` of extract(), distinct_features_extractor_orb.cpp:16-24): width x height bytes, dense,
+ * copied before the call returns, which only enqueues the mask levels of step 3.  NULL = no mask. */
+int dsopp_hip_orb_detector_set_mask(dsopp_hip_orb_detector *d, const uint8_t *mask_host);
+/* The same from the level-0 mask `pyramid` kept from its last dsopp_hip_pyramid_set_semantics, taken as validity: a non-zero byte is
+ * 255.  A mask byte of 1 .. 254 is valid at level 0 and, by the threshold of step 3, masks every pixel of the levels above that it
+ * touches; a caller whose mask holds such bytes and wants that hands the bytes over with set_mask.  Only enqueues, behind the
+ * pyramid's ready event.  DSOPP_HIP_ERR_INVALID_ARGUMENT when the pyramid never had set_semantics, or its size or device is not the
+ * detector's. */
+int dsopp_hip_orb_detector_set_mask_from_pyramid(dsopp_hip_orb_detector *d, const dsopp_hip_pyramid *pyramid);
+/* detect (distinct_features_extractor_orb.cpp:16-38; optical_flow.cpp:44-46; correspondences_finder.cpp:12-15), blocking: *n
+ * detections in the canonical order, xy n x 2 floats, level n int32, response n floats.  `stride` = bytes between rows, >= width.  The
+ * results come back through one pinned block with one wait (a second only when boundary ties keep more than nfeatures + 256).  More
+ * detections than `capacity`: DSOPP_HIP_ERR_CAPACITY, *n = the count needed, nothing else written. */
+int dsopp_hip_orb_detector_detect(dsopp_hip_orb_detector *d, const uint8_t *image_host, size_t stride, int32_t capacity, float *xy, int32_t *level,
+                                  float *response, int32_t *n);
+/* same, the image in HBM (any alignment) / the grey image a pyramid keeps, with the conventions and errors of
+ * dsopp_hip_flow_tracker_set_reference_device and _from_pyramid */
+int dsopp_hip_orb_detector_detect_device(dsopp_hip_orb_detector *d, const void *image_dev, size_t stride, int32_t capacity, float *xy, int32_t *level,
+                                         float *response, int32_t *n);
+int dsopp_hip_orb_detector_detect_from_pyramid(dsopp_hip_orb_detector *d, const dsopp_hip_pyramid *pyramid, int32_t capacity, float *xy,
+                                               int32_t *level, float *response, int32_t *n);
+/* For tests, blocking: of level `level` the image and the FAST score plane (step 4, before the suppression) of the last detect, and
+ * the mask bytes (all 255 without a mask), each w_l x h_l dense bytes; any pointer may be NULL, *w and *h take the level's size.
+ * DSOPP_HIP_ERR_STATE for an image or score plane before the first detect. */
+int dsopp_hip_orb_detector_get_level(dsopp_hip_orb_detector *d, int level, uint8_t *image_out, uint8_t *mask_out, uint8_t *score_out, int *w, int *h);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * The bootstrap's standstill test: the pure-rotation RANSAC over the matches of two frames (replaces estimateSO3inlierCount<3> —
  * src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48 —, that is ransac::ransac — src/ransac/include/ransac/ransac.hpp:27-56 —
  * over the three-point PureRorationSolver — src/energy/n_point_solvers/src/pure_rotation_estimator.cpp:14-67 —, which
  * MonocularInitializer::tick — monocular_initializer.cpp:71-94 — and the feature-based tracker — add_new_frame.cpp:36-45 — run on every
- * frame).  Not built: the essential-matrix and PnP RANSACs, triangulation, the refinement, ORB, the SimpleRadialCamera instantiation.
+ * frame).  Not built: the essential-matrix and PnP RANSACs, triangulation, the refinement, ORB descriptors and matching, the SimpleRadialCamera instantiation.
  *
  * The arithmetic is fixed here; tests/rotation_ransac_model.py is its NumPy form.  Everything is binary64 (the reference's Precision);
  * float points of the flow tracker are widened by the caller.
