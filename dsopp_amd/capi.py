@@ -39,6 +39,37 @@ class RotationRansacResult(C.Structure):
                 ("rotation", C.c_double * 9)]
 
 
+class GeometricBAProblem(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("num_frames", C.c_int32), ("num_landmarks", C.c_int32), ("num_observations", C.c_int32), ("reserved", C.c_int32),
+                ("poses", C.c_void_p), ("positions", C.c_void_p), ("landmark_offsets", C.c_void_p), ("obs_frame", C.c_void_p),
+                ("obs_xy", C.c_void_p)]
+
+
+class GeometricBAOptions(C.Structure):
+    _fields_ = [("a", C.c_double), ("lambda_0", C.c_double), ("function_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("decrease_factor", C.c_double), ("increase_factor", C.c_double), ("max_iterations", C.c_int32), ("iteration_group", C.c_int32)]
+
+
+class GeometricBAResult(C.Structure):
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_lambda", C.c_double), ("valid_residuals", C.c_int32),
+                ("iterations", C.c_int32), ("accepted_steps", C.c_int32), ("converged", C.c_int32), ("reason", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GeometricBATrace(C.Structure):
+    _fields_ = [("cost_before", C.c_double), ("cost_candidate", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+GEOMETRIC_BA_DEBUG_FIELDS = ("obs_valid", "obs_residual", "obs_weight", "landmark_H", "landmark_b", "reduced_H", "reduced_b", "pose_step",
+                             "system_lambda", "candidate_poses", "candidate_positions", "trace")
+
+
+class GeometricBADebug(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in GEOMETRIC_BA_DEBUG_FIELDS]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 # every symbol include/dsopp_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -92,6 +123,8 @@ SYMBOLS = [
     "dsopp_hip_orb_detector_set_mask_from_pyramid", "dsopp_hip_orb_detector_detect", "dsopp_hip_orb_detector_detect_device",
     "dsopp_hip_orb_detector_detect_from_pyramid", "dsopp_hip_orb_detector_get_level",
     "dsopp_hip_rotation_ransac_create", "dsopp_hip_rotation_ransac_destroy", "dsopp_hip_rotation_ransac_estimate",
+    "dsopp_hip_geometric_ba_default_options", "dsopp_hip_geometric_ba_create", "dsopp_hip_geometric_ba_destroy", "dsopp_hip_geometric_ba_evaluate",
+    "dsopp_hip_geometric_ba_solve", "dsopp_hip_geometric_ba_triangulate", "dsopp_hip_geometric_ba_flag_outliers",
 ]
 
 _lib = None
@@ -662,6 +695,107 @@ class RotationRansac:
         if with_hypotheses:
             out.update(hyp_counts=hyp[0], hyp_rotations=hyp[1], hyp_valid=hyp[2])
         return out
+
+
+def default_geometric_ba_options(**kw) -> GeometricBAOptions:
+    o = GeometricBAOptions()
+    lib().dsopp_hip_geometric_ba_default_options(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+class GeometricBA:
+    """The bootstrap's geometric bundle adjustment on the device (dsopp_hip_geometric_ba): evaluate, the LM solve, triangulation and pruning
+    of one problem: camera = (fx, fy, cx, cy, width, height), poses (F, 12) float64 (R row-major, t of t_agent_world), positions (L, 3),
+    landmark_offsets (L + 1,) int32, obs_frame (M,) int32, obs_xy (M, 2): the observations grouped by landmark."""
+
+    def __init__(self, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.device = device
+        _chk(lib().dsopp_hip_geometric_ba_create(int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_geometric_ba_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def problem(camera, poses, positions, landmark_offsets, obs_frame, obs_xy):
+        """(GeometricBAProblem, the arrays it points into: poses and positions are the copies a call updates)"""
+        fx, fy, cx, cy, width, height = camera
+        arrays = (np.array(poses, dtype=np.float64, order="C").reshape(-1, 12), np.array(positions, dtype=np.float64, order="C").reshape(-1, 3),
+                  np.ascontiguousarray(landmark_offsets, dtype=np.int32), np.ascontiguousarray(obs_frame, dtype=np.int32),
+                  np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2))
+        assert len(arrays[2]) == len(arrays[1]) + 1 and len(arrays[3]) == len(arrays[4]), [a.shape for a in arrays]
+        pr = GeometricBAProblem(fx, fy, cx, cy, int(width), int(height), len(arrays[0]), len(arrays[1]), len(arrays[3]), 0,
+                                *[a.ctypes.data for a in arrays])
+        return pr, arrays
+
+    def evaluate(self, camera, poses, positions, landmark_offsets, obs_frame, obs_xy, a=1.5, with_observations=False):
+        """dict: cost, valid_residuals, and with with_observations obs_valid (M,) uint8, obs_residual (M, 2), obs_weight (M,); blocking"""
+        pr, keep = self.problem(camera, poses, positions, landmark_offsets, obs_frame, obs_xy)
+        m = pr.num_observations
+        cost, nvalid = C.c_double(), C.c_int32()
+        obs = (np.zeros(m, np.uint8), np.zeros((m, 2)), np.zeros(m)) if with_observations else (None, None, None)
+        _chk(lib().dsopp_hip_geometric_ba_evaluate(self._h, C.byref(pr), C.c_double(a), C.byref(cost), C.byref(nvalid), _p(obs[0], np.uint8),
+                                                   _p(obs[1]), _p(obs[2])))
+        out = {"cost": cost.value, "valid_residuals": nvalid.value}
+        if with_observations:
+            out.update(obs_valid=obs[0], obs_residual=obs[1], obs_weight=obs[2])
+        return out
+
+    def solve(self, camera, poses, positions, landmark_offsets, obs_frame, obs_xy, options=None, debug=False, **option_fields):
+        """The LM solve.  Returns a dict: poses (F, 12), positions (L, 3), the result record's fields, and with debug the optional outputs of
+        dsopp_hip_geometric_ba_debug (reduced_H (n, n), trace = the records of the iterations run, ...); blocking"""
+        pr, keep = self.problem(camera, poses, positions, landmark_offsets, obs_frame, obs_xy)
+        opt = options if options is not None else default_geometric_ba_options()
+        for k, v in option_fields.items():
+            setattr(opt, k, v)
+        res = GeometricBAResult()
+        f, l, m = pr.num_frames, pr.num_landmarks, pr.num_observations
+        n = max(6 * (f - 1) - 1, 0)
+        dbg, bufs = None, {}
+        if debug:
+            bufs = dict(obs_valid=np.zeros(m, np.uint8), obs_residual=np.zeros((m, 2)), obs_weight=np.zeros(m), landmark_H=np.zeros((l, 6)),
+                        landmark_b=np.zeros((l, 3)), reduced_H=np.zeros((n, n)), reduced_b=np.zeros(n), pose_step=np.zeros(n),
+                        system_lambda=np.zeros(1), candidate_poses=np.zeros((f, 12)), candidate_positions=np.zeros((l, 3)),
+                        trace=np.zeros(max(int(opt.max_iterations), 1) * C.sizeof(GeometricBATrace), np.uint8))
+            dbg = GeometricBADebug(*[bufs[name].ctypes.data for name in GEOMETRIC_BA_DEBUG_FIELDS])
+        _chk(lib().dsopp_hip_geometric_ba_solve(self._h, C.byref(pr), C.byref(opt), C.byref(res), C.byref(dbg) if debug else None))
+        out = {"poses": keep[0], "positions": keep[1]}
+        out.update({name: getattr(res, name) for name, _ in GeometricBAResult._fields_ if name != "reserved"})
+        if debug:
+            records = (GeometricBATrace * res.iterations).from_buffer_copy(bufs["trace"][:res.iterations * C.sizeof(GeometricBATrace)].tobytes())
+            bufs["trace"] = [(t.cost_before, t.cost_candidate, t.accepted, t.lambda_) for t in records]
+            bufs["system_lambda"] = float(bufs["system_lambda"][0])
+            out.update(bufs)
+        return out
+
+    def triangulate(self, camera, poses, positions, landmark_offsets, obs_frame, obs_xy, has_position, min_number_of_projections=4,
+                    retriangulation=False):
+        """(triangulated (L,) uint8, positions (L, 3): the rows of the triangulated landmarks rewritten, the others as given); blocking"""
+        pr, keep = self.problem(camera, poses, positions, landmark_offsets, obs_frame, obs_xy)
+        has = np.ascontiguousarray(has_position, dtype=np.uint8)
+        assert len(has) == pr.num_landmarks, (len(has), pr.num_landmarks)
+        done = np.zeros(pr.num_landmarks, np.uint8)
+        _chk(lib().dsopp_hip_geometric_ba_triangulate(self._h, C.byref(pr), _p(has, np.uint8), int(min_number_of_projections),
+                                                      int(bool(retriangulation)), _p(done, np.uint8)))
+        return done, keep[1]
+
+    def flag_outliers(self, camera, poses, positions, landmark_offsets, obs_frame, obs_xy, outlier_threshold=0.5):
+        """flags (M,) uint8: 1 = removeOutliers would drop the projection; blocking"""
+        pr, keep = self.problem(camera, poses, positions, landmark_offsets, obs_frame, obs_xy)
+        flags, count = np.zeros(pr.num_observations, np.uint8), C.c_int32()
+        _chk(lib().dsopp_hip_geometric_ba_flag_outliers(self._h, C.byref(pr), C.c_double(outlier_threshold), _p(flags, np.uint8), C.byref(count)))
+        assert count.value == int(flags.sum())
+        return flags
 
 
 class DepthMaps:

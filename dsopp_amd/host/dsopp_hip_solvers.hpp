@@ -16,13 +16,16 @@
 // Ownership mirrors the reference: the solver copies what it needs at pushFrame, image pyramids are borrowed (they must
 // outlive the frame's stay in the solver, as the keyframe's PixelMap does there), single-threaded use per object.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdlib>
+#include <deque>
 #include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include <limits>
 #include <functional>
@@ -1240,6 +1243,171 @@ class HipRotationStandstill {
 
  private:
   dsopp_hip_rotation_ransac *r_ = nullptr;
+  int width_, height_;
+};
+
+/** A frame of the bootstrap's track (feature_based_slam::track::Frame): t_world_agent as 12 doubles, R row-major then t */
+struct RefineFrame {
+  size_t frame_id = 0;
+  std::array<double, 12> t_world_agent{1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  bool initialized = false;
+};
+/** A landmark of the bootstrap's track (track::Landmark): an optional position and its projections (frame id, pixel) */
+struct RefineLandmark {
+  bool has_position = false;
+  std::array<double, 3> position{0, 0, 0};
+  std::vector<std::pair<size_t, Vector2>> projections;
+  const Vector2 *projection(size_t frame_id) const {
+    for (const auto &p : projections)
+      if (p.first == frame_id) return &p.second;
+    return nullptr;
+  }
+};
+
+/** The refinement of the bootstrap's track on the device, the three steps MonocularTracker runs after estimateSE3PnP
+ *  (src/feature_based_slam/tracker/src/monocular_tracker.cpp:54-68): triangulatePoints (triangulate_points.cpp:47-71),
+ *  optimizeTransformations (refine_track.cpp:16-83) and removeOutliers (remove_outliers.cpp:15-47), over dsopp_hip_geometric_ba.
+ *  The object takes at most 16 frames per call (DSOPP_HIP_ERR_CAPACITY beyond): triangulatePoints reads every frame it is given, the
+ *  other two the initialised ones among the last number_of_frames.
+ *  Deviations: the solve is the library's LM over the Huber IRLS blocks, not Ceres's trust region with its loss corrector (include/dsopp_hip.h);
+ *  with fewer than two initialised frames in the window optimizeTransformations changes nothing (Ceres would still move the landmarks
+ *  against the one fixed frame); a second local frame whose t_agent_world has no translation (|t_1| = 0: no direction to hold) is
+ *  DSOPP_HIP_ERR_INVALID_ARGUMENT. */
+class HipRefineTrack {
+ public:
+  /** width, height: the image size of `model`, which bounds the ROI */
+  HipRefineTrack(int width, int height, int device = 0, void *stream = nullptr) : width_(width), height_(height) {
+    check(dsopp_hip_geometric_ba_create(device, stream, &b_));
+  }
+  ~HipRefineTrack() { dsopp_hip_geometric_ba_destroy(b_); }
+  HipRefineTrack(const HipRefineTrack &) = delete;
+  HipRefineTrack &operator=(const HipRefineTrack &) = delete;
+
+  /** triangulatePoints(landmarks, frames, model, min_number_of_projections, retriangulation); returns how many positions were set */
+  size_t triangulatePoints(std::vector<RefineLandmark> &landmarks, const std::deque<RefineFrame> &frames, const PinholeModel &model,
+                           size_t min_number_of_projections, bool retriangulation) {
+    std::vector<size_t> local;  // every frame takes part, initialised or not, as in the reference
+    for (size_t i = 0; i < frames.size(); ++i) local.push_back(i);
+    std::vector<size_t> chosen(landmarks.size());
+    for (size_t l = 0; l < landmarks.size(); ++l) chosen[l] = l;
+    Problem p = gather(landmarks, frames, local, chosen, model, false);
+    std::vector<uint8_t> has(chosen.size()), done(chosen.size(), 0);
+    for (size_t k = 0; k < chosen.size(); ++k) has[k] = landmarks[chosen[k]].has_position ? 1 : 0;
+    check(dsopp_hip_geometric_ba_triangulate(b_, &p.c, has.data(), static_cast<int>(min_number_of_projections), retriangulation ? 1 : 0, done.data()));
+    size_t count = 0;
+    for (size_t k = 0; k < chosen.size(); ++k)
+      if (done[k]) {
+        RefineLandmark &lm = landmarks[chosen[k]];
+        lm.has_position = true;
+        for (size_t r = 0; r < 3; ++r) lm.position[r] = p.positions[3 * k + r];
+        ++count;
+      }
+    return count;
+  }
+
+  /** optimizeTransformations<PinholeCamera, false>(landmarks, ..., frames, reprojection_threshold, number_of_frames_to_optimize, ...):
+   *  the window of the last frames, the landmarks with a position and a projection in it (exists_in_window), the initialised frames as
+   *  local frames, write-back of poses and positions.  `options` (NULL = the defaults with a = reprojection_threshold) */
+  dsopp_hip_geometric_ba_result optimizeTransformations(std::vector<RefineLandmark> &landmarks, std::deque<RefineFrame> &frames, const PinholeModel &model,
+                                                        double reprojection_threshold = 1.5, size_t number_of_frames_to_optimize = 10,
+                                                        const dsopp_hip_geometric_ba_options *options = nullptr) {
+    const size_t number_of_frames = std::min(frames.size(), number_of_frames_to_optimize), start = frames.size() - number_of_frames;
+    std::vector<size_t> chosen, local;
+    for (size_t l = 0; l < landmarks.size(); ++l) {
+      bool exists_in_window = false;
+      for (size_t i = start; i < frames.size(); ++i)
+        if (landmarks[l].has_position && landmarks[l].projection(frames[i].frame_id)) exists_in_window = true;
+      if (exists_in_window) chosen.push_back(l);
+    }
+    for (size_t i = start; i < frames.size(); ++i)
+      if (frames[i].initialized) local.push_back(i);
+    dsopp_hip_geometric_ba_result result{};
+    if (local.size() < 2) return result;
+    Problem p = gather(landmarks, frames, local, chosen, model, true);
+    dsopp_hip_geometric_ba_options o;
+    if (options) {
+      o = *options;
+    } else {
+      dsopp_hip_geometric_ba_default_options(&o);
+      o.a = reprojection_threshold;
+    }
+    check(dsopp_hip_geometric_ba_solve(b_, &p.c, &o, &result, nullptr));
+    for (size_t f = 0; f < local.size(); ++f) frames[local[f]].t_world_agent = inverse(p.poses.data() + 12 * f);
+    for (size_t k = 0; k < chosen.size(); ++k)
+      for (size_t r = 0; r < 3; ++r) landmarks[chosen[k]].position[r] = p.positions[3 * k + r];
+    return result;
+  }
+
+  /** removeOutliers(landmarks, model, frames, last_frames_to_filter, outlier_threshold); returns how many projections were removed */
+  size_t removeOutliers(std::vector<RefineLandmark> &landmarks, const std::deque<RefineFrame> &frames, const PinholeModel &model,
+                        size_t last_frames_to_filter = 10, double outlier_threshold = 0.5) {
+    const size_t number_of_frames = std::min(frames.size(), last_frames_to_filter), start = frames.size() - number_of_frames;
+    std::vector<size_t> chosen, local;
+    for (size_t i = start; i < frames.size(); ++i)
+      if (frames[i].initialized) local.push_back(i);
+    for (size_t l = 0; l < landmarks.size(); ++l)
+      if (landmarks[l].has_position) chosen.push_back(l);
+    if (local.empty()) return 0;
+    Problem p = gather(landmarks, frames, local, chosen, model, true);
+    std::vector<uint8_t> flags(p.obs_frame.size(), 0);
+    int32_t flagged = 0;
+    check(dsopp_hip_geometric_ba_flag_outliers(b_, &p.c, outlier_threshold, flags.data(), &flagged));
+    for (size_t k = 0; k < chosen.size(); ++k) {
+      RefineLandmark &lm = landmarks[chosen[k]];
+      for (int32_t o = p.offsets[k]; o < p.offsets[k + 1]; ++o)
+        if (flags[static_cast<size_t>(o)]) {
+          const size_t frame_id = frames[local[static_cast<size_t>(p.obs_frame[static_cast<size_t>(o)])]].frame_id;
+          lm.projections.erase(std::remove_if(lm.projections.begin(), lm.projections.end(), [&](const auto &q) { return q.first == frame_id; }),
+                               lm.projections.end());
+        }
+    }
+    return static_cast<size_t>(flagged);
+  }
+  dsopp_hip_geometric_ba *handle() const { return b_; }
+
+  /** the inverse of a rigid transform given as 12 doubles */
+  static std::array<double, 12> inverse(const double *T) {
+    std::array<double, 12> out{};
+    for (size_t r = 0; r < 3; ++r) {
+      for (size_t c = 0; c < 3; ++c) out[3 * r + c] = T[3 * c + r];
+      out[9 + r] = -(T[r] * T[9] + T[3 + r] * T[10] + T[6 + r] * T[11]);
+    }
+    return out;
+  }
+
+ private:
+  struct Problem {
+    std::vector<double> poses, positions, obs_xy;
+    std::vector<int32_t> offsets, obs_frame;
+    dsopp_hip_geometric_ba_problem c;
+  };
+  /** the problem of local frames `local` (indices into `frames`) and landmarks `chosen`: t_agent_world per local frame, the observations
+   *  grouped by landmark in the local frames' order */
+  Problem gather(const std::vector<RefineLandmark> &landmarks, const std::deque<RefineFrame> &frames, const std::vector<size_t> &local,
+                 const std::vector<size_t> &chosen, const PinholeModel &model, bool positions_required) const {
+    Problem p;
+    for (size_t i : local) {
+      const std::array<double, 12> t_agent_world = inverse(frames[i].t_world_agent.data());
+      p.poses.insert(p.poses.end(), t_agent_world.begin(), t_agent_world.end());
+    }
+    p.offsets.push_back(0);
+    for (size_t l : chosen) {
+      const RefineLandmark &lm = landmarks[l];
+      for (size_t r = 0; r < 3; ++r) p.positions.push_back(lm.has_position || positions_required ? lm.position[r] : 0.0);
+      for (size_t f = 0; f < local.size(); ++f)
+        if (const Vector2 *xy = lm.projection(frames[local[f]].frame_id)) {
+          p.obs_frame.push_back(static_cast<int32_t>(f));
+          p.obs_xy.push_back((*xy)[0]);
+          p.obs_xy.push_back((*xy)[1]);
+        }
+      p.offsets.push_back(static_cast<int32_t>(p.obs_frame.size()));
+    }
+    p.c = dsopp_hip_geometric_ba_problem{model.fx, model.fy, model.cx, model.cy, width_, height_, static_cast<int32_t>(local.size()),
+                                         static_cast<int32_t>(chosen.size()), static_cast<int32_t>(p.obs_frame.size()), 0, p.poses.data(),
+                                         p.positions.data(), p.offsets.data(), p.obs_frame.data(), p.obs_xy.data()};
+    return p;
+  }
+  dsopp_hip_geometric_ba *b_ = nullptr;
   int width_, height_;
 };
 

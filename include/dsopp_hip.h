@@ -260,7 +260,7 @@ int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out
  * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
  * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
  * The refill of lost features from a fresh ORB detection (optical_flow.cpp:44-53) is dsopp_hip_orb_detector_* below, and
- * estimateSO3inlierCount dsopp_hip_rotation_ransac_*.  Not built: initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ * estimateSO3inlierCount dsopp_hip_rotation_ransac_*, and the refinement behind them dsopp_hip_geometric_ba_*.  Not built: the RANSACs of initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
  *
  * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
  * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
@@ -415,7 +415,8 @@ int dsopp_hip_orb_detector_get_level(dsopp_hip_orb_detector *d, int level, uint8
  * src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48 —, that is ransac::ransac — src/ransac/include/ransac/ransac.hpp:27-56 —
  * over the three-point PureRorationSolver — src/energy/n_point_solvers/src/pure_rotation_estimator.cpp:14-67 —, which
  * MonocularInitializer::tick — monocular_initializer.cpp:71-94 — and the feature-based tracker — add_new_frame.cpp:36-45 — run on every
- * frame).  Not built: the essential-matrix and PnP RANSACs, triangulation, the refinement, ORB descriptors and matching, the SimpleRadialCamera instantiation.
+ * frame).  Not built: the essential-matrix and PnP RANSACs, ORB descriptors and matching, the SimpleRadialCamera instantiation
+ * (triangulation and the refinement are dsopp_hip_geometric_ba_* below).
  *
  * The arithmetic is fixed here; tests/rotation_ransac_model.py is its NumPy form.  Everything is binary64 (the reference's Precision);
  * float points of the flow tracker are widened by the caller.
@@ -463,6 +464,133 @@ int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, 
                                        const double *points_a, const double *points_b, int iterations, const int32_t *samples, double threshold,
                                        double inliers_tolerance, dsopp_hip_rotation_ransac_result *result, int32_t *inlier_indices,
                                        int32_t *hyp_counts, double *hyp_rotations, uint8_t *hyp_valid);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The bootstrap's geometric bundle adjustment: the reprojection-error refinement of the last frames' poses and of every landmark seen in
+ * them, with the triangulation before it and the pruning after it (replaces, per bootstrap frame once the initialiser has succeeded —
+ * src/feature_based_slam/tracker/src/monocular_tracker.cpp:54-68 —, triangulatePoints — triangulate_points.cpp:47-71, triangulation.hpp:52-64 —,
+ * optimizeTransformations — refine_track.cpp:16-83, which runs Ceres SPARSE_SCHUR with a Huber loss through
+ * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  Not built: estimateSE3PnP and the
+ * essential-matrix RANSAC (OpenGV), the SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks, the
+ * two-view triangulatePoints that only initializePoses calls.
+ *
+ * The arithmetic is fixed here; tests/geometric_ba_model.py is its NumPy form.  Everything is binary64.
+ *   Problem: a pinhole camera fx, fy, cx, cy, width, height; F frames, 2 <= F <= 16 (a 17th is DSOPP_HIP_ERR_CAPACITY; the reference uses
+ *     at most 10), each with its t_agent_world (world to camera) as 12 doubles: R row-major, then t; L landmark positions X; M observations
+ *     (frame, landmark, x, y), every (frame, landmark) pair at most once, listed grouped by landmark: landmark l owns observations
+ *     landmark_offsets[l] .. landmark_offsets[l + 1] - 1.  The caller passes the participating frames only, in the reference's order:
+ *     frame 0 is local_frames[0].
+ *   Residual (bundle_adjustment_geometric_cost_functor.hpp:41-60, pinhole_camera.hpp:78-90): p = R_f X_l + t_f,
+ *     q = (fx p_x / p_z + cx, fy p_y / p_z + cy); the observation is valid iff p_z >= 0.001 and roi(q), roi(q) = 4 <= q_x <= width - 5 &&
+ *     4 <= q_y <= height - 5; r = obs - q when valid, else r = 0 with a zero Jacobian.
+ *   Cost: s = |r|^2, rho(s) = s for s <= a^2 and 2 a sqrt(s) - a^2 otherwise (ceres::HuberLoss(a), a = reprojection_threshold = 1.5),
+ *     cost = 1/2 sum rho(s) over the valid observations.  The linearisation is plain IRLS: w = rho'(s) = 1 or a / sqrt(s), blocks J^T w J
+ *     and J^T w r.  Deviation: Ceres also applies its second-order corrector to outliers; that is not built.
+ *   Degrees of freedom (ceres_geometric_bundle_adjustment_solver.cpp:41-53): frame 0 is fixed.  A frame f >= 2 has six, delta = (upsilon,
+ *     omega), T <- T exp(delta) (a right increment, LocalParameterizationSE3), so dp = R (upsilon + omega x X): J_x = -G R with
+ *     G = dq / dp, J_p = J_x [I | -hat(X)].  Frame 1 has five, (alpha, beta, omega): R <- R Exp(omega), and with n = |t_1| on entry and
+ *     d = t_1 / |t_1|: t_1 <- n normalize(d + alpha b1 + beta b2), where k = the first axis with the smallest |d_k|, b1 = normalize(d x e_k),
+ *     b2 = d x b1.  In the six components of a free frame that is upsilon = n R^T (alpha b1 + beta b2): the 6 x 5 basis B through which
+ *     frame 1's blocks pass.  (Ceres spans the same plane with a Householder basis.)  |t_1| = 0 or a non-finite input is
+ *     DSOPP_HIP_ERR_INVALID_ARGUMENT.  Every landmark has three.
+ *   System: H = sum J^T w J, b = sum J^T w r, damped H + lambda diag(H) on pose and landmark blocks alike (for frame 1 the diagonal of
+ *     B^T H_pp B), step (H + lambda D) delta = -b, solved through the Schur complement on the landmarks: with
+ *     L_l L_l^T = H_ll + lambda diag(H_ll), the reduced system is B^T (H_pp - sum_l W_l (L_l L_l^T)^-1 W_l^T) B + lambda diag(B^T H_pp B),
+ *     its right-hand side -B^T (b_p - sum_l W_l (L_l L_l^T)^-1 b_l), in the order (alpha, beta, omega) of frame 1, then (upsilon, omega) of
+ *     frames 2, 3, ...; delta_l = -(L_l L_l^T)^-1 (b_l + sum_f W_lf^T delta_f).  A landmark whose 3 x 3 Cholesky meets a pivot that is <= 0
+ *     or not finite (no valid observation, H_ll = 0, ...) takes no step and adds nothing to the reduced system.  A reduced system whose
+ *     Cholesky meets such a pivot (a free frame without a valid observation, ...) gives no step: the iteration counts as rejected, with
+ *     an infinite candidate cost in the trace.
+ *   Control, the reference's own LM driver (levenberg_marquardt_algorithm.hpp:77-128), not Ceres's trust-region loop: lambda_0 = 1e-4 (the
+ *     reciprocal of Ceres's default radius); E = the cost; the loop runs while iterations remain, nothing has converged and a residual is
+ *     valid.  Per iteration: linearise unless the last step was rejected; solve; E' = the candidate's cost; no valid candidate residual
+ *     ends the loop with the step rejected; |E - E'| / E < function_tolerance converges (accepted or not); E' < E accepts: step norm
+ *     |delta_p|^2 + sum_l |delta_l|^2 (delta_p in the reduced coordinates) < parameter_tolerance * (state norm + parameter_tolerance)
+ *     converges, with the state norm sum over the free frames (|t|^2 + 1) + sum_l |X_l|^2 of the state the step left; lambda /= 2;
+ *     otherwise lambda *= 10 and the Jacobians are kept.  function_tolerance = parameter_tolerance = 1e-10 (the reference's solver
+ *     options), max_iterations 50 (the driver's default).  Parity with Ceres's iteration path is unpinned: only the minimiser is shared.
+ *   Triangulation: for every landmark without a position (all of them with retriangulation) and MORE than min_number_of_projections
+ *     observations (the tracker passes 4): A = sum_i A_i^T A_i, A_i = P_i - v_i v_i^T P_i, P_i the 3 x 4 [R | t] of the observation's
+ *     frame, v_i = normalize((x - cx) / fx, (y - cy) / fy, 1) (no roi test: the reference ignores unproject's result there); X = the
+ *     eigenvector of A's smallest eigenvalue divided by its last entry.  Any backward-stable route serves (the device: cyclic Jacobi);
+ *     the result is unpinned where the two smallest eigenvalues nearly coincide.
+ *   Pruning: observation (f, l) is flagged iff it is not valid or sqrt(|obs - q|^2) > outlier_threshold (0.5, strict).
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_geometric_ba dsopp_hip_geometric_ba;
+typedef struct dsopp_hip_geometric_ba_problem {
+  double fx, fy, cx, cy;
+  int32_t width, height;
+  int32_t num_frames, num_landmarks, num_observations, reserved;
+  double *poses;                   /* num_frames x 12: R row-major, t; solve updates them in place */
+  double *positions;               /* num_landmarks x 3; solve and triangulate update them in place */
+  const int32_t *landmark_offsets; /* num_landmarks + 1, ascending from 0 to num_observations */
+  const int32_t *obs_frame;        /* num_observations, 0 .. num_frames - 1 */
+  const double *obs_xy;            /* num_observations x 2 */
+} dsopp_hip_geometric_ba_problem;
+typedef struct dsopp_hip_geometric_ba_options {
+  double a;                   /* the Huber width, 1.5 */
+  double lambda_0;            /* 1e-4 */
+  double function_tolerance;  /* 1e-10 */
+  double parameter_tolerance; /* 1e-10 */
+  double decrease_factor;     /* lambda is divided by it on accept, 2 */
+  double increase_factor;     /* lambda is multiplied by it on reject, 10 */
+  int32_t max_iterations;     /* 50 */
+  int32_t iteration_group;    /* iterations enqueued between two reads of the state record; 0 = the library's choice */
+} dsopp_hip_geometric_ba_options;
+enum {
+  DSOPP_HIP_GEOMETRIC_BA_FUNCTION_TOLERANCE = 1,
+  DSOPP_HIP_GEOMETRIC_BA_PARAMETER_TOLERANCE = 2,
+  DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL = 4
+};
+typedef struct dsopp_hip_geometric_ba_result {
+  double initial_cost, final_cost, final_lambda;
+  int32_t valid_residuals; /* valid observations at the final state */
+  int32_t iterations;      /* iterations run, accepted or not */
+  int32_t accepted_steps;
+  int32_t converged;       /* a tolerance was reached */
+  int32_t reason;          /* the DSOPP_HIP_GEOMETRIC_BA_* bits that ended the loop; 0 = max_iterations */
+  int32_t reserved;
+} dsopp_hip_geometric_ba_result;
+typedef struct dsopp_hip_geometric_ba_trace {
+  double cost_before, cost_candidate, lambda; /* lambda = the one the iteration's system was damped with */
+  int32_t accepted, reserved;
+} dsopp_hip_geometric_ba_trace;
+/* Optional outputs of solve, each NULL-able, there so that a divergence from the stated arithmetic can be located.  All but the trace and
+ * the candidate belong to the LAST linearisation (the state the last iteration started from): obs_valid (M bytes), obs_residual (M x 2),
+ * obs_weight (M), landmark_H (L x 6: xx xy xz yy yz zz, undamped) and landmark_b (L x 3); reduced_H (n x n, row-major, damped with
+ * *system_lambda), reduced_b (n) and pose_step (n) of the last iteration's solve, n = 6 (F - 1) - 1; candidate_poses (F x 12) and
+ * candidate_positions (L x 3) that iteration evaluated; trace (max_iterations records, result->iterations of them written).  Without an
+ * iteration the system and the step are zero and the candidate is the state. */
+typedef struct dsopp_hip_geometric_ba_debug {
+  uint8_t *obs_valid;
+  double *obs_residual, *obs_weight, *landmark_H, *landmark_b, *reduced_H, *reduced_b, *pose_step, *system_lambda, *candidate_poses, *candidate_positions;
+  dsopp_hip_geometric_ba_trace *trace;
+} dsopp_hip_geometric_ba_debug;
+void dsopp_hip_geometric_ba_default_options(dsopp_hip_geometric_ba_options *options);
+/* `stream` is a hipStream_t (NULL = a stream of its own); all work of the object runs on it.  Its buffers grow with F, L and M. */
+int dsopp_hip_geometric_ba_create(int device, void *stream, dsopp_hip_geometric_ba **out);
+void dsopp_hip_geometric_ba_destroy(dsopp_hip_geometric_ba *b);
+/* Every call below is blocking.  DSOPP_HIP_ERR_CAPACITY: more than 16 frames.  DSOPP_HIP_ERR_INVALID_ARGUMENT: fewer frames than the call
+ * needs (solve 2, the others 1), negative counts, an image without a region of interest, a camera, pose, observation or (where the call
+ * reads them) position that is not finite, offsets that do not ascend from 0 to num_observations, a frame index out of range, a
+ * (frame, landmark) pair listed twice, a NULL required argument, and what each call adds below. */
+/* cost and valid observations of the state as given; one wait.  Optional per-observation outputs as in the debug record. */
+int dsopp_hip_geometric_ba_evaluate(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem, double a, double *cost,
+                                    int32_t *valid_residuals, uint8_t *obs_valid, double *obs_residual, double *obs_weight);
+/* The LM solve; poses and positions are updated in place.  The iterations are enqueued in groups of options->iteration_group with one
+ * wait after each group but the last and one at the end.  Also invalid: |t_1| = 0, an option that is not finite, a <= 0, lambda_0 < 0,
+ * a factor <= 0, max_iterations < 0, iteration_group < 0.  M = 0 returns at once with DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL. */
+int dsopp_hip_geometric_ba_solve(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const dsopp_hip_geometric_ba_options *options,
+                                 dsopp_hip_geometric_ba_result *result, const dsopp_hip_geometric_ba_debug *debug);
+/* has_position, triangulated: num_landmarks bytes.  Writes problem->positions of the landmarks it triangulated (triangulated[l] = 1) and
+ * leaves the others; positions are not read.  Also invalid: min_number_of_projections < 2 (the reference's CHECK_GE).  One wait. */
+int dsopp_hip_geometric_ba_triangulate(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const uint8_t *has_position,
+                                       int min_number_of_projections, int retriangulation, uint8_t *triangulated);
+/* flags: num_observations bytes, 1 = the reference would remove the projection; *flagged (NULL-able) = their number.  Also invalid: a
+ * threshold that is not a number.  One wait. */
+int dsopp_hip_geometric_ba_flag_outliers(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem, double outlier_threshold,
+                                         uint8_t *flags, int32_t *flagged);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
