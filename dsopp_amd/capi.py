@@ -39,6 +39,17 @@ class RotationRansacResult(C.Structure):
                 ("rotation", C.c_double * 9)]
 
 
+class PnpRansacOptions(C.Structure):
+    _fields_ = [("lambda_0", C.c_double), ("function_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("decrease_factor", C.c_double), ("increase_factor", C.c_double), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PnpRansacResult(C.Structure):
+    _fields_ = [("matches", C.c_int32), ("best_iteration", C.c_int32), ("best_solution", C.c_int32), ("ransac_inlier_count", C.c_int32),
+                ("refined_inlier_count", C.c_int32), ("refine_iterations", C.c_int32), ("refine_flags", C.c_int32), ("reserved", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("pose_ransac", C.c_double * 12), ("pose", C.c_double * 12)]
+
+
 class GeometricBAProblem(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
                 ("num_frames", C.c_int32), ("num_landmarks", C.c_int32), ("num_observations", C.c_int32), ("reserved", C.c_int32),
@@ -125,6 +136,8 @@ SYMBOLS = [
     "dsopp_hip_rotation_ransac_create", "dsopp_hip_rotation_ransac_destroy", "dsopp_hip_rotation_ransac_estimate",
     "dsopp_hip_geometric_ba_default_options", "dsopp_hip_geometric_ba_create", "dsopp_hip_geometric_ba_destroy", "dsopp_hip_geometric_ba_evaluate",
     "dsopp_hip_geometric_ba_solve", "dsopp_hip_geometric_ba_triangulate", "dsopp_hip_geometric_ba_flag_outliers",
+    "dsopp_hip_pnp_ransac_default_iterations", "dsopp_hip_pnp_ransac_default_options", "dsopp_hip_pnp_ransac_create", "dsopp_hip_pnp_ransac_destroy",
+    "dsopp_hip_pnp_ransac_estimate",
 ]
 
 _lib = None
@@ -694,6 +707,64 @@ class RotationRansac:
                "matches": res.matches, "rotation": np.array(res.rotation).reshape(3, 3), "inliers": idx[:res.inlier_count].copy()}
         if with_hypotheses:
             out.update(hyp_counts=hyp[0], hyp_rotations=hyp[1], hyp_valid=hyp[2])
+        return out
+
+
+def default_pnp_ransac_options(**kw) -> PnpRansacOptions:
+    o = PnpRansacOptions()
+    lib().dsopp_hip_pnp_ransac_default_options(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def pnp_ransac_default_iterations() -> int:
+    return int(lib().dsopp_hip_pnp_ransac_default_iterations())
+
+
+class PnpRansac:
+    """estimateSE3PnP on the device (dsopp_hip_pnp_ransac): the pose of a bootstrap frame from its landmarks with a position, every
+    three-point hypothesis scored in one launch, the winner refined over its inliers and the inliers selected again.  Poses are world to
+    camera, 12 doubles: R row-major, then t.  The sample triples are the caller's."""
+
+    def __init__(self, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.device = device
+        _chk(lib().dsopp_hip_pnp_ransac_create(int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_pnp_ransac_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate(self, camera, X, obs, samples, threshold_px=0.5, options=None, with_hypotheses=False):
+        """camera = (fx, fy, cx, cy, width, height); X (n, 3) and obs (n, 2) float64; samples (iterations, 3) int32; options: a
+        PnpRansacOptions (None = the defaults).  Returns a dict: the result record's fields (pose_ransac and pose as (12,) arrays),
+        inliers (ascending int32), and with with_hypotheses the per-hypothesis hyp_num_solutions (iterations,), hyp_poses
+        (iterations, 4, 12), hyp_counts (iterations, 4); blocking"""
+        fx, fy, cx, cy, width, height = camera
+        x = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        o = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 2)
+        s = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3)
+        assert len(x) == len(o), (x.shape, o.shape)
+        n, m = len(x), len(s)
+        res = PnpRansacResult()
+        idx = np.zeros(n, np.int32)
+        hyp = (np.zeros(m, np.int32), np.zeros((m, 4, 12)), np.zeros((m, 4), np.int32)) if with_hypotheses else (None, None, None)
+        _chk(lib().dsopp_hip_pnp_ransac_estimate(self._h, C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(width), int(height),
+                                                 n, _p(x), _p(o), m, _p(s, np.int32), C.c_double(threshold_px),
+                                                 C.byref(options) if options is not None else None, C.byref(res), _p(idx, np.int32),
+                                                 _p(hyp[0], np.int32), _p(hyp[1]), _p(hyp[2], np.int32)))
+        out = {name: getattr(res, name) for name, _ in PnpRansacResult._fields_ if name not in ("reserved", "pose_ransac", "pose")}
+        out.update(pose_ransac=np.array(res.pose_ransac), pose=np.array(res.pose), inliers=idx[:res.refined_inlier_count].copy())
+        if with_hypotheses:
+            out.update(hyp_num_solutions=hyp[0], hyp_poses=hyp[1], hyp_counts=hyp[2])
         return out
 
 

@@ -1411,4 +1411,88 @@ class HipRefineTrack {
   int width_, height_;
 };
 
+/** The pose of a bootstrap frame on the device: estimateSE3PnP (src/feature_based_slam/tracker/src/estimate_se3_pnp.cpp:23-77), the step
+ *  MonocularTracker runs ahead of HipRefineTrack's three (monocular_tracker.cpp:54-56) and initializePoses for every intermediate frame
+ *  (initialize_poses.cpp:47-73), over dsopp_hip_pnp_ransac.
+ *  Deviations: the solver is the library's three-point RANSAC with an LM refinement, not OpenGV's EPnP RANSAC (include/dsopp_hip.h);
+ *  every hypothesis is scored, there is no adaptive stop; the sample triples come from std::rand(), the sampler the rotation RANSAC
+ *  mirrors, not from OpenGV's own generator. */
+class HipEstimateSE3PnP {
+ public:
+  struct Result {
+    size_t inliers, matches;  // estimateSE3PnP's pair: RANSAC's inliers (not the re-selected ones) and the matches
+    dsopp_hip_pnp_ransac_result record;
+    std::vector<size_t> inlier_landmarks;  // the landmarks that keep their projection: the refined pose's inliers, ascending
+  };
+  /** width, height: the image size of `model`, which bounds the ROI */
+  HipEstimateSE3PnP(int width, int height, int device = 0, void *stream = nullptr) : width_(width), height_(height) {
+    check(dsopp_hip_pnp_ransac_create(device, stream, &r_));
+  }
+  ~HipEstimateSE3PnP() { dsopp_hip_pnp_ransac_destroy(r_); }
+  HipEstimateSE3PnP(const HipEstimateSE3PnP &) = delete;
+  HipEstimateSE3PnP &operator=(const HipEstimateSE3PnP &) = delete;
+
+  /** the landmarks with a position and a projection in frame `frame_id`, in landmark order: the candidates of estimateSE3PnP's first
+   *  loop.  Those whose projection fails the ROI are no matches of the reference; the device leaves them out of every count. */
+  static std::vector<size_t> candidates(size_t frame_id, const std::vector<RefineLandmark> &landmarks) {
+    std::vector<size_t> out;
+    for (size_t l = 0; l < landmarks.size(); ++l)
+      if (landmarks[l].has_position && landmarks[l].projection(frame_id)) out.push_back(l);
+    return out;
+  }
+
+  /** estimateSE3PnP(frame_id, landmarks, frame.t_world_agent, model, pnp_ransac_threshold): the triples come from std::rand() */
+  Result estimate(size_t frame_id, std::vector<RefineLandmark> &landmarks, RefineFrame &frame, const PinholeModel &model,
+                  double pnp_ransac_threshold = 0.5) {
+    const size_t n = candidates(frame_id, landmarks).size();
+    const size_t iterations = static_cast<size_t>(dsopp_hip_pnp_ransac_default_iterations());
+    return estimate(frame_id, landmarks, frame, model, n < 3 ? std::vector<int32_t>() : HipRotationStandstill::drawSamples(n, iterations),
+                    pnp_ransac_threshold);
+  }
+  /** the same over the caller's triples (3 indices per hypothesis, into the candidates) */
+  Result estimate(size_t frame_id, std::vector<RefineLandmark> &landmarks, RefineFrame &frame, const PinholeModel &model,
+                  const std::vector<int32_t> &samples, double pnp_ransac_threshold = 0.5, const dsopp_hip_pnp_ransac_options *options = nullptr) {
+    const std::vector<size_t> chosen = candidates(frame_id, landmarks);
+    const size_t n = chosen.size();
+    std::vector<double> positions(3 * n), observations(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+      const RefineLandmark &lm = landmarks[chosen[k]];
+      const Vector2 &xy = *lm.projection(frame_id);
+      for (size_t r = 0; r < 3; ++r) positions[3 * k + r] = lm.position[r];
+      observations[2 * k] = xy[0];
+      observations[2 * k + 1] = xy[1];
+    }
+    Result out;
+    std::vector<int32_t> indices(n, 0);
+    check(dsopp_hip_pnp_ransac_estimate(r_, model.fx, model.fy, model.cx, model.cy, width_, height_, static_cast<int>(n), positions.data(),
+                                        observations.data(), static_cast<int>(samples.size() / 3), samples.data(), pnp_ransac_threshold, options,
+                                        &out.record, indices.data(), nullptr, nullptr, nullptr));
+    out.inliers = static_cast<size_t>(out.record.ransac_inlier_count);
+    out.matches = static_cast<size_t>(out.record.matches);
+    frame.t_world_agent = HipRefineTrack::inverse(out.record.pose);
+    // every landmark with a position that is not a final inlier loses its projection in this frame (:64-74), a non-match too
+    std::vector<uint8_t> keeps(n, 0);
+    for (int32_t k = 0; k < out.record.refined_inlier_count; ++k) keeps[static_cast<size_t>(indices[static_cast<size_t>(k)])] = 1;
+    for (size_t k = 0; k < n; ++k) {
+      if (keeps[k]) {
+        out.inlier_landmarks.push_back(chosen[k]);
+        continue;
+      }
+      auto &projections = landmarks[chosen[k]].projections;
+      projections.erase(std::remove_if(projections.begin(), projections.end(), [&](const auto &q) { return q.first == frame_id; }), projections.end());
+    }
+    return out;
+  }
+
+  /** initializePoses' test of the returned pair (initialize_poses.cpp:47-73): inliers > (size_t)(ratio * matches) */
+  static bool initialised(size_t inliers, size_t matches, double ratio = 0.5) {
+    return inliers > static_cast<size_t>(ratio * static_cast<double>(matches));
+  }
+  dsopp_hip_pnp_ransac *handle() const { return r_; }
+
+ private:
+  dsopp_hip_pnp_ransac *r_ = nullptr;
+  int width_, height_;
+};
+
 }  // namespace dsopp_hip_host

@@ -260,7 +260,7 @@ int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out
  * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
  * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
  * The refill of lost features from a fresh ORB detection (optical_flow.cpp:44-53) is dsopp_hip_orb_detector_* below, and
- * estimateSO3inlierCount dsopp_hip_rotation_ransac_*, and the refinement behind them dsopp_hip_geometric_ba_*.  Not built: the RANSACs of initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ * estimateSO3inlierCount dsopp_hip_rotation_ransac_*, estimateSE3PnP dsopp_hip_pnp_ransac_*, and the refinement behind them dsopp_hip_geometric_ba_*.  Not built: the essential-matrix RANSAC of initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
  *
  * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
  * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
@@ -415,8 +415,8 @@ int dsopp_hip_orb_detector_get_level(dsopp_hip_orb_detector *d, int level, uint8
  * src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48 —, that is ransac::ransac — src/ransac/include/ransac/ransac.hpp:27-56 —
  * over the three-point PureRorationSolver — src/energy/n_point_solvers/src/pure_rotation_estimator.cpp:14-67 —, which
  * MonocularInitializer::tick — monocular_initializer.cpp:71-94 — and the feature-based tracker — add_new_frame.cpp:36-45 — run on every
- * frame).  Not built: the essential-matrix and PnP RANSACs, ORB descriptors and matching, the SimpleRadialCamera instantiation
- * (triangulation and the refinement are dsopp_hip_geometric_ba_* below).
+ * frame).  Not built: the essential-matrix RANSAC, ORB descriptors and matching, the SimpleRadialCamera instantiation
+ * (triangulation and the refinement are dsopp_hip_geometric_ba_* below, the PnP RANSAC dsopp_hip_pnp_ransac_* below them).
  *
  * The arithmetic is fixed here; tests/rotation_ransac_model.py is its NumPy form.  Everything is binary64 (the reference's Precision);
  * float points of the flow tracker are widened by the caller.
@@ -470,8 +470,8 @@ int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, 
  * them, with the triangulation before it and the pruning after it (replaces, per bootstrap frame once the initialiser has succeeded —
  * src/feature_based_slam/tracker/src/monocular_tracker.cpp:54-68 —, triangulatePoints — triangulate_points.cpp:47-71, triangulation.hpp:52-64 —,
  * optimizeTransformations — refine_track.cpp:16-83, which runs Ceres SPARSE_SCHUR with a Huber loss through
- * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  Not built: estimateSE3PnP and the
- * essential-matrix RANSAC (OpenGV), the SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks, the
+ * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  Not built: the
+ * essential-matrix RANSAC (OpenGV; estimateSE3PnP is dsopp_hip_pnp_ransac_* below), the SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks, the
  * two-view triangulatePoints that only initializePoses calls.
  *
  * The arithmetic is fixed here; tests/geometric_ba_model.py is its NumPy form.  Everything is binary64.
@@ -591,6 +591,99 @@ int dsopp_hip_geometric_ba_triangulate(dsopp_hip_geometric_ba *b, dsopp_hip_geom
  * threshold that is not a number.  One wait. */
 int dsopp_hip_geometric_ba_flag_outliers(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem, double outlier_threshold,
                                          uint8_t *flags, int32_t *flagged);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The pose of a bootstrap frame: a PnP RANSAC over the frame's landmarks with a position, with the refinement and the re-selection behind
+ * it (replaces estimateSE3PnP — src/feature_based_slam/tracker/src/estimate_se3_pnp.cpp:23-77 —, which the feature-based tracker runs
+ * first on every bootstrap frame once the initialiser has succeeded — monocular_tracker.cpp:54-56 — and initializePoses for every
+ * intermediate frame — initialize_poses.cpp:47-73).  The reference hands its matches to OpenGV: EPnP inside OpenGV's RANSAC, then
+ * optimizeModelCoefficients and selectWithinDistance.  OpenGV is not part of the reference's tree, so, like the bundle adjustment above,
+ * this is the library's own algorithm for the same job: a three-point pose per hypothesis and an LM refinement of the winner.  Parity
+ * with OpenGV's iteration path (its EPnP solutions, its sampler, its adaptive stopping rule, its refinement) is unpinned.  What is
+ * mirrored is everything around the solver: which landmarks are matches (:31-43), the threshold's conversion (:45), the error measure,
+ * refine-then-reselect (:56-60), which projections are removed (:64-74, in the host mirror) and the returned pair (:76).
+ * Not built: the autocalibration variant, the SimpleRadialCamera instantiation.
+ *
+ * The arithmetic is fixed here; tests/pnp_ransac_model.py is its NumPy form.  Everything is binary64.
+ *   Inputs: a pinhole camera fx, fy, cx, cy, width, height; n matches: the world position X[j] (3 doubles) and the observation obs[j]
+ *     (x, y); `iterations` sample triples S[i] = (s1, s2, s3) of distinct indices < n, drawn by the caller; threshold_px (the reference's
+ *     pnp_ransac_threshold, 0.5); the refinement's options.
+ *   roi(p) and unproject(p) as in the rotation RANSAC's block; f_j = normalize(unproject(obs[j])).  A match whose observation fails roi is
+ *     no match of the reference (unproject returns false, :38): it is never an inlier, a triple that holds one is invalid, and it does
+ *     not count in `matches`.
+ *   Threshold and measure (:45, OpenGV's absolute-pose distance): t_ang = 1 - cos(atan(threshold_px / fx)), computed once on the host.
+ *     For a pose (R, t), world to camera: p = R X_j + t, d_j = 1 - f_j . p / |p|; point j is an inlier iff d_j < t_ang (strict; a NaN is
+ *     no inlier).  No depth test: a point behind the camera has d near 2.
+ *   Hypothesis i, the three-point pose by Grunert's elimination over the points 1, 2, 3 of its triple: a^2 = |X2 - X3|^2,
+ *     b^2 = |X1 - X3|^2, c^2 = |X1 - X2|^2; ca = f2 . f3, cb = f1 . f3, cg = f1 . f2; the depths are s1, s2 = u s1, s3 = v s1.  With
+ *     K = (a^2 - c^2) / b^2: N(v) = (K - 1) v^2 - 2 K cb v + 1 + K, D(v) = 2 (cg - v ca), Q(v) = v^2 - 2 cb v + 1; u = N / D, and v is a
+ *     real root of the quartic D^2 + N^2 - 2 cg N D - (c^2 / b^2) Q D^2 = 0.  The roots with v > 0, u > 0, Q(v) > 0 are kept, in
+ *     ascending v: at most four solutions.  s1 = sqrt(b^2 / Q(v)), the camera-frame points are Y_k = s_k f_k, and the pose comes from
+ *     the two congruent triangles by frames: e1 = normalize(X2 - X1), e3 = normalize(e1 x (X3 - X1)), e2 = e3 x e1, E_w = [e1 e2 e3];
+ *     the same from Y gives E_c; R = E_c E_w^T, t = Y_1 - R X_1.  A solution whose pose is not finite is dropped.  The triple is
+ *     invalid, with zero solutions, when one of its observations fails roi, when b^2 = 0, or when
+ *     |(X2 - X1) x (X3 - X1)|^2 <= 1e-12 |X2 - X1|^2 |X3 - X1|^2 (a degenerate world triangle).  Any route to the quartic's real roots
+ *     that reaches them to rounding serves (the device: brackets from the derivatives' roots, a safeguarded Newton iteration in each; the
+ *     model: numpy.roots); where two roots nearly coincide their number and the poses are unpinned.
+ *   Score and selection: every solution of every hypothesis is scored against all n points.  A hypothesis's count is its best solution's,
+ *     the lower solution index winning a tie; the winner is the hypothesis with the greatest count, the lowest index winning a tie.
+ *     Deviation: there is no early stop — all hypotheses are scored in one launch anyway, and OpenGV's serial adaptive stopping rule has
+ *     nothing to mirror here.  best_iteration = -1 when no count exceeds 0: the pose is then the identity, there are no inliers and
+ *     there is no refinement.  dsopp_hip_pnp_ransac_default_iterations() = 256: log(0.01) / log(1 - w^3) <= 256 down to an inlier share
+ *     w = 0.262 (OpenGV's confidence 0.99 with a three-point sample; w = 0.26 would take 260).
+ *   Refinement (the role of optimizeModelCoefficients, :57-58), over the winner's inliers only, the landmarks fixed: the pixel residual
+ *     r = obs - q with q and G = dq / dp as in the geometric BA's block; a point counts iff p_z >= 0.001 (no roi test on q, no robust
+ *     loss); cost = 1/2 sum |r|^2.  Right increment T <- T exp(delta), delta = (upsilon, omega): J = -G R [I | -hat(X)], H = sum J^T J,
+ *     b = sum J^T r in a fixed order of summation (the same input gives the same bits on every run); (H + lambda diag H) delta = -b by
+ *     a 6 x 6 Cholesky; a pivot <= 0 or not finite gives no step and the iteration counts as rejected.  Control is the geometric BA's
+ *     driver with one free frame: lambda_0 = 1e-4, / 2 on accept, x 10 on reject; |E - E'| / E < function_tolerance converges (accepted
+ *     or not); E' < E accepts, and |delta|^2 < parameter_tolerance (|t|^2 + 1 + parameter_tolerance) converges, t of the state the step
+ *     left; no counting point, at the start or at a candidate, ends the loop (the candidate rejected); function_tolerance =
+ *     parameter_tolerance = 1e-10; max_iterations 10.  refine_flags are the DSOPP_HIP_GEOMETRIC_BA_* bits, 0 = max_iterations.
+ *   Final selection (selectWithinDistance on the refined model, :59-60): the same test with the refined pose; its inliers, ascending, are
+ *     the call's index list.  ransac_inlier_count, the first number the reference returns, is the winner's count, not the re-selected one.
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_pnp_ransac dsopp_hip_pnp_ransac;
+typedef struct dsopp_hip_pnp_ransac_options {
+  double lambda_0;            /* 1e-4 */
+  double function_tolerance;  /* 1e-10 */
+  double parameter_tolerance; /* 1e-10 */
+  double decrease_factor;     /* lambda is divided by it on accept, 2 */
+  double increase_factor;     /* lambda is multiplied by it on reject, 10 */
+  int32_t max_iterations;     /* 10 */
+  int32_t reserved;
+} dsopp_hip_pnp_ransac_options;
+typedef struct dsopp_hip_pnp_ransac_result {
+  int32_t matches;              /* the observations inside the ROI, the reference's matching number */
+  int32_t best_iteration;       /* the winning hypothesis, -1 when no count exceeded 0 */
+  int32_t best_solution;        /* its solution, 0 .. 3; -1 without a winner */
+  int32_t ransac_inlier_count;  /* the winner's count */
+  int32_t refined_inlier_count; /* the inliers of the refined pose: the length of the index list */
+  int32_t refine_iterations;    /* iterations run, accepted or not */
+  int32_t refine_flags;         /* the DSOPP_HIP_GEOMETRIC_BA_* bits that ended the loop; 0 = max_iterations */
+  int32_t reserved;
+  double cost_initial, cost_final; /* 1/2 sum |r|^2 over the winner's inliers, before and after */
+  double pose_ransac[12];       /* the winner's pose, world to camera: R row-major, then t (the t_agent_world layout above) */
+  double pose[12];              /* the refined pose */
+} dsopp_hip_pnp_ransac_result;
+int dsopp_hip_pnp_ransac_default_iterations(void);
+void dsopp_hip_pnp_ransac_default_options(dsopp_hip_pnp_ransac_options *options);
+/* `stream` is a hipStream_t (NULL = a stream of its own); all work of the object runs on it.  Its buffers grow with n and iterations. */
+int dsopp_hip_pnp_ransac_create(int device, void *stream, dsopp_hip_pnp_ransac **out);
+void dsopp_hip_pnp_ransac_destroy(dsopp_hip_pnp_ransac *r);
+/* One launch and one wait, blocking.  positions: n x 3 doubles; observations: n x 2; samples: iterations x 3 int32; options: NULL = the
+ * defaults; inlier_indices: room for n int32, the first result->refined_inlier_count of which are written, ascending.  Optional (NULL)
+ * per-hypothesis outputs, there so that a divergence from the stated arithmetic can be located: hyp_num_solutions (iterations int32),
+ * hyp_poses (iterations x 4 x 12 doubles, unused slots zero), hyp_counts (iterations x 4 int32, unused slots zero); they cover every
+ * hypothesis.  n = 0 or iterations = 0 returns at once without a winner.  DSOPP_HIP_ERR_INVALID_ARGUMENT: n < 0, iterations < 0,
+ * 0 < n < 3 with iterations > 0, a sample index outside 0 .. n - 1 or repeated within its triple, a position, observation, threshold or
+ * intrinsic that is not finite, an option that is not finite or out of range (lambda_0 < 0, a factor <= 0, max_iterations < 0), a NULL
+ * required argument. */
+int dsopp_hip_pnp_ransac_estimate(dsopp_hip_pnp_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
+                                  const double *positions, const double *observations, int iterations, const int32_t *samples, double threshold_px,
+                                  const dsopp_hip_pnp_ransac_options *options, dsopp_hip_pnp_ransac_result *result, int32_t *inlier_indices,
+                                  int32_t *hyp_num_solutions, double *hyp_poses, int32_t *hyp_counts);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
