@@ -50,6 +50,18 @@ class PnpRansacResult(C.Structure):
                 ("cost_initial", C.c_double), ("cost_final", C.c_double), ("pose_ransac", C.c_double * 12), ("pose", C.c_double * 12)]
 
 
+class TwoViewRansacOptions(C.Structure):
+    _fields_ = [("a", C.c_double), ("lambda_0", C.c_double), ("function_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("decrease_factor", C.c_double), ("increase_factor", C.c_double), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TwoViewRansacResult(C.Structure):
+    _fields_ = [("matches", C.c_int32), ("best_iteration", C.c_int32), ("best_solution", C.c_int32), ("ransac_inlier_count", C.c_int32),
+                ("inlier_count", C.c_int32), ("refine_iterations", C.c_int32 * 2), ("refine_flags", C.c_int32 * 2), ("reserved", C.c_int32),
+                ("cost_initial", C.c_double * 2), ("cost_final", C.c_double * 2), ("pose_ransac", C.c_double * 12),
+                ("pose_reselect", C.c_double * 12), ("pose", C.c_double * 12)]
+
+
 class GeometricBAProblem(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
                 ("num_frames", C.c_int32), ("num_landmarks", C.c_int32), ("num_observations", C.c_int32), ("reserved", C.c_int32),
@@ -138,6 +150,8 @@ SYMBOLS = [
     "dsopp_hip_geometric_ba_solve", "dsopp_hip_geometric_ba_triangulate", "dsopp_hip_geometric_ba_flag_outliers",
     "dsopp_hip_pnp_ransac_default_iterations", "dsopp_hip_pnp_ransac_default_options", "dsopp_hip_pnp_ransac_create", "dsopp_hip_pnp_ransac_destroy",
     "dsopp_hip_pnp_ransac_estimate",
+    "dsopp_hip_two_view_ransac_default_iterations", "dsopp_hip_two_view_ransac_default_options", "dsopp_hip_two_view_ransac_create",
+    "dsopp_hip_two_view_ransac_destroy", "dsopp_hip_two_view_ransac_estimate", "dsopp_hip_two_view_ransac_triangulate",
 ]
 
 _lib = None
@@ -766,6 +780,81 @@ class PnpRansac:
         if with_hypotheses:
             out.update(hyp_num_solutions=hyp[0], hyp_poses=hyp[1], hyp_counts=hyp[2])
         return out
+
+
+def default_two_view_ransac_options(**kw) -> TwoViewRansacOptions:
+    o = TwoViewRansacOptions()
+    lib().dsopp_hip_two_view_ransac_default_options(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def two_view_ransac_default_iterations() -> int:
+    return int(lib().dsopp_hip_two_view_ransac_default_iterations())
+
+
+class TwoViewRansac:
+    """estimateSO3xS2 and the two-view triangulatePoints on the device (dsopp_hip_two_view_ransac): the pose between the first and the
+    last bootstrap frame from their matches, every five-point hypothesis scored in one launch, the winner refined over its inliers, the
+    inliers selected again and the pose refined over those.  A pose is 12 doubles, R row-major, then t, |t| = 1, and maps the last frame
+    (B) into the first (A).  The samples are the caller's."""
+
+    def __init__(self, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.device = device
+        _chk(lib().dsopp_hip_two_view_ransac_create(int(device), C.c_void_p(stream or 0), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_two_view_ransac_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate(self, camera, A, B, samples, threshold_px=0.5, min_matches=50, options=None, with_hypotheses=False):
+        """camera = (fx, fy, cx, cy, width, height); A, B (n, 2) float64: the first and the last frame's observations; samples
+        (iterations, 5) int32; options: a TwoViewRansacOptions (None = the defaults).  Returns a dict: the result record's fields (the
+        per-stage ones as 2-tuples, the three poses as (12,) arrays), inliers (ascending int32), and with with_hypotheses the
+        per-hypothesis hyp_num_solutions (iterations,), hyp_poses (iterations, 10, 12), hyp_counts (iterations, 10); blocking"""
+        fx, fy, cx, cy, width, height = camera
+        a = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(B, dtype=np.float64).reshape(-1, 2)
+        s = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 5)
+        assert len(a) == len(b), (a.shape, b.shape)
+        n, m = len(a), len(s)
+        res = TwoViewRansacResult()
+        idx = np.zeros(n, np.int32)
+        hyp = (np.zeros(m, np.int32), np.zeros((m, 10, 12)), np.zeros((m, 10), np.int32)) if with_hypotheses else (None, None, None)
+        _chk(lib().dsopp_hip_two_view_ransac_estimate(self._h, C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(width),
+                                                      int(height), n, _p(a), _p(b), m, _p(s, np.int32), C.c_double(threshold_px),
+                                                      int(min_matches), C.byref(options) if options is not None else None, C.byref(res),
+                                                      _p(idx, np.int32), _p(hyp[0], np.int32), _p(hyp[1]), _p(hyp[2], np.int32)))
+        out = {name: getattr(res, name) for name in ("matches", "best_iteration", "best_solution", "ransac_inlier_count", "inlier_count")}
+        out.update({name: tuple(getattr(res, name)) for name in ("refine_iterations", "refine_flags", "cost_initial", "cost_final")})
+        out.update(pose_ransac=np.array(res.pose_ransac), pose_reselect=np.array(res.pose_reselect), pose=np.array(res.pose),
+                   inliers=idx[:res.inlier_count].copy())
+        if with_hypotheses:
+            out.update(hyp_num_solutions=hyp[0], hyp_poses=hyp[1], hyp_counts=hyp[2])
+        return out
+
+    def triangulate(self, camera, A, B, pose_a_b, pose_world_a, cos_threshold=0.9999):
+        """the two-view triangulation of the pairs under pose_a_b (12,), placed by pose_world_a (12,): (X_world (n, 3), keep (n,) bool)"""
+        fx, fy, cx, cy, width, height = camera
+        a = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(B, dtype=np.float64).reshape(-1, 2)
+        assert len(a) == len(b), (a.shape, b.shape)
+        pab = np.ascontiguousarray(pose_a_b, dtype=np.float64).reshape(12)
+        pwa = np.ascontiguousarray(pose_world_a, dtype=np.float64).reshape(12)
+        X, keep = np.zeros((len(a), 3)), np.zeros(len(a), np.uint8)
+        _chk(lib().dsopp_hip_two_view_ransac_triangulate(self._h, C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(width),
+                                                         int(height), len(a), _p(a), _p(b), _p(pab), _p(pwa), C.c_double(cos_threshold), _p(X),
+                                                         _p(keep, np.uint8)))
+        return X, keep.astype(bool)
 
 
 def default_geometric_ba_options(**kw) -> GeometricBAOptions:

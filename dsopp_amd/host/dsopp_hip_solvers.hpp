@@ -1495,4 +1495,221 @@ class HipEstimateSE3PnP {
   int width_, height_;
 };
 
+/** The two-view pose that initialises a track, on the device: estimateSO3xS2 (src/feature_based_slam/tracker/src/estimate_so3xs2.cpp:23-110)
+ *  and the two-view triangulatePoints (triangulate_points.cpp:18-45), steps I and II of initializePoses, over dsopp_hip_two_view_ransac.
+ *  The reference calls its result t_t_r, but it maps the target (last) frame into the reference (first) frame and is stored as the last
+ *  frame's t_world_agent (initialize_poses.cpp:31-33, include/dsopp_hip.h): so it is here.
+ *  Deviations: the solver is the library's five-point RANSAC with its own LM refinements, not OpenGV's and Ceres's (include/dsopp_hip.h);
+ *  every hypothesis is scored, there is no adaptive stop; the samples come from std::rand(), as HipEstimateSE3PnP's do. */
+class HipEstimateSO3xS2 {
+ public:
+  struct Result {
+    size_t inliers, matches;  // estimateSO3xS2's pair: the re-selected inliers and the matches
+    dsopp_hip_two_view_ransac_result record;
+    std::vector<size_t> inlier_landmarks;  // the landmarks that keep their projection in the target frame, ascending
+  };
+  /** width, height: the image size of `model`, which bounds the ROI */
+  HipEstimateSO3xS2(int width, int height, int device = 0, void *stream = nullptr) : width_(width), height_(height) {
+    check(dsopp_hip_two_view_ransac_create(device, stream, &r_));
+  }
+  ~HipEstimateSO3xS2() { dsopp_hip_two_view_ransac_destroy(r_); }
+  HipEstimateSO3xS2(const HipEstimateSO3xS2 &) = delete;
+  HipEstimateSO3xS2 &operator=(const HipEstimateSO3xS2 &) = delete;
+
+  /** getLandmarksFromTwoFrames: the landmarks with a projection in both frames, in landmark order.  Those with an observation outside the
+   *  ROI are no matches of the reference (:40-41); the device leaves them out of every count. */
+  static std::vector<size_t> candidates(size_t reference_frame_id, size_t target_frame_id, const std::vector<RefineLandmark> &landmarks) {
+    std::vector<size_t> out;
+    for (size_t l = 0; l < landmarks.size(); ++l)
+      if (landmarks[l].projection(reference_frame_id) && landmarks[l].projection(target_frame_id)) out.push_back(l);
+    return out;
+  }
+
+  /** `iterations` samples of five distinct indices < n from std::rand(), drawn as HipRotationStandstill::drawSamples draws its triples */
+  static std::vector<int32_t> drawSamples(size_t n, size_t iterations) {
+    if (iterations > 0 && n < 5) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "fewer than 5 pairs: no sample of distinct indices");
+    std::vector<int32_t> samples(5 * iterations);
+    for (size_t i = 0; i < iterations; ++i) {
+      size_t sequence[5];
+      for (size_t k = 0; k < 5; ++k) {
+        size_t next = static_cast<size_t>(std::rand()) % n;
+        auto repeats = [&] {
+          for (size_t j = 0; j < k; ++j)
+            if (sequence[j] == next) return true;
+          return false;
+        };
+        while (repeats()) next = static_cast<size_t>(std::rand()) % n;
+        sequence[k] = next;
+      }
+      for (size_t k = 0; k < 5; ++k) samples[5 * i + k] = static_cast<int32_t>(sequence[k]);
+    }
+    return samples;
+  }
+
+  /** estimateSO3xS2(reference_frame_id, target_frame_id, landmarks, target.t_world_agent, ..., min_ransac_matches,
+   *  essential_matrix_ransac_threshold, reprojection_threshold): the samples come from std::rand() */
+  Result estimate(size_t reference_frame_id, size_t target_frame_id, std::vector<RefineLandmark> &landmarks, RefineFrame &target,
+                  const PinholeModel &model, size_t min_ransac_matches = 50, double essential_matrix_ransac_threshold = 0.5,
+                  double reprojection_threshold = 1.5) {
+    const size_t n = candidates(reference_frame_id, target_frame_id, landmarks).size();
+    const size_t iterations = static_cast<size_t>(dsopp_hip_two_view_ransac_default_iterations());
+    return estimate(reference_frame_id, target_frame_id, landmarks, target, model, n < 5 ? std::vector<int32_t>() : drawSamples(n, iterations),
+                    min_ransac_matches, essential_matrix_ransac_threshold, reprojection_threshold);
+  }
+  /** the same over the caller's samples (5 indices per hypothesis, into the candidates) */
+  Result estimate(size_t reference_frame_id, size_t target_frame_id, std::vector<RefineLandmark> &landmarks, RefineFrame &target,
+                  const PinholeModel &model, const std::vector<int32_t> &samples, size_t min_ransac_matches = 50,
+                  double essential_matrix_ransac_threshold = 0.5, double reprojection_threshold = 1.5) {
+    const std::vector<size_t> chosen = candidates(reference_frame_id, target_frame_id, landmarks);
+    const size_t n = chosen.size();
+    std::vector<double> a(2 * n), b(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+      const Vector2 &pa = *landmarks[chosen[k]].projection(reference_frame_id), &pb = *landmarks[chosen[k]].projection(target_frame_id);
+      a[2 * k] = pa[0];
+      a[2 * k + 1] = pa[1];
+      b[2 * k] = pb[0];
+      b[2 * k + 1] = pb[1];
+    }
+    dsopp_hip_two_view_ransac_options options;
+    dsopp_hip_two_view_ransac_default_options(&options);
+    options.a = reprojection_threshold;
+    Result out;
+    std::vector<int32_t> indices(n, 0);
+    check(dsopp_hip_two_view_ransac_estimate(r_, model.fx, model.fy, model.cx, model.cy, width_, height_, static_cast<int>(n), a.data(), b.data(),
+                                             static_cast<int>(samples.size() / 5), samples.data(), essential_matrix_ransac_threshold,
+                                             static_cast<int>(min_ransac_matches), &options, &out.record, indices.data(), nullptr, nullptr, nullptr));
+    out.matches = static_cast<size_t>(out.record.matches);
+    // too few matches: {0, matches}, the pose and the projections untouched (:48)
+    if (out.matches < min_ransac_matches) {
+      out.inliers = 0;
+      return out;
+    }
+    out.inliers = static_cast<size_t>(out.record.inlier_count);
+    for (size_t e = 0; e < 12; ++e) target.t_world_agent[e] = out.record.pose[e];
+    // every landmark of the two frames that is not an inlier loses its projection in the target frame (:77-86), a non-match too
+    std::vector<uint8_t> keeps(n, 0);
+    for (int32_t k = 0; k < out.record.inlier_count; ++k) keeps[static_cast<size_t>(indices[static_cast<size_t>(k)])] = 1;
+    for (size_t k = 0; k < n; ++k) {
+      if (keeps[k]) {
+        out.inlier_landmarks.push_back(chosen[k]);
+        continue;
+      }
+      auto &projections = landmarks[chosen[k]].projections;
+      projections.erase(std::remove_if(projections.begin(), projections.end(), [&](const auto &q) { return q.first == target_frame_id; }),
+                        projections.end());
+    }
+    return out;
+  }
+
+  /** triangulatePoints(reference_frame_id, target_frame_id, landmarks, reference.t_world_agent, target.t_world_agent, model,
+   *  triangulation_cos_threshold): sets the position of every kept landmark of the two frames; returns their number */
+  size_t triangulatePoints(size_t reference_frame_id, size_t target_frame_id, std::vector<RefineLandmark> &landmarks, const RefineFrame &reference,
+                           const RefineFrame &target, const PinholeModel &model, double triangulation_cos_threshold = 0.9999) {
+    const std::vector<size_t> chosen = candidates(reference_frame_id, target_frame_id, landmarks);
+    const size_t n = chosen.size();
+    std::vector<double> a(2 * n), b(2 * n), positions(3 * n);
+    std::vector<uint8_t> keep(n, 0);
+    for (size_t k = 0; k < n; ++k) {
+      const Vector2 &pa = *landmarks[chosen[k]].projection(reference_frame_id), &pb = *landmarks[chosen[k]].projection(target_frame_id);
+      a[2 * k] = pa[0];
+      a[2 * k + 1] = pa[1];
+      b[2 * k] = pb[0];
+      b[2 * k + 1] = pb[1];
+    }
+    // t_r_t = t_w_r^-1 t_w_t (:21)
+    const std::array<double, 12> inv = HipRefineTrack::inverse(reference.t_world_agent.data());
+    std::array<double, 12> t_r_t{};
+    for (size_t i = 0; i < 3; ++i) {
+      for (size_t j = 0; j < 3; ++j)
+        t_r_t[3 * i + j] = inv[3 * i] * target.t_world_agent[j] + inv[3 * i + 1] * target.t_world_agent[3 + j] + inv[3 * i + 2] * target.t_world_agent[6 + j];
+      t_r_t[9 + i] = inv[3 * i] * target.t_world_agent[9] + inv[3 * i + 1] * target.t_world_agent[10] + inv[3 * i + 2] * target.t_world_agent[11] + inv[9 + i];
+    }
+    check(dsopp_hip_two_view_ransac_triangulate(r_, model.fx, model.fy, model.cx, model.cy, width_, height_, static_cast<int>(n), a.data(), b.data(),
+                                                t_r_t.data(), reference.t_world_agent.data(), triangulation_cos_threshold, positions.data(), keep.data()));
+    size_t count = 0;
+    for (size_t k = 0; k < n; ++k)
+      if (keep[k]) {
+        RefineLandmark &lm = landmarks[chosen[k]];
+        lm.has_position = true;
+        for (size_t r = 0; r < 3; ++r) lm.position[r] = positions[3 * k + r];
+        ++count;
+      }
+    return count;
+  }
+
+  /** initializePoses' test of the returned pair (initialize_poses.cpp:37): false iff inliers < (size_t)(ratio * matches) */
+  static bool accepted(size_t inliers, size_t matches, double ratio = 0.6) { return !(inliers < static_cast<size_t>(ratio * static_cast<double>(matches))); }
+  dsopp_hip_two_view_ransac *handle() const { return r_; }
+
+ private:
+  dsopp_hip_two_view_ransac *r_ = nullptr;
+  int width_, height_;
+};
+
+/** initializePoses (src/feature_based_slam/tracker/src/initialize_poses.cpp:17-78) composed from the library: I. HipEstimateSO3xS2 between
+ *  the first and the last frame, II. its triangulation, III. HipEstimateSE3PnP for every frame between them, IV. HipRefineTrack's
+ *  optimizeTransformations over all frames (refine_track's defaults: the last 10), V. the PnP again for the frames III left uninitialised.
+ *  The samples of every step come from std::rand(), which the caller seeds. */
+class HipInitializePoses {
+ public:
+  struct Options {  // feature_based_slam/tracker/initializer.hpp:25-39
+    double reprojection_threshold = 1.5;
+    size_t min_ransac_matches = 50;
+    double se3_inlier_ratio = 0.6;
+    double essential_matrix_ransac_threshold = 0.5;
+    double triangulation_cos_threshold = 0.9999;
+    double pnp_inlier_ratio = 0.5;
+    double pnp_ransac_threshold = 0.5;
+  };
+  struct Result {
+    bool success = false;
+    HipEstimateSO3xS2::Result two_view{};
+    size_t triangulated = 0, pnp_initialized = 0;
+    std::vector<HipEstimateSE3PnP::Result> pnp, second_pnp;  // per intermediate frame of III; per frame V ran for
+    dsopp_hip_geometric_ba_result refinement{};
+  };
+  HipInitializePoses(int width, int height, int device = 0, void *stream = nullptr)
+      : two_view_(width, height, device, stream), pnp_(width, height, device, stream), refine_(width, height, device, stream) {}
+
+  Result run(std::deque<RefineFrame> &frames, std::vector<RefineLandmark> &landmarks, const PinholeModel &model) {
+    return run(frames, landmarks, model, Options{});
+  }
+  Result run(std::deque<RefineFrame> &frames, std::vector<RefineLandmark> &landmarks, const PinholeModel &model, const Options &options) {
+    Result out;
+    if (frames.size() < 2) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "initializePoses needs two frames");
+    RefineFrame &first = frames.front(), &last = frames.back();
+    /* I. */
+    out.two_view = two_view_.estimate(first.frame_id, last.frame_id, landmarks, last, model, options.min_ransac_matches,
+                                      options.essential_matrix_ransac_threshold, options.reprojection_threshold);
+    if (!HipEstimateSO3xS2::accepted(out.two_view.inliers, out.two_view.matches, options.se3_inlier_ratio)) return out;
+    first.initialized = true;
+    last.initialized = true;
+    /* II. */
+    out.triangulated = two_view_.triangulatePoints(first.frame_id, last.frame_id, landmarks, first, last, model, options.triangulation_cos_threshold);
+    /* III. */
+    for (size_t i = 1; i + 1 < frames.size(); ++i) {
+      out.pnp.push_back(pnp_.estimate(frames[i].frame_id, landmarks, frames[i], model, options.pnp_ransac_threshold));
+      if (HipEstimateSE3PnP::initialised(out.pnp.back().inliers, out.pnp.back().matches, options.pnp_inlier_ratio)) {
+        frames[i].initialized = true;
+        ++out.pnp_initialized;
+      }
+    }
+    if (out.pnp_initialized < 1) return out;
+    /* IV. */
+    out.refinement = refine_.optimizeTransformations(landmarks, frames, model, options.reprojection_threshold);
+    /* V. */
+    for (size_t i = 1; i + 1 < frames.size(); ++i) {
+      if (frames[i].initialized) continue;
+      out.second_pnp.push_back(pnp_.estimate(frames[i].frame_id, landmarks, frames[i], model, options.pnp_ransac_threshold));
+    }
+    out.success = true;
+    return out;
+  }
+
+ private:
+  HipEstimateSO3xS2 two_view_;
+  HipEstimateSE3PnP pnp_;
+  HipRefineTrack refine_;
+};
+
 }  // namespace dsopp_hip_host

@@ -260,7 +260,7 @@ int dsopp_hip_pyramid_get_image(dsopp_hip_pyramid *p, int channels, uint8_t *out
  * of features::OpticalFlowMatch — src/feature_based_slam/features/src/optical_flow.cpp:11-42 — which MonocularInitializer::tick —
  * src/feature_based_slam/tracker/src/monocular_initializer.cpp:36-102 — runs on every frame until the sequence is initialised)
  * The refill of lost features from a fresh ORB detection (optical_flow.cpp:44-53) is dsopp_hip_orb_detector_* below, and
- * estimateSO3inlierCount dsopp_hip_rotation_ransac_*, estimateSE3PnP dsopp_hip_pnp_ransac_*, and the refinement behind them dsopp_hip_geometric_ba_*.  Not built: the essential-matrix RANSAC of initializePoses, a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
+ * estimateSO3inlierCount dsopp_hip_rotation_ransac_*, estimateSE3PnP dsopp_hip_pnp_ransac_*, and the refinement behind them dsopp_hip_geometric_ba_*.  estimateSO3xS2 and the two-view triangulation of initializePoses dsopp_hip_two_view_ransac_*.  Not built: a dsopp_hip_pyramid_group_* form, OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel images.
  *
  * The arithmetic is fixed here, a restatement of OpenCV 4's calcOpticalFlowPyrLK (the scalar path of lkpyramid.cpp) for 8-bit
  * single-channel images; tests/optical_flow_model.py is its NumPy form and the device is held to it bit for bit.  OpenCV sums the window
@@ -415,8 +415,9 @@ int dsopp_hip_orb_detector_get_level(dsopp_hip_orb_detector *d, int level, uint8
  * src/feature_based_slam/tracker/src/estimate_so3_inlier_count.cpp:17-48 —, that is ransac::ransac — src/ransac/include/ransac/ransac.hpp:27-56 —
  * over the three-point PureRorationSolver — src/energy/n_point_solvers/src/pure_rotation_estimator.cpp:14-67 —, which
  * MonocularInitializer::tick — monocular_initializer.cpp:71-94 — and the feature-based tracker — add_new_frame.cpp:36-45 — run on every
- * frame).  Not built: the essential-matrix RANSAC, ORB descriptors and matching, the SimpleRadialCamera instantiation
- * (triangulation and the refinement are dsopp_hip_geometric_ba_* below, the PnP RANSAC dsopp_hip_pnp_ransac_* below them).
+ * frame).  Not built: ORB descriptors and matching, the SimpleRadialCamera instantiation
+ * (triangulation and the refinement are dsopp_hip_geometric_ba_* below, the PnP RANSAC dsopp_hip_pnp_ransac_* below them, the
+ * essential-matrix RANSAC dsopp_hip_two_view_ransac_* below those).
  *
  * The arithmetic is fixed here; tests/rotation_ransac_model.py is its NumPy form.  Everything is binary64 (the reference's Precision);
  * float points of the flow tracker are widened by the caller.
@@ -471,8 +472,8 @@ int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, 
  * src/feature_based_slam/tracker/src/monocular_tracker.cpp:54-68 —, triangulatePoints — triangulate_points.cpp:47-71, triangulation.hpp:52-64 —,
  * optimizeTransformations — refine_track.cpp:16-83, which runs Ceres SPARSE_SCHUR with a Huber loss through
  * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  Not built: the
- * essential-matrix RANSAC (OpenGV; estimateSE3PnP is dsopp_hip_pnp_ransac_* below), the SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks, the
- * two-view triangulatePoints that only initializePoses calls.
+ * SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks (estimateSE3PnP is dsopp_hip_pnp_ransac_* below;
+ * the essential-matrix RANSAC and the two-view triangulatePoints that only initializePoses calls are dsopp_hip_two_view_ransac_* below it).
  *
  * The arithmetic is fixed here; tests/geometric_ba_model.py is its NumPy form.  Everything is binary64.
  *   Problem: a pinhole camera fx, fy, cx, cy, width, height; F frames, 2 <= F <= 16 (a 17th is DSOPP_HIP_ERR_CAPACITY; the reference uses
@@ -684,6 +685,129 @@ int dsopp_hip_pnp_ransac_estimate(dsopp_hip_pnp_ransac *r, double fx, double fy,
                                   const double *positions, const double *observations, int iterations, const int32_t *samples, double threshold_px,
                                   const dsopp_hip_pnp_ransac_options *options, dsopp_hip_pnp_ransac_result *result, int32_t *inlier_indices,
                                   int32_t *hyp_num_solutions, double *hyp_poses, int32_t *hyp_counts);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The two-view pose that initialises a track: a five-point essential-matrix RANSAC over the matches of the first and the last bootstrap
+ * frame, the Sampson refinement around its re-selection, and the two-view triangulation behind it (replaces estimateSO3xS2 —
+ * src/feature_based_slam/tracker/src/estimate_so3xs2.cpp:23-110 —, refineSO3xS2 — src/energy/problems/src/so3xs2_refinement.cpp:13-50 with
+ * cost_functors/sampson_distance_cost.hpp:17-66 — and the two-view triangulatePoints — triangulate_points.cpp:18-45 with
+ * epipolar_geometry/triangulation.hpp:26-42: steps I and II of initializePoses, initialize_poses.cpp:29-45; steps III to V are
+ * dsopp_hip_pnp_ransac_* and dsopp_hip_geometric_ba_* above).  The reference hands step I to OpenGV (Stewenius' five-point solver inside
+ * OpenGV's RANSAC, then optimizeModelCoefficients and selectWithinDistance) and refines with Ceres (Sampson error, Huber loss, quaternion
+ * x S^2 parameterisation).  Neither library is part of the reference's tree, so, like the bundle adjustment and the PnP above, this is the
+ * library's own algorithm for the same job.  Mirrored: which landmarks are matches (:33-46), the minimum number of matches (:48), the
+ * threshold's conversion (:55-56), refine-then-reselect (:58-68), the normalised translation (:70-71), which projections are removed
+ * (:77-86, in the host mirror), the refinement's residual, loss, threshold and iteration limit (:88-105) and the returned pair (:109).
+ * The library's own: the five-point solver, the two-view measure, both refinements' iteration.  Unpinned: OpenGV's sampler, its three
+ * extra disambiguation points, its stopping rule and its optimiser; Ceres' second-order corrector and its trust-region path.
+ * Not built: the SimpleRadialCamera instantiation, the focal-length refinement.
+ *
+ * Direction.  The reference names the result t_t_r, but it maps the TARGET (last) frame into the REFERENCE (first) frame: OpenGV's
+ * central relative pose is frame 2 seen from frame 1 with (reference_bearings, target_bearings) as frames 1 and 2 (:52); the refinement
+ * is handed its two point lists swapped (:93-99), so its cost x_first . E x_last with E = hat(t) R (sampson_distance_cost.hpp:52-59) is the
+ * epipolar constraint of exactly that direction; and initialize_poses.cpp:31-33 stores the result as last_frame.t_world_agent with the
+ * first frame at the identity.  The same holds for the triangulation, whose `target` is the first frame's ray and whose t_t_r argument is
+ * t_first_last (triangulate_points.cpp:22-37).  That direction is kept here.
+ *
+ * The arithmetic is fixed here; tests/two_view_ransac_model.py is its NumPy form.  Everything is binary64.
+ *   Inputs: a pinhole camera fx, fy, cx, cy, width, height; n matches: A[j], the first frame's observation, and B[j], the last frame's
+ *     (x, y); `iterations` samples S[i] of five distinct indices < n, drawn by the caller; threshold_px (the reference's
+ *     essential_matrix_ransac_threshold, 0.5); min_matches (min_ransac_matches, 50); the refinement's options.
+ *   Pose: (R, t) with |t| = 1 and p_A = R p_B + t, as 12 doubles: R row-major, then t.  E = hat(t) R, and f_A . E f_B = 0.
+ *   roi(p) and unproject(p) as in the rotation RANSAC's block; f_A = normalize(unproject(A[j])), f_B likewise.  A match with an
+ *     observation that fails roi is no match of the reference (:40-41): it is never an inlier, a sample that holds one is invalid, and it
+ *     does not count in `matches`.  matches < min_matches returns without a winner and without looking at the samples.
+ *   Triangulation of a pair under a pose (triangulation.hpp:29-41): a = f_A, b = normalize(R f_B), den = 1 / (1 - (a.b)^2),
+ *     alpha = den (a.t - (a.b)(b.t)), beta = den ((a.b)(a.t) - b.t), X_A = (alpha a + beta b + t) / 2, X_B = R^T (X_A - t).
+ *   Threshold and measure: t_ang = 1 - cos(atan(threshold_px / fx)), computed once on the host;
+ *     d_j = (1 - f_A . X_A / |X_A|) + (1 - f_B . X_B / |X_B|), the role of OpenGV's two-view reprojection distance; a match is an inlier
+ *     iff d_j < t_ang (strict; a NaN is no inlier, and parallel rays give one).
+ *   Hypothesis i: its essential matrices are the real E in the four-dimensional null space of the five constraints f_A (x) f_B that
+ *     satisfy det E = 0 and 2 E E^T E - tr(E E^T) E = 0, at most ten.  With an orthonormal basis E_1 .. E_4 of the null space and
+ *     E = x E_1 + y E_2 + z E_3 + E_4 these are ten cubics in (x, y, z).  Each solution is polished on those ten cubics, evaluated on E
+ *     itself, by Gauss-Newton (3 x 3 normal equations; at most 12 steps, until |step|^2 <= 1e-28 (1 + |(x, y, z)|^2)), so the route that
+ *     found it contributes second-order error only; E is then scaled to |E|_F^2 = 2, and an E on which a constraint still exceeds 1e-9 in
+ *     magnitude is dropped.  Any basis serves, and any route to the solutions that reaches them to rounding (the model: the 10 x 10 action
+ *     matrix from the Gauss-Jordan-reduced 10 x 20 coefficient matrix and numpy.linalg.eig; the device: the hidden-variable form, a
+ *     polynomial of degree 10 in z whose real roots are bracketed through the chain of its derivatives and closed by the PnP's safeguarded
+ *     Newton iteration).  Per E = U diag(s, s, 0) V^T the four candidates are R in {U W V^T, U W^T V^T}, signs fixed so that det R = +1,
+ *     with t = +-u_3 (the device takes them in closed form: t the unit normal of E's columns, R = Cof(E) -+ hat(t) E); the one candidate
+ *     under which all five sample pairs have alpha > 0 and beta > 0 is kept, an E without one is dropped.  Non-finite poses are dropped;
+ *     the surviving poses are listed in descending trace R.  A sample with an observation outside roi is invalid, with zero solutions.
+ *     Where two solutions nearly coincide their number and the poses are unpinned; a rank-deficient sample (a repeated pair of
+ *     observations, ...) is unpinned too, but yields either nothing or finite poses with an orthonormal R and a unit t.
+ *   Score and selection as in the PnP's block: every solution is scored against all n matches; a hypothesis counts its best solution, the
+ *     lower index winning a tie; the winner is the greatest count, the lowest hypothesis winning a tie; best_iteration = -1 when no count
+ *     exceeds 0; no early stop.  dsopp_hip_two_view_ransac_default_iterations() = 256: log(0.01) / log(1 - w^5) <= 256 down to an inlier
+ *     share w = 0.447, well under the 0.6 below which initializePoses rejects the result anyway (:37).
+ *   Refinement, one routine run twice.  Residual (sampson_distance_cost.hpp:17-28, 52-66): x_A = ((A - c) / fx, 1), x_B = ((B - c) / fx, 1) —
+ *     fx divides both axes, as in the reference —, top = x_A . E x_B, bottom = |(E x_B)_xy / fx|^2 + |(x_A^T E)_xy / fx|^2,
+ *     r = top / sqrt(bottom), or top when bottom < 1e-16: pixels.  Cost = 1/2 sum rho(r^2) with the geometric BA's Huber rho (a = 1.5, the
+ *     reference's reprojection_threshold) and plain IRLS weights.  Five degrees of freedom (alpha, beta, omega): R <- R Exp(omega),
+ *     t <- normalize(t + alpha b1 + beta b2), b1 and b2 by the geometric BA's rule for its frame 1 with d = t; the Jacobian is analytic
+ *     (dE = hat(b1) R, hat(b2) R, E hat(e_k)).  H = sum w J^T J and b = sum w J^T r in a fixed order of summation; (H + lambda diag H)
+ *     delta = -b by a 5 x 5 Cholesky.  Control is the PnP block's driver: lambda_0 = 1e-4, / 2, x 10, both tolerances 1e-10, the state norm
+ *     |t|^2 + 1; max_iterations 40 (so3xs2_refinement.cpp:41); no pair to sum over ends the loop.  The flags are the
+ *     DSOPP_HIP_GEOMETRIC_BA_* bits, 0 = max_iterations.
+ *   Sequence: 1. the winner, pose_ransac; 2. the refinement over the winner's inliers (the role of optimizeModelCoefficients),
+ *     pose_reselect; 3. the re-selection with pose_reselect: its ascending index list is the call's inlier list and its length
+ *     inlier_count, the first number the reference returns; 4. the refinement over the re-selected inliers (refineSO3xS2), pose.  There
+ *     is no third selection.  Without a winner the three poses are the identity rotation with a zero translation.
+ *   Two-view triangulation (step II): for each pair X_A by the formulas above under pose_a_b; keep iff both observations pass roi,
+ *     X_A.z > 0, f_A . X_A / |X_A| > cos_threshold and f_B . X_B / |X_B| > cos_threshold (triangulation_cos_threshold, 0.9999; strict)
+ *     and everything is finite; X_world = pose_world_a X_A is written for every pair.
+ * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct dsopp_hip_two_view_ransac dsopp_hip_two_view_ransac;
+typedef struct dsopp_hip_two_view_ransac_options {
+  double a;                   /* the Huber width, 1.5 */
+  double lambda_0;            /* 1e-4 */
+  double function_tolerance;  /* 1e-10 */
+  double parameter_tolerance; /* 1e-10 */
+  double decrease_factor;     /* lambda is divided by it on accept, 2 */
+  double increase_factor;     /* lambda is multiplied by it on reject, 10 */
+  int32_t max_iterations;     /* 40, of either refinement */
+  int32_t reserved;
+} dsopp_hip_two_view_ransac_options;
+typedef struct dsopp_hip_two_view_ransac_result {
+  int32_t matches;              /* the pairs with both observations inside the ROI, the reference's matching number */
+  int32_t best_iteration;       /* the winning hypothesis, -1 when no count exceeded 0 */
+  int32_t best_solution;        /* its solution, 0 .. 9; -1 without a winner */
+  int32_t ransac_inlier_count;  /* the winner's count */
+  int32_t inlier_count;         /* the inliers of pose_reselect: the length of the index list, the reference's first number */
+  int32_t refine_iterations[2]; /* per stage: iterations run, accepted or not */
+  int32_t refine_flags[2];      /* per stage: the DSOPP_HIP_GEOMETRIC_BA_* bits that ended the loop; 0 = max_iterations */
+  int32_t reserved;
+  double cost_initial[2], cost_final[2]; /* per stage: 1/2 sum rho(r^2) over the stage's inliers, before and after */
+  double pose_ransac[12];       /* the winner's pose: R row-major, then t; p_A = R p_B + t */
+  double pose_reselect[12];     /* after the first refinement: the pose of the re-selection */
+  double pose[12];              /* after the second refinement: the call's pose */
+} dsopp_hip_two_view_ransac_result;
+int dsopp_hip_two_view_ransac_default_iterations(void);
+void dsopp_hip_two_view_ransac_default_options(dsopp_hip_two_view_ransac_options *options);
+/* `stream` is a hipStream_t (NULL = a stream of its own); all work of the object runs on it.  Its buffers grow with n and iterations. */
+int dsopp_hip_two_view_ransac_create(int device, void *stream, dsopp_hip_two_view_ransac **out);
+void dsopp_hip_two_view_ransac_destroy(dsopp_hip_two_view_ransac *r);
+/* One launch and one wait, blocking.  points_a, points_b: n x 2 doubles; samples: iterations x 5 int32; options: NULL = the defaults;
+ * inlier_indices: room for n int32, the first result->inlier_count of which are written, ascending.  Optional (NULL) per-hypothesis
+ * outputs, there so that a divergence from the stated arithmetic can be located: hyp_num_solutions (iterations int32), hyp_poses
+ * (iterations x 10 x 12 doubles, unused slots zero), hyp_counts (iterations x 10 int32, unused slots zero); they cover every hypothesis.
+ * n = 0, iterations = 0 or matches < min_matches returns at once without a winner (the samples are then not read).
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: n < 0, iterations < 0, min_matches < 0, 0 < n < 5 with iterations > 0, a sample index outside
+ * 0 .. n - 1 or repeated within its sample, an observation, threshold or intrinsic that is not finite, an option that is not finite or
+ * out of range (a <= 0, lambda_0 < 0, a factor <= 0, max_iterations < 0), a NULL required argument. */
+int dsopp_hip_two_view_ransac_estimate(dsopp_hip_two_view_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
+                                       const double *points_a, const double *points_b, int iterations, const int32_t *samples, double threshold_px,
+                                       int min_matches, const dsopp_hip_two_view_ransac_options *options,
+                                       dsopp_hip_two_view_ransac_result *result, int32_t *inlier_indices, int32_t *hyp_num_solutions,
+                                       double *hyp_poses, int32_t *hyp_counts);
+/* The two-view triangulation; one launch and one wait, blocking.  pose_a_b: the pose above (the last frame into the first);
+ * pose_world_a: the first frame's t_world_agent, 12 doubles; positions: n x 3 doubles, X_world of every pair; keep: n bytes, 1 = the
+ * reference would set the landmark's position.  DSOPP_HIP_ERR_INVALID_ARGUMENT: n < 0, an observation, intrinsic or pose entry that is
+ * not finite, a cos_threshold that is not a number, a NULL required argument. */
+int dsopp_hip_two_view_ransac_triangulate(dsopp_hip_two_view_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
+                                          const double *points_a, const double *points_b, const double pose_a_b[12], const double pose_world_a[12],
+                                          double cos_threshold, double *positions, uint8_t *keep);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Semantic segmentation: the per-frame camera mask and the class image of a frame (replaces, per frame, the undistortion of the class
