@@ -1152,7 +1152,8 @@ SolveArgs makeSolveArgs(W &w) {
 
 size_t solveSmemBytes(int K) {
   const size_t N = static_cast<size_t>(K) + 1;
-  return (N * (N + 1) + 4 * static_cast<size_t>(K) + 32 + 38 * static_cast<size_t>(kMaxFrames)) * sizeof(double);
+  // (the last term: the column substitution's exchange, one double per thread of the helper waves — choleskyAugmentedImpl's `ex`)
+  return (N * (N + 1) + 4 * static_cast<size_t>(K) + 32 + 38 * static_cast<size_t>(kMaxFrames) + (kSchurThreads - 64)) * sizeof(double);
 }
 
 /** K3 */

@@ -11,7 +11,8 @@
 //   * the Jacobi guard (pivot threshold) is taken while the diagonal is written, not in a pass of its own.
 // The factorisation itself (blocked Cholesky over the frame blocks with a look-ahead panel wave, right-hand side as an extra row,
 // v_rsq_f64 seed + two Newton steps, pivots below 1e-30 of the Jacobi-scaled diagonal treated as zero) and the back-substitution
-// are shared with assembleSolveKernel: choleskyAugmented and backSubstituteWave (pba_solve_kernels.hpp), one definition each.
+// are shared with assembleSolveKernel: choleskyAugmentedImpl — with the back-substitution riding under it on its helper waves where there are
+// enough of them — and backSubstituteWave (pba_solve_kernels.hpp), one definition each.
 #pragma once
 #include "pba_solve_kernels.hpp"
 
@@ -139,7 +140,10 @@ __device__ __forceinline__ void combBlockDecode(int b, int &bi, int &bj) {
  *  for the same counter BEFORE they decide: they read the scalar workgroup's sums and, per landmark, the record the Schur reducers stored at
  *  agent scope (reduceSchurBody<true>) with agent-scope loads — the choice "reducers store, landmark workgroups read behind the counter", not
  *  a recomputation.  No fence anywhere: a release wrote the whole L2 back and arrived 5 us late. */
-template <int THREADS, int COPIES, bool FUSED>
+/** WG > THREADS (the fused launch up to 8 keyframes: 512 against 256): the solver's upper waves come along as helpers of the column
+ *  substitution (choleskyAugmentedImpl).  They pass every barrier of the head — which gives them nothing to do: each piece of its work is
+ *  dealt out by thread index below THREADS — and leave behind the barrier that publishes the step. */
+template <int THREADS, int COPIES, bool FUSED, int WG = THREADS>
 __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_ticket_p, double *bs_hand_next_p, const LmControl *dec_in_p,
                                                   const double *dec_scalars_p, const double *comb_p, const FrameDev *frames_p, WindowState *st_p,
                                                   int F_p, const SolveCombArgs &a, const double *t_fused) {
@@ -153,7 +157,9 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
   double *epsl = Linv + 36 * kMaxFrames;             // K: state increment eps of every frame
   double *stpl = epsl + K;                           // K: the new step (-x), kept in LDS for the pair refresh / prior energy
   double *ab0l = stpl + K;                           // 2 F: affine brightness at the linearisation point
+  double *colx = ab0l + 2 * kMaxFrames;              // WG - 64: the column substitution's exchange (WG > THREADS; solveSmemBytes)
   const int tid = threadIdx.x;
+  const bool extra = WG > THREADS && tid >= THREADS;  // a helper wave behind the body's own threads
   const int wave = tid >> 6, lane = tid & 63;
   const long long sc_t_entry = (kStamps && a.dbg_stamps) ? wall_clock64() : 0;  // (tuning aid: the solving workgroup's first cycle)
 
@@ -622,7 +628,7 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
     if (!s_system_there) return;  // (the landmark workgroups' wait for the step runs out in turn)
     SC_STAMP(16);
     if (tid < K) rhs_c = __hip_atomic_load(glb(comb_p) + combBlockCount(F) * 64 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    loadBatch(0);
+    if (!extra) loadBatch(0);
   }
   const double *prior_diag = Linv;
   // Where entry e = base + tid + THREADS * u goes: its block index (e >> 6) is the same for the whole wave (THREADS and base are multiples
@@ -670,10 +676,12 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
       }
     }
   };
-  storeBatch(0);
-  for (int base = kBatch * THREADS; base < n_entries; base += kBatch * THREADS) {
-    loadBatch(base);
-    storeBatch(base);
+  if (!extra) {
+    storeBatch(0);
+    for (int base = kBatch * THREADS; base < n_entries; base += kBatch * THREADS) {
+      loadBatch(base);
+      storeBatch(base);
+    }
   }
   SC_STAMP(11);
   if (tid < K) {
@@ -697,27 +705,48 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
   // did: the copies that unify two request sites' registers where the paths join, the test of P.valid (which the compiler evaluates as soon
   // as the word is loaded unless it is pinned at its use), a kernel-argument array read through a vector load with vmcnt(0) behind it —
   // each a memory round trip on the solving workgroup's path.
-  if (main_wg) requestPairInputs();
+  // (with helper waves: behind the factorisation, by the panel wave, which is through first and waits for the helpers' last column step —
+  // held across their column steps these 44 registers were spilled, with a wait for the loads in front of the factorisation)
+  constexpr bool kColumns = WG > THREADS;  // the back-substitution rides under the factorisation (below)
+  if (!kColumns && main_wg) requestPairInputs();
 
-  choleskyAugmented<THREADS>(A, pv, Linv, F, tid, a.dbg_stamps);
-  SC_STAMP(2);
-  // what only the kernel's tail reads (pair-constant refresh, prior energy of the candidate) is requested HERE, to land under the
-  // back-substitution: requested at the head, these 24 doubles per thread were held — or spilled and reloaded — across the factorisation
-  if (ticketed) requestTailInputs();
-  if (wave == 0) {
-    backSubstituteWave(A, Linv, xs, F, lane);
-    SC_STAMP(6);
-  }
-  __syncthreads();
-  if (tid < K) {
-    const double x = xs[tid];
-    stpl[tid] = -x;
+  // the step leaves from whoever holds it: hand-over slot, step, frame state and the LDS copy the kernel's tail reads
+  auto stepOut = [&](int q, double x) {
+    stpl[q] = -x;
     // (a device-scope store: written through to where the other XCDs read — no flag, no fence: the slot's sentinel gives way to the value)
-    if (a.bs_hand) __hip_atomic_store(a.bs_hand + tid, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the waiting workgroups' copy
-    a.step[tid] = x;
-    st_p->step[tid >> 3][tid & 7] = -x;  // problem.hpp:353-357
+    if (a.bs_hand) __hip_atomic_store(a.bs_hand + q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the waiting workgroups' copy
+    a.step[q] = x;
+    st_p->step[q >> 3][q & 7] = -x;  // problem.hpp:353-357
+  };
+  if (kColumns) {
+    // the fused launch up to 8 keyframes (K <= 64, seven helper waves): the back-substitution rides under the factorisation on the waves
+    // behind the panel wave, which store the step themselves — no chain of K unknowns, no barrier and reload between substitution and
+    // step out.  The 256-thread launches of the two-launch path keep backSubstituteWave: their three helper waves carry the whole
+    // trailing update too and outlast the panel wave in the early block steps — the barrier behind factor + panel grew from 0.24 to 2.96 us
+    // per solve and the iteration lost 8 % (profiles/backsub_under_factorisation/first_form_*switch0*).
+    choleskyAugmentedImpl<THREADS, WG, true>(A, pv, Linv, F, tid, a.dbg_stamps, colx, true, stepOut);
+    if (main_wg) requestPairInputs();
+    SC_STAMP(2);
+    if (ticketed) requestTailInputs();  // (as below)
+    ldsBarrier();  // the new step is visible (stpl)
+    SC_STAMP(6);
+    if (extra) return;
+  } else {
+    choleskyAugmented<THREADS>(A, pv, Linv, F, tid, a.dbg_stamps);
+    SC_STAMP(2);
+    // what only the kernel's tail reads (pair-constant refresh, prior energy of the candidate) is requested HERE, to land under the
+    // back-substitution: requested at the head, these 24 doubles per thread were held — or spilled and reloaded — across the factorisation
+    if (ticketed) requestTailInputs();
+    if (wave == 0) {
+      backSubstituteWave(A, Linv, xs, F, lane);
+      SC_STAMP(6);
+    }
+    __syncthreads();
+    if (tid < K) stepOut(tid, xs[tid]);
+    SC_STAMP(3);   // (slots 2, 6, 3 as ever on this path: factorisation done, substitution done, step out — in front of the barrier)
+    ldsBarrier();  // the new step is visible (stpl)
   }
-  SC_STAMP(3);
+  if (kColumns) SC_STAMP(3);  // (the helper waves stored the step in front of the barrier above: slot 6 and slot 3 coincide)
   // prior + marginal energy at the candidate state x = eps + step (calculateEnergy, problem.hpp:293-312) and the frame part of the
   // norms acceptStep reports for this candidate (problem.hpp:366-388; read by the next decision from the control block): one
   // entry per thread of the waves behind wave 0, which meanwhile refreshes the pair constants
@@ -739,7 +768,6 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
   };
   if (fast_refresh) {
     // FEJ: only the current reprojection / brightness constants move with the state; all inputs are in registers / LDS
-    ldsBarrier();
     Rigid *E = reinterpret_cast<Rigid *>(A);  // [2][F]: exp(+xi_f), exp(-xi_f); A is free now
     if (tid < 2 * F) {
       const int f = tid < F ? tid : tid - F;
@@ -780,7 +808,6 @@ __device__ __forceinline__ void solveCombinedBody(char *smem_raw, unsigned *bs_t
     }
     priorMath();  // (waves 1..: beside the pair constants of wave 0)
   } else {
-    ldsBarrier();  // the new step is visible
     priorMath();
   }
   // (without first-estimate Jacobians every pair constant moves with the state: the host launches pairSetupKernel behind this
@@ -851,7 +878,8 @@ __global__ void __launch_bounds__(THREADS, 1) solveCombinedKernel(unsigned *bs_t
  *                                         advances by the same amount for every launch, which is what lets the host pass the target.
  *   n_reducers                            the solver: solveCombinedBody<THREADS, 1, true>, armed from the launch's first cycle (see there)
  *   (n_reducers, n_reducers + dec_blocks] the landmark workgroups of the solve launch
- * THREADS = 256 (up to 8 frames): the upper four waves of the solver and of the landmark workgroups leave before the body starts.
+ * THREADS = 256 (up to 8 frames): the upper four waves of the landmark workgroups leave before the body starts; the solver's stay as helper
+ * waves of its column substitution (solveCombinedBody, WG).
  * Only the solver and the landmark workgroups wait, for workgroups of the same launch that wait for nobody; dec_blocks + 1 workgroups fit
  * on the device at once (launchReduceSolveFused), so a reducer that has not been dispatched yet is only ever delayed by them.
  */
@@ -895,8 +923,9 @@ __global__ void __launch_bounds__(kSchurThreads) reduceSolveFusedKernel(const Lm
     }
     __syncthreads();
   }
-  if (static_cast<int>(threadIdx.x) >= THREADS) return;
-  solveCombinedBody<THREADS, 1, true>(smem_raw, nullptr, sa.bs_hand_next, ctrl_p, nullptr, sa.comb, sa.frames, sa.st, F_p, sa, s_sums);
+  // (the solver's upper waves stay: helpers of its column substitution — solveCombinedBody, WG; the landmark workgroups' leave)
+  if (THREADS < kSchurThreads && static_cast<int>(threadIdx.x) >= THREADS && static_cast<int>(blockIdx.x) != n_reducers) return;
+  solveCombinedBody<THREADS, 1, true, kSchurThreads>(smem_raw, nullptr, sa.bs_hand_next, ctrl_p, nullptr, sa.comb, sa.frames, sa.st, F_p, sa, s_sums);
 }
 
 }  // namespace dsopp_hip

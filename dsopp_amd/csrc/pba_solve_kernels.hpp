@@ -882,9 +882,33 @@ __device__ __forceinline__ double readLane(double v, int src_lane) {
  * last row is y^T = (L^-1 b)^T.  pv: the K Jacobi-scaled diagonals diag + 10 the zero-pivot guard refers to.  Linv: reciprocal pivots out
  * (frame block kb at 36 kb + lowIdx(c, c)).  stamps: nullable, -DDSOPP_HIP_STAMPS builds only (slots 12 - 15 of the fused kernel).
  * The caller has a barrier between its last store to A / pv and this call; the routine ends behind one.
+ *
+ * COLUMNS (and `cols`, K <= 64 only): the back-substitution rides under the factorisation, on the waves behind the panel wave.  The step is
+ * x = L^-T y, i.e. x_q = z_q . y with z_q = L^-1 e_q, column q of L^-1 — a forward substitution that needs block row kb of L only once block
+ * column kb has been factored, which is what the barrier of block step kb announces.  The K columns are independent, so while the panel wave
+ * factors block column kb + 1 the helper waves take every column q <= 8 kb + 7 through block row kb.  Behind the last barrier only the 8-row
+ * solve with the last diagonal block is left, instead of backSubstituteWave's chain of K dependent unknowns.
+ * Mapping: a helper wave carries a whole frame block of columns, eight lanes per column q = 8 b + g (g = lane >> 3), lane rho = lane & 7
+ * owning row rho of every block row.  RESTRICTION: H = WG / 64 - 1 is 3 or 7, the two workgroup sizes of today's callers (static_assert
+ * below); which wave carries which block is a hand-written deal for each of the two (`first_block`), not a general one over any number of
+ * helper waves — another H needs its own deal there, nothing else in the routine depends on H.  WG - THREADS threads behind the factorisation's own
+ * (the fused launch's upper waves) only substitute.
+ * Order of the arithmetic of ONE column (tests/dense_solve_columns_model.py states it in NumPy), the same for every H and every owner:
+ *   s_i = 0 for the block rows i > b, x = 0;  for kb = b .. F-1:
+ *     t = e_g (kb == b) or -s_kb; the 8-row solve z_c = (t_c - sum_{c' < c} L[8 kb + c][8 kb + c'] z_c') inv[8 kb + c], c and c' ascending
+ *     (every lane of the column redundantly, so that all eight hold z); x += z_c y[8 kb + c], c ascending;
+ *     for i > kb: s_i[rho] += L[8 i + rho][8 kb + c] z_c, c ascending                — every multiply-add one fma.
+ * A pivot under the guard has inv = 0 and a zero column of L: row r of every column and the whole column r are 0, so x_r = 0 and the rest
+ * solves the reduced system, as backSubstituteWave does through gi = 0.
+ * ex: WG - 64 doubles of LDS, the in-column exchange of t (each lane stores its row, all eight read the column's).  emit(q, x_q) is called
+ * by one lane per column behind the last barrier of the factorisation; the caller's next barrier publishes what it stores to LDS.
+ * K > 64 (9 - 16 keyframes) keeps backSubstituteWave: eight column blocks per helper wave do not fit its registers, and z in LDS (K^2
+ * doubles) does not fit beside A at K = 96 .. 128; those windows are not the headline.
  */
-template <int THREADS>
-__device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, double *Linv, int F, int tid, long long *stamps) {
+template <int THREADS, int WG, bool COLUMNS, class Emit>
+__device__ __forceinline__ void choleskyAugmentedImpl(double *A, const double *pv, double *Linv, int F, int tid, long long *stamps, double *ex, bool cols,
+                                                      Emit emit) {
+  static_assert(WG >= THREADS && (WG == 256 || WG == 512), "three or seven helper waves behind the panel wave (first_block)");
   const int K = kBlk * F;
   const int N = K + 1;   // augmented with the right-hand side row
   const int ld = N + 1;
@@ -983,12 +1007,134 @@ __device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, d
       cs_t = now;
     }
   };
+  // ---- the column substitution of the helper waves (COLUMNS; see the routine's comment)
+  constexpr int H = WG / 64 - 1;          // helper waves
+  constexpr int NS = (8 + H - 1) / H;     // frame blocks of columns per helper wave (K <= 64)
+  const bool helper_cols = COLUMNS && cols;  // (workgroup-uniform)
+  const bool helper = helper_cols && wave > 0;
+  const int cg = lane >> 3, rho = lane & 7;
+  double cs[NS][kBlk - 1], cx[NS];        // per column block of this wave: s of the block rows 1 .. 7 (this lane's row), x
+#pragma unroll
+  for (int sl = 0; sl < NS; ++sl) {
+    cx[sl] = 0;
+#pragma unroll
+    for (int i = 0; i < kBlk - 1; ++i) cs[sl][i] = 0;
+  }
+  // Which helper wave carries which frame block of columns.  With seven helper waves (the fused launch) the early blocks, whose columns run
+  // through every block step, go to the waves that have no share in the trailing update (7, 6, 5), the late ones to the waves that do (3, 2,
+  // 1) — their trailing update has shrunk by the time those columns start — and block 6, which at 7 keyframes has nothing to do before the
+  // last barrier, to wave 4, the wave that shares the panel wave's SIMD.  Three helper waves: block b on wave 1 + b mod 3.
+  const int first_block = H == 7 ? (wave >= 5 ? 7 - wave : (wave == 4 ? 6 : 6 - wave)) : wave - 1;
+  // INVARIANT the block-row updates below rest on (updateRange): cs[sl][i - 1], this lane's row of s_i, is READ exactly once — by the exchange
+  // for block row i (own = cs[sl][kb - 1] at step kb = i, or at the end of step F - 2 for i = F - 1) — and only for b < i < F.  Every
+  // update of it that counts (steps kb = b .. i - 1) comes before that read.  The straight-line updates also write cs[sl][i - 1] at steps
+  // kb >= i (from entries on / above the diagonal of A, which nobody wrote: any bits) and for i >= F (from block row F - 1's operands): those
+  // values are dead — no exchange, no x and no store ever reads them — and every address they are computed from lies inside A.  Whoever adds
+  // a second reader of cs has to restore the guards (i > kb && i < F) first.
+  // t = -s_kb of a column block, every lane's row handed to the eight lanes of its column through LDS
+  double *exw = ex + (wave > 0 ? wave - 1 : 0) * 64;
+  auto exchange = [&](int sl, int kb, double (&t)[kBlk]) {
+    double own = 0;
+#pragma unroll
+    for (int i = 1; i < kBlk; ++i) own = i == kb ? cs[sl][i - 1] : own;
+    exw[lane] = -own;
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int c = 0; c < kBlk; ++c) t[c] = exw[kBlk * cg + c];
+    __builtin_amdgcn_wave_barrier();  // (the next store stays behind these reads)
+  };
+  // (the first column block's t for block row F - 1 is exchanged at the end of step F - 2, in front of the last barrier: one LDS round trip
+  // less behind it.  The other column blocks of a wave exchange behind the barrier: sixteen registers each.)
+  double t_last[kBlk];
+#pragma unroll
+  for (int c = 0; c < kBlk; ++c) t_last[c] = 0;
+  auto columnStep = [&](int kb, auto last_tag) {
+    constexpr bool LAST = decltype(last_tag)::value;  // block row F - 1: nothing below it to update
+    // block row kb of every column this wave carries; L_kb,kb, its pivot reciprocals and y_kb are the same words for every lane
+    const int k0 = kb * kBlk;
+    if (first_block > kb) return;  // (wave-uniform) none of this wave's columns has started
+    const double *lrow = A + rho * ld + k0;  // this lane's row of block row 0, at block column kb
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+      const int b = first_block + H * sl;  // (wave-uniform)
+      if (b > kb || b >= F) continue;
+      // (the diagonal block and its reciprocals are fetched per column block, where they are used: held across the block-row updates of a
+      // previous column block they cost 72 registers, and the fused launch's kernel spilled the solver's pair inputs for them — a memory
+      // round trip in front of the factorisation)
+      double ld_[28], iv[kBlk];
+      {
+        int e = 0;
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) {
+          iv[c] = Linv[kb * 36 + lowIdx(c, c)];
+#pragma unroll
+          for (int c2 = 0; c2 < c; ++c2) ld_[e++] = A[(k0 + c) * ld + k0 + c2];
+        }
+      }
+      double t[kBlk];
+      if (b == kb) {
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) t[c] = c == cg ? 1.0 : 0.0;
+      } else if (LAST && sl == 0) {
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) t[c] = t_last[c];
+      } else {
+        exchange(sl, kb, t);
+      }
+      double z[kBlk];
+      {
+        int e = 0;
+#pragma unroll
+        for (int c = 0; c < kBlk; ++c) {
+          double acc = t[c];
+#pragma unroll
+          for (int c2 = 0; c2 < c; ++c2) acc = fma(-ld_[e++], z[c2], acc);
+          z[c] = acc * iv[c];
+        }
+      }
+      double x = cx[sl];
+#pragma unroll
+      for (int c = 0; c < kBlk; ++c) x = fma(z[c], A[K * ld + k0 + c], x);
+      cx[sl] = x;
+      if (!LAST) __builtin_amdgcn_sched_barrier(0);
+      // The block rows below: straight-line code over fixed ranges of them, so that a range's operands are requested before its first chain
+      // starts and its chains interleave (one branch per block row left each row's LDS latency and its eight dependent fma exposed, one
+      // after the other).  Rows of a range that need no update take one all the same: an s that has been consumed (i <= kb), or that nobody
+      // reads (i >= F: the operands of block row F - 1 stand in).  Ranges of at most three rows, kept apart: the operands of all seven at once
+      // are 112 registers.
+      auto updateRange = [&](auto lo_tag, auto hi_tag) {
+        constexpr int LO = decltype(lo_tag)::value, HI = decltype(hi_tag)::value;
+#pragma unroll
+        for (int i = LO; i < HI; ++i) {
+          const double *lr = lrow + kBlk * min(i, F - 1) * ld;
+          double sacc = cs[sl][i - 1];
+#pragma unroll
+          for (int c = 0; c < kBlk; ++c) sacc = fma(lr[c], z[c], sacc);
+          cs[sl][i - 1] = sacc;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      if (!LAST) {
+        if (kb < 3) updateRange(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
+        updateRange(std::integral_constant<int, 4>{}, std::integral_constant<int, 6>{});
+        updateRange(std::integral_constant<int, 6>{}, std::integral_constant<int, kBlk>{});
+        if (sl == 0 && kb + 2 == F) exchange(0, kb + 1, t_last);
+      }
+    }
+  };
   if (wave == 0) factorAndPanel(0);
   ldsBarrier();
   csMark(2);
-  for (int kb = 0; kb < F; ++kb) {
+  // (block step F - 1 has nothing left to factor or to update — two barriers with nothing between them.  With the column substitution the
+  // loop ends in front of it, behind the barrier of factorAndPanel(F - 1); without, the loop is kept as it always was: the kernels that
+  // substitute with backSubstituteWave then compile to the code they had, and dropping the step there measured nothing)
+  // (two loops over one body rather than one loop with a bound chosen at run time: with the bound in a variable the compiler kept the fused
+  // kernel's step index in a vector register — compares and selects of the helper waves' column steps on the vector unit)
+  auto blockStep = [&](int kb, auto has_next_tag) {
+    constexpr bool HAS_NEXT = decltype(has_next_tag)::value;  // block column kb + 1 exists (known where the loop ends in front of step F - 1)
     const int k0 = kb * kBlk, k1 = k0 + kBlk, k2 = k1 + kBlk;
-    if (kb + 1 < F) {
+    if ((WG == THREADS || tid < THREADS) && (HAS_NEXT || kb + 1 < F)) {
       // all waves: block column kb+1 (rows k1 .. N-1, columns k1 .. k1+7) -= panel kb contribution (one element per thread)
       const int n_el = (N - k1) * kBlk;
       for (int e = tid; e < n_el; e += THREADS) {
@@ -1005,31 +1151,55 @@ __device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, d
     ldsBarrier();
     csMark(1);
     if (wave == 0) {
-      if (kb + 1 < F) factorAndPanel(kb + 1);
+      if (HAS_NEXT || kb + 1 < F) factorAndPanel(kb + 1);
       csMark(2);
     } else {
-      // trailing update of columns >= k2 with panel kb: A_ij -= sum_c L_ic L_jc  (the other waves as a 12 x 16 / 28 x 16 tile)
-      const int t = tid - 64, tr = t >> 4, tc = t & 15;
-      for (int row = k2 + tr; row < N; row += (THREADS - 64) / 16) {
-        const double *li = A + row * ld + k0;
-        double lic[kBlk];
+      if (WG == THREADS || tid < THREADS) {
+        // trailing update of columns >= k2 with panel kb: A_ij -= sum_c L_ic L_jc  (the other waves as a 12 x 16 / 28 x 16 tile)
+        const int t = tid - 64, tr = t >> 4, tc = t & 15;
+        for (int row = k2 + tr; row < N; row += (THREADS - 64) / 16) {
+          const double *li = A + row * ld + k0;
+          double lic[kBlk];
 #pragma unroll
-        for (int c = 0; c < kBlk; ++c) lic[c] = li[c];
-        for (int col = k2 + tc; col <= row; col += 16) {
-          const double *lj = A + col * ld + k0;
-          double sacc = 0;
+          for (int c = 0; c < kBlk; ++c) lic[c] = li[c];
+          for (int col = k2 + tc; col <= row; col += 16) {
+            const double *lj = A + col * ld + k0;
+            double sacc = 0;
 #pragma unroll
-          for (int c = 0; c < kBlk; ++c) sacc += lic[c] * lj[c];
-          A[row * ld + col] -= sacc;
+            for (int c = 0; c < kBlk; ++c) sacc += lic[c] * lj[c];
+            A[row * ld + col] -= sacc;
+          }
         }
       }
+      // block row kb of L and y_kb are final (factorAndPanel(kb), a barrier ago); nobody writes them again
+      if (helper) columnStep(kb, std::false_type{});
     }
     ldsBarrier();
     csMark(3);
+  };
+  if (helper_cols) {
+    for (int kb = 0; kb + 1 < F; ++kb) blockStep(kb, std::true_type{});
+  } else {
+    for (int kb = 0; kb < F; ++kb) blockStep(kb, std::false_type{});
   }
   if (kStamps && stamps && tid == 0) {
     for (int q = 0; q < 4; ++q) stamps[12 + q] = cs_acc[q];
   }
+  if (helper) {
+    // what is left behind the last barrier: the 8-row solve with L_F-1,F-1 and the last eight terms of x
+    columnStep(F - 1, std::true_type{});
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+      const int b = first_block + H * sl;
+      if (b < F && rho == 0) emit(kBlk * b + cg, cx[sl]);
+    }
+  }
+}
+
+/** the factorisation alone (K > 64, and every caller that substitutes with backSubstituteWave) */
+template <int THREADS>
+__device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, double *Linv, int F, int tid, long long *stamps) {
+  choleskyAugmentedImpl<THREADS, THREADS, false>(A, pv, Linv, F, tid, stamps, nullptr, false, [](int, double) {});
 }
 
 /**
@@ -1037,6 +1207,11 @@ __device__ __forceinline__ void choleskyAugmented(double *A, const double *pv, d
  * going down from k = K-1, x_k = y_k / L_kk is broadcast with v_readlane and every lane j < k takes y_j -= L_kj x_k.
  * 4-7 instructions per unknown, no LDS round trip or barrier inside the chain (L_kj is prefetched a frame block ahead).
  * Wave 0 only (lane = its lane index), behind the barrier choleskyAugmented ends with; x goes to xs[0 .. K-1].
+ * Where it runs: K > 64 everywhere, and K <= 64 in the 256-thread launches of the two-launch loop.  The fused launch and assembleSolveKernel
+ * substitute under the factorisation instead (choleskyAugmentedImpl, COLUMNS): with the fused launch's seven helper waves that takes the
+ * 2.5 us of this chain at 7 keyframes down to 0.6 us behind the last barrier; with the three helper waves of a 256-thread launch, which
+ * carry the whole trailing update too, it lost (the barrier behind factor + panel 0.24 -> 2.96 us per solve, the C1 iteration 8 % slower:
+ * profiles/backsub_under_factorisation/).
  */
 __device__ __forceinline__ void backSubstituteWave(const double *A, const double *Linv, double *xs, int F, int lane) {
   const int K = kBlk * F, ld = K + 2;
@@ -1109,8 +1284,8 @@ __device__ __forceinline__ void backSubstituteWave(const double *A, const double
 
 /**
  * evaluateLinearSystemPrior (problem.hpp:37-77), calculateStep (problem.hpp:342-361) and NormalLinearSystem::solve
- * (normal_linear_system.cpp:10-16,52-59; here choleskyAugmented + backSubstituteWave, the arithmetic of the fused loop's
- * solveCombinedKernel) from the four systems H_pp, b_pp, H_schur, b_schur — one workgroup.  Three callers (pba.hip): stageLinearize and
+ * (normal_linear_system.cpp:10-16,52-59; here choleskyAugmentedImpl — up to 8 keyframes with the column substitution of its helper waves, the
+ * fused launch's arithmetic; above, backSubstituteWave behind it) from the four systems H_pp, b_pp, H_schur, b_schur — one workgroup.  Three callers (pba.hip): stageLinearize and
  * foldMarginalized assemble only (store_system: system_pose with priors, the symmetrised H_schur and Hsc_copy are written back, and
  * !do_solve ends the kernel there); stageStep — the stage API's calculate_step and every step of lm_mode 1 — solves: it stores the step
  * and, with first-estimate Jacobians, moves the pair constants that follow the state to eps + step (without them the host launches
@@ -1124,7 +1299,7 @@ __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArg
   double *A = reinterpret_cast<double *>(smem_raw);  // N x ld (lower triangle used)
   double *pv = A + N * ld;                           // K preconditioner
   double *xs = pv + K;                               // K + 16 scratch
-  double *Linv = xs + K + 16;                        // F x 36 inverses of the diagonal blocks
+  double *Linv = xs + K + 16;                        // kMaxFrames x 36: reciprocal pivots of the diagonal blocks
   const int tid = threadIdx.x;
   const double lam = a.lambda;
   // ---- system_pose = sums + priors (problem.hpp:39-62).  This thread's vector entries and the first tile batch are requested before
@@ -1240,13 +1415,21 @@ __global__ void __launch_bounds__(kSolveThreads, 1) assembleSolveKernel(SolveArg
   if (tid == 0) A[K * ld + K] = 0;
   if (!a.do_solve) return;
   __syncthreads();
-  choleskyAugmented<kSolveThreads>(A, pv, Linv, F, tid, nullptr);
-  if (tid < 64) backSubstituteWave(A, Linv, xs, F, tid);  // wave 0
-  __syncthreads();
-  if (tid < K) {
-    const double x = xs[tid];
-    a.step[tid] = x;
-    a.st->step[tid >> 3][tid & 7] = -x;  // problem.hpp:353-357
+  // up to 8 keyframes the back-substitution rides under the factorisation and the step leaves from the lanes that hold it
+  const bool by_columns = K <= 64;
+  double *ex = Linv + 36 * kMaxFrames;  // kSolveThreads - 64 doubles: the column substitution's exchange (solveSmemBytes)
+  choleskyAugmentedImpl<kSolveThreads, kSolveThreads, true>(A, pv, Linv, F, tid, nullptr, ex, by_columns, [&](int q, double x) {
+    a.step[q] = x;
+    a.st->step[q >> 3][q & 7] = -x;  // problem.hpp:353-357
+  });
+  if (!by_columns) {
+    if (tid < 64) backSubstituteWave(A, Linv, xs, F, tid);  // wave 0
+    __syncthreads();
+    if (tid < K) {
+      const double x = xs[tid];
+      a.step[tid] = x;
+      a.st->step[tid >> 3][tid & 7] = -x;  // problem.hpp:353-357
+    }
   }
   __syncthreads();  // the state written above is re-read from memory below
   Rigid *E = reinterpret_cast<Rigid *>(A);  // [2][F]: exp(+xi_f), exp(-xi_f); A is free now
