@@ -10,95 +10,38 @@
 // One launch.  A wave owns one hypothesis, four waves a workgroup.  Every lane of the wave solves the three-point problem redundantly
 // (no lane waits for another), then the lanes stride over the points with up to four poses in registers and the wave counts by ballot
 // and population count.  The solutions live in statically indexed slots throughout, so nothing of them goes to scratch.
-//   The workgroup that takes the last ticket of a counter closes the call: the selection (wave 0), then with all four waves the LM
-// refinement over the winner's inliers — thread-strided partial sums, a butterfly over the wave, the four waves' sums added in wave
-// order, so the same input gives the same bits — and the final inlier list in ascending order.  A ticket only: no workgroup waits for
-// another.  Hand-off to that workgroup as in rotation_ransac.hip: plain stores, every wave's vmcnt(0), a barrier, one lane's agent-scope
-// release, the ticket; behind the ticket one agent-scope acquire, a barrier, and loads that bypass the vector cache.
+//   The workgroup that takes the last ticket of a counter closes the call (lastWorkgroup, ransac_device.hpp): the selection (wave 0),
+// then with all four waves the LM refinement over the winner's inliers — thread-strided partial sums, a butterfly over the wave, the
+// four waves' sums added in wave order, so the same input gives the same bits — and the final inlier list in ascending order.
 //
 // The quartic's real roots: no closed form.  The positive roots of a polynomial lie one in each interval between its positive critical
 // points where its sign changes, so the second derivative's roots (a quadratic, closed form) bracket the derivative's, and those bracket
-// the quartic's; within a bracket a safeguarded Newton iteration (bisection whenever Newton leaves the bracket or slows down) runs to its
-// fixed point.  Whether a pair of roots exists is then decided by the polynomial's sign at a critical point, which an error of the
-// critical point moves in second order only.
-#include "common.hpp"
+// the quartic's; within a bracket a safeguarded Newton iteration (bracketedRoot, ransac_device.hpp) runs to its fixed point.  Whether a
+// pair of roots exists is then decided by the polynomial's sign at a critical point, which an error of the critical point moves in
+// second order only.
+#include "ransac_device.hpp"
 #include "se3_math.hpp"
-
-#include <cfloat>
-#include <climits>
-#include <cmath>
-#include <memory>
+#include "staged_call.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dsopp_hip {
 namespace {
+using namespace ransac;
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
-constexpr int kMaxRootSteps = 200;  // a bracket of doubles is exhausted by ~64 bisections (geometric ones across magnitudes); the cap only bounds the loop
 constexpr double kMinDepth = 0.001;
 
-struct PnpParams {
-  double fx, fy, cx, cy, xmax, ymax, t_ang;
+struct PnpParams : PinholeRoi {
+  double t_ang;
   double lambda_0, function_tolerance, parameter_tolerance, decrease_factor, increase_factor;
   int n, iterations, max_iterations;
 };
-
-__device__ __forceinline__ bool insideRoi(double x, double y, const PnpParams &p) { return x >= 4.0 && x <= p.xmax && y >= 4.0 && y <= p.ymax; }
-
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-/** f = normalize(unproject(x, y)) */
-__device__ __forceinline__ void bearing(double x, double y, const PnpParams &p, double *f) {
-  const double ux = (x - p.cx) / p.fx, uy = (y - p.cy) / p.fy;
-  const double norm = sqrt(ux * ux + uy * uy + 1.0);
-  f[0] = ux / norm;
-  f[1] = uy / norm;
-  f[2] = 1.0 / norm;
-}
 
 // ---- polynomials of degree <= 4, c[0] + c[1] x + ... + c[4] x^4
 
 __device__ __forceinline__ double evalPoly(const double (&c)[5], double x) { return (((c[4] * x + c[3]) * x + c[2]) * x + c[1]) * x + c[0]; }
 __device__ __forceinline__ double evalDerivative(const double (&c)[5], double x) {
   return ((4.0 * c[4] * x + 3.0 * c[3]) * x + 2.0 * c[2]) * x + c[1];
-}
-
-/** the middle of a bracket 0 <= lo < hi: geometric where the ends differ in magnitude, so that a bracket up to a polynomial's root bound
- *  is exhausted as fast as a narrow one */
-__device__ __forceinline__ double middle(double lo, double hi) {
-  if (lo == 0.0) return hi > 2.0 ? 1.0 : 0.5 * hi;
-  if (hi > 4.0 * lo) return sqrt(lo) * sqrt(hi);
-  return 0.5 * (lo + hi);
-}
-
-/** the root inside (lo, hi), where the polynomial has the sign of flo at lo and the other sign at hi */
-__device__ double bracketedRoot(const double (&c)[5], double lo, double hi, double flo) {
-  double x = middle(lo, hi), last_step = hi - lo;
-  for (int it = 0; it < kMaxRootSteps; ++it) {
-    const double f = evalPoly(c, x);
-    if (f == 0.0) return x;
-    if ((f > 0.0) == (flo > 0.0)) {
-      lo = x;
-    } else {
-      hi = x;
-    }
-    const double mid = middle(lo, hi);
-    if (!(mid > lo && mid < hi)) break;  // neighbouring doubles
-    double next = x - f / evalDerivative(c, x);
-    if (!(next > lo && next < hi) || !(fabs(next - x) <= 0.5 * fabs(last_step))) next = mid;
-    if (next == x) break;
-    last_step = next - x;
-    x = next;
-  }
-  return x;
 }
 
 /** the positive roots of c, one slot per interval between its positive critical points `crit` (ascending, NaN = none): a NaN slot holds
@@ -108,6 +51,8 @@ __device__ __forceinline__ void positiveRoots(const double (&c)[5], const double
   const double top = c[4] != 0.0 ? c[4] : (c[3] != 0.0 ? c[3] : (c[2] != 0.0 ? c[2] : c[1]));  // the leading coefficient
   const double big = fmax(fmax(fmax(fabs(c[0]), fabs(c[1])), fmax(fabs(c[2]), fabs(c[3]))), fabs(c[4]));
   const double bound = 1.0 + big / fabs(top);  // Cauchy's: no root lies beyond
+  const auto eval = [&](double x) { return evalPoly(c, x); };
+  const auto derivative = [&](double x) { return evalDerivative(c, x); };
   double lo = 0.0, flo = c[0];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -118,14 +63,14 @@ __device__ __forceinline__ void positiveRoots(const double (&c)[5], const double
       if (fhi == 0.0) {
         root[k] = hi;
       } else if (flo != 0.0 && (flo > 0.0) != (fhi > 0.0)) {
-        root[k] = bracketedRoot(c, lo, hi, flo);
+        root[k] = bracketedRoot<true>(eval, derivative, lo, hi, flo);
       }
       lo = hi;
       flo = fhi;
     }
   }
   root[K] = NAN;
-  if (top != 0.0 && bound < DBL_MAX && flo != 0.0 && (flo > 0.0) != (top > 0.0)) root[K] = bracketedRoot(c, lo, bound, flo);
+  if (top != 0.0 && bound < DBL_MAX && flo != 0.0 && (flo > 0.0) != (top > 0.0)) root[K] = bracketedRoot<true>(eval, derivative, lo, bound, flo);
 }
 
 /** the positive real roots of the quartic c, ascending in the filled slots */
@@ -259,36 +204,7 @@ __device__ __forceinline__ bool isInlier(const double *T, const double *__restri
   return angularDistance(T, Xj, f) < p.t_ang;
 }
 
-template <typename T>
-__device__ __forceinline__ T freshLoad(const T *ptr) {
-  return __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- the closing workgroup's tools
-
-/** every thread's v[k] becomes the sum over the workgroup, in one fixed order: a butterfly over the wave (both partners add the same two
- *  numbers), then the waves' sums in wave order.  s_sum: kWavesPerBlock x K doubles */
-template <int K>
-__device__ __forceinline__ void blockSum(double (&v)[K], double *s_sum, int lane, int wave) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_sum[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double total = s_sum[k];
-#pragma unroll
-    for (int w = 1; w < kWavesPerBlock; ++w) total += s_sum[w * K + k];
-    v[k] = total;
-  }
-  __syncthreads();  // (s_sum is written again)
-}
+// ---- the refinement: what refinePose (ransac_device.hpp) minimises
 
 /** the pixel residual of point j at pose T: false when the point does not count (p_z < 0.001) */
 __device__ __forceinline__ bool pixelResidual(const double *T, const double *__restrict__ X, const double *__restrict__ obs, int j, const PnpParams &p,
@@ -303,122 +219,76 @@ __device__ __forceinline__ bool pixelResidual(const double *T, const double *__r
   return true;
 }
 
-/** sum |r|^2 and the number of counting points over the inliers of `Tsel`, at pose T: (cost, count) on every thread */
-__device__ __forceinline__ void blockCost(const double *T, const double *Tsel, const double *__restrict__ X, const double *__restrict__ obs,
-                                          const PnpParams &p, double *s_sum, int tid, double &cost, double &count) {
-  double v[2] = {0.0, 0.0};
-  for (int j = tid; j < p.n; j += kBlock) {
-    if (!isInlier(Tsel, X, obs, j, p)) continue;
-    double Xj[3], pc[3], r[2];
-    if (!pixelResidual(T, X, obs, j, p, Xj, pc, r)) continue;
-    v[0] += r[0] * r[0] + r[1] * r[1];
-    v[1] += 1.0;
-  }
-  blockSum<2>(v, s_sum, tid & 63, tid >> 6);
-  cost = 0.5 * v[0];
-  count = v[1];
-}
+/** the reprojection error over the six degrees of freedom of the pose; s_sum: kWavesPerBlock x 27 doubles */
+struct PnpRefinement {
+  static constexpr int kUnknowns = 6;
+  const double *X, *obs;
+  const PnpParams &p;
+  double *s_sum;
+  int tid;
 
-/** H (upper triangle, row by row: 21) and b (6) over the inliers of `Tsel`, at pose T */
-__device__ __forceinline__ void blockLinearise(const double *T, const double *Tsel, const double *__restrict__ X, const double *__restrict__ obs,
-                                               const PnpParams &p, double *s_sum, int tid, double (&Hb)[27]) {
-#pragma unroll
-  for (int k = 0; k < 27; ++k) Hb[k] = 0.0;
-  for (int j = tid; j < p.n; j += kBlock) {
-    if (!isInlier(Tsel, X, obs, j, p)) continue;
-    double Xj[3], pc[3], r[2];
-    if (!pixelResidual(T, X, obs, j, p, Xj, pc, r)) continue;
-    const double z = pc[2];
-    const double g00 = p.fx / z, g02 = -p.fx * pc[0] / (z * z), g11 = p.fy / z, g12 = -p.fy * pc[1] / (z * z);
-    double J[2][6];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      J[0][c] = -(g00 * T[c] + g02 * T[6 + c]);
-      J[1][c] = -(g11 * T[3 + c] + g12 * T[6 + c]);
+  /** sum |r|^2 and the number of counting points over the inliers of `Tsel`, at pose T: (cost, count) on every thread */
+  __device__ __forceinline__ void cost(const double *T, const double *Tsel, double &value, double &count) const {
+    double v[2] = {0.0, 0.0};
+    for (int j = tid; j < p.n; j += kBlock) {
+      if (!isInlier(Tsel, X, obs, j, p)) continue;
+      double Xj[3], pc[3], r[2];
+      if (!pixelResidual(T, X, obs, j, p, Xj, pc, r)) continue;
+      v[0] += r[0] * r[0] + r[1] * r[1];
+      v[1] += 1.0;
     }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      J[k][3] = J[k][2] * Xj[1] - J[k][1] * Xj[2];
-      J[k][4] = J[k][0] * Xj[2] - J[k][2] * Xj[0];
-      J[k][5] = J[k][1] * Xj[0] - J[k][0] * Xj[1];
-    }
-    int at = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int b = a; b < 6; ++b) Hb[at++] += J[0][a] * J[0][b] + J[1][a] * J[1][b];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) Hb[21 + a] += J[0][a] * r[0] + J[1][a] * r[1];
+    blockSum<2>(v, s_sum, tid & 63, tid >> 6);
+    value = 0.5 * v[0];
+    count = v[1];
   }
-  blockSum<27>(Hb, s_sum, tid & 63, tid >> 6);
-}
 
-/** (H + lambda diag H) delta = -b by an unblocked right-looking Cholesky; false when a pivot is <= 0 or not finite */
-__device__ __forceinline__ bool dampedSolve(const double (&Hb)[27], double lambda, double (&delta)[6]) {
-  double L[6][6];
-  int at = 0;
+  /** H (upper triangle, row by row: 21) and b (6) over the inliers of `Tsel`, at pose T */
+  __device__ __forceinline__ void linearise(const double *T, const double *Tsel, double (&Hb)[27]) const {
 #pragma unroll
-  for (int a = 0; a < 6; ++a)
+    for (int k = 0; k < 27; ++k) Hb[k] = 0.0;
+    for (int j = tid; j < p.n; j += kBlock) {
+      if (!isInlier(Tsel, X, obs, j, p)) continue;
+      double Xj[3], pc[3], r[2];
+      if (!pixelResidual(T, X, obs, j, p, Xj, pc, r)) continue;
+      const double z = pc[2];
+      const double g00 = p.fx / z, g02 = -p.fx * pc[0] / (z * z), g11 = p.fy / z, g12 = -p.fy * pc[1] / (z * z);
+      double J[2][6];
 #pragma unroll
-    for (int b = a; b < 6; ++b) {
-      const double h = Hb[at++];
-      L[b][a] = a == b ? h + lambda * h : h;
+      for (int c = 0; c < 3; ++c) {
+        J[0][c] = -(g00 * T[c] + g02 * T[6 + c]);
+        J[1][c] = -(g11 * T[3 + c] + g12 * T[6 + c]);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        J[k][3] = J[k][2] * Xj[1] - J[k][1] * Xj[2];
+        J[k][4] = J[k][0] * Xj[2] - J[k][2] * Xj[0];
+        J[k][5] = J[k][1] * Xj[0] - J[k][0] * Xj[1];
+      }
+      int at = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) Hb[at++] += J[0][a] * J[0][b] + J[1][a] * J[1][b];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) Hb[21 + a] += J[0][a] * r[0] + J[1][a] * r[1];
     }
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const double d = L[k][k];
-    ok = ok && d > 0.0 && d <= DBL_MAX;
-    const double root = sqrt(d);
-    L[k][k] = root;
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) L[i][k] /= root;
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i)
-#pragma unroll
-      for (int j = k + 1; j <= i; ++j) L[i][j] -= L[i][k] * L[j][k];
+    blockSum<27>(Hb, s_sum, tid & 63, tid >> 6);
   }
-  if (!ok) return false;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) delta[k] = -Hb[21 + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    delta[k] /= L[k][k];
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) delta[i] -= L[i][k] * delta[k];
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; --k) {
-    delta[k] /= L[k][k];
-#pragma unroll
-    for (int i = 0; i < k; ++i) delta[i] -= L[k][i] * delta[k];
-  }
-  return true;
-}
 
-/** the inliers of pose T in ascending order: 256 points per step, a wave's ballot places its lanes, the waves' counts place the waves */
-__device__ __forceinline__ int listInliers(const double *T, const double *__restrict__ X, const double *__restrict__ obs, const PnpParams &p,
-                                           int *s_wave_count, int tid, int *__restrict__ inliers) {
-  const int lane = tid & 63, wave = tid >> 6;
-  int total = 0;
-  for (int base = 0; base < p.n; base += kBlock) {
-    const int j = base + tid;
-    const bool in = j < p.n && isInlier(T, X, obs, j, p);
-    const unsigned long long mask = __ballot(in);
-    if (lane == 0) s_wave_count[wave] = __builtin_popcountll(mask);
-    __syncthreads();
-    int offset = total, step = 0;
+  /** T Exp(delta) */
+  __device__ __forceinline__ void retract(const double *T, const double (&delta)[6], double *C) const {
+    Rigid current;
 #pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) {
-      if (w < wave) offset += s_wave_count[w];
-      step += s_wave_count[w];
-    }
-    if (in) inliers[offset + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = j;
-    total += step;
-    __syncthreads();  // (s_wave_count is written again)
+    for (int e = 0; e < 9; ++e) current.R[e] = T[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) current.t[e] = T[9 + e];
+    const Rigid candidate = rigidMul(current, rigidExp(delta));
+#pragma unroll
+    for (int e = 0; e < 9; ++e) C[e] = candidate.R[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) C[9 + e] = candidate.t[e];
   }
-  return total;
-}
+};
 
 __global__ void __launch_bounds__(kBlock) pnpRansacKernel(const double *__restrict__ X, const double *__restrict__ obs, const int *__restrict__ samples,
                                                           unsigned *ticket, int *hyp_num_solutions, double *hyp_poses, int *hyp_counts,
@@ -478,56 +348,9 @@ __global__ void __launch_bounds__(kBlock) pnpRansacKernel(const double *__restri
       }
     }
   }
-  // the hand-off: the stores above have left every wave, then one release at device scope, then the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = drawn == gridDim.x - 1 ? 1u : 0u;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lastWorkgroup(ticket, s_last)) return;
 
-  // the selection, by wave 0: the greatest count, the lowest hypothesis among equals, the lowest solution among that one's
-  if (wave == 0) {
-    int best = 0, best_i = INT_MAX;
-    for (int i = lane; i < p.iterations; i += 64) {
-      int c = 0;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int cs = freshLoad(hyp_counts + 4 * static_cast<size_t>(i) + s);
-        c = cs > c ? cs : c;
-      }
-      if (c > best) {
-        best = c;
-        best_i = i;
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int c = __shfl_xor(best, o, 64), i = __shfl_xor(best_i, o, 64);
-      if (c > best || (c == best && i < best_i)) {
-        best = c;
-        best_i = i;
-      }
-    }
-    if (lane == 0) {
-      int solution = -1;
-      if (best > 0) {
-        for (int s = 3; s >= 0; --s)
-          if (freshLoad(hyp_counts + 4 * static_cast<size_t>(best_i) + s) == best) solution = s;
-      }
-      s_best_iteration = best > 0 ? best_i : -1;
-      s_best_solution = solution;
-      s_best_count = best;
-    }
-  }
+  if (wave == 0) selectBest<4>(hyp_counts, p.iterations, lane, s_best_iteration, s_best_solution, s_best_count);
   __syncthreads();
   const int best_iteration = s_best_iteration, best_solution = s_best_solution;
   double T0[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, T[12];
@@ -540,56 +363,8 @@ __global__ void __launch_bounds__(kBlock) pnpRansacKernel(const double *__restri
   int iterations = 0, flags = 0, total = 0;
   double cost_initial = 0.0, cost = 0.0;
   if (best_iteration >= 0) {
-    // the LM driver of the geometric BA over the one pose; every thread takes every decision from the same sums
-    double counting, lambda = p.lambda_0;
-    blockCost(T, T0, X, obs, p, s_sum, tid, cost, counting);
-    cost_initial = cost;
-    if (counting == 0.0) flags = DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL;
-    bool linearise = true;
-    double Hb[27];
-    while (iterations < p.max_iterations && flags == 0) {
-      if (linearise) blockLinearise(T, T0, X, obs, p, s_sum, tid, Hb);
-      linearise = false;
-      double delta[6];
-      ++iterations;
-      if (!dampedSolve(Hb, lambda, delta)) {
-        lambda *= p.increase_factor;
-        continue;
-      }
-      Rigid current, candidate;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) current.R[e] = T[e];
-#pragma unroll
-      for (int e = 0; e < 3; ++e) current.t[e] = T[9 + e];
-      candidate = rigidMul(current, rigidExp(delta));
-      double C[12], candidate_cost, candidate_counting;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) C[e] = candidate.R[e];
-#pragma unroll
-      for (int e = 0; e < 3; ++e) C[9 + e] = candidate.t[e];
-      blockCost(C, T0, X, obs, p, s_sum, tid, candidate_cost, candidate_counting);
-      if (candidate_counting == 0.0) {
-        flags = DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL;
-        break;
-      }
-      int reason = fabs(cost - candidate_cost) / cost < p.function_tolerance ? DSOPP_HIP_GEOMETRIC_BA_FUNCTION_TOLERANCE : 0;
-      if (candidate_cost < cost) {
-        double step = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) step += delta[k] * delta[k];
-        const double state = T[9] * T[9] + T[10] * T[10] + T[11] * T[11] + 1.0;
-        if (step < p.parameter_tolerance * (state + p.parameter_tolerance)) reason |= DSOPP_HIP_GEOMETRIC_BA_PARAMETER_TOLERANCE;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[e] = C[e];
-        cost = candidate_cost;
-        linearise = true;
-        lambda /= p.decrease_factor;
-      } else {
-        lambda *= p.increase_factor;
-      }
-      flags = reason;
-    }
-    total = listInliers(T, X, obs, p, s_wave_count, tid, inliers);
+    refinePose(PnpRefinement{X, obs, p, s_sum, tid}, T, T0, iterations, flags, cost_initial, cost);
+    total = listInliers(p.n, [&](int j) { return isInlier(T, X, obs, j, p); }, s_wave_count, tid, inliers);
   }
   if (tid == 0) {
     result->matches = 0;  // (the host counts them)
@@ -613,14 +388,7 @@ __global__ void __launch_bounds__(kBlock) pnpRansacKernel(const double *__restri
 }  // namespace
 }  // namespace dsopp_hip
 
-struct dsopp_hip_pnp_ransac {
-  dsopp_hip::StreamRef sr;
-  dsopp_hip::Event done;
-  // the inputs and the results of an estimate(): one device block and one pinned mirror each, laid out by PnpLayout; they grow geometrically
-  dsopp_hip::DeviceMem<uint8_t> d_in, d_out;
-  dsopp_hip::PinnedMem<uint8_t> h_in, h_out;
-  size_t in_capacity = 0, out_capacity = 0;
-};
+struct dsopp_hip_pnp_ransac : dsopp_hip::StagedCall {};
 
 namespace dsopp_hip {
 namespace {
@@ -644,14 +412,6 @@ struct PnpLayout {
     out_bytes = solutions + 4 * iterations;
   }
 };
-
-size_t grown(size_t capacity, size_t need) {
-  size_t cap = capacity ? capacity : 4096;
-  while (cap < need) cap *= 2;
-  return cap;
-}
-
-bool finite(double v) { return std::fabs(v) <= DBL_MAX; }
 
 void defaultOptions(dsopp_hip_pnp_ransac_options *o) {
   o->lambda_0 = 1e-4;
@@ -691,13 +451,7 @@ void estimate(dsopp_hip_pnp_ransac *h, double fx, double fy, double cx, double c
   }
   if (n > 0 && iterations > 0) {
     if (n < 3) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d points: a triple of distinct indices needs 3", n);
-    if (!samples) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    for (int i = 0; i < iterations; ++i) {
-      const int32_t *s = samples + 3 * static_cast<size_t>(i);
-      for (int k = 0; k < 3; ++k)
-        if (s[k] < 0 || s[k] >= n) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d holds index %d of %d points", i, s[k], n);
-      if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d repeats an index", i);
-    }
+    checkSamples<3, true>(samples, iterations, n, "points");
   }
   std::memset(result, 0, sizeof(*result));
   result->matches = matches;
@@ -708,20 +462,7 @@ void estimate(dsopp_hip_pnp_ransac *h, double fx, double fy, double cx, double c
   h->sr.use();
   const hipStream_t st = h->sr.stream;
   const PnpLayout lay(count, hyps);
-  if (h->in_capacity < lay.in_bytes) {
-    const size_t cap = grown(h->in_capacity, lay.in_bytes);
-    h->in_capacity = 0;
-    h->d_in.alloc(cap);
-    h->h_in.reserve(cap);
-    h->in_capacity = cap;
-  }
-  if (h->out_capacity < lay.out_bytes) {
-    const size_t cap = grown(h->out_capacity, lay.out_bytes);
-    h->out_capacity = 0;
-    h->d_out.alloc(cap);
-    h->h_out.reserve(cap);
-    h->out_capacity = cap;
-  }
+  h->ensure(lay.in_bytes, lay.out_bytes);
   uint8_t *hi = h->h_in.get(), *di = h->d_in.get(), *ho = h->h_out.get(), *dout = h->d_out.get();
   std::memset(hi, 0, 16);  // (the ticket is armed by the upload)
   std::memcpy(hi + lay.x, positions, 24 * count);
@@ -778,21 +519,9 @@ void dsopp_hip_pnp_ransac_default_options(dsopp_hip_pnp_ransac_options *options)
   if (options) defaultOptions(options);
 }
 
-int dsopp_hip_pnp_ransac_create(int device, void *stream, dsopp_hip_pnp_ransac **out) {
-  return guarded([&] {
-    if (!out) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    auto r = std::make_unique<dsopp_hip_pnp_ransac>();
-    r->sr.init(device, stream);
-    *out = r.release();
-  });
-}
+int dsopp_hip_pnp_ransac_create(int device, void *stream, dsopp_hip_pnp_ransac **out) { return createHandle(device, stream, out); }
 
-void dsopp_hip_pnp_ransac_destroy(dsopp_hip_pnp_ransac *r) {
-  if (!r) return;
-  (void)hipSetDevice(r->sr.device);
-  if (r->sr.stream) (void)hipStreamSynchronize(r->sr.stream);
-  delete r;
-}
+void dsopp_hip_pnp_ransac_destroy(dsopp_hip_pnp_ransac *r) { destroyHandle(r); }
 
 int dsopp_hip_pnp_ransac_estimate(dsopp_hip_pnp_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
                                   const double *positions, const double *observations, int iterations, const int32_t *samples, double threshold_px,

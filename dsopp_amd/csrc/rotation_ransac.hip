@@ -12,37 +12,28 @@
 // ballot and population count.  The points are read straight through the vector cache: the waves of a workgroup walk the same 32 n bytes
 // side by side.  A wave whose triple is invalid looks for its nearest valid predecessor itself (the triples' validity is six comparisons
 // each) and solves and scores that one, or the identity: no wave reads what another wave wrote.
-//   The workgroup that takes the last ticket of a counter closes the call: the selection walk over the counts (a prefix maximum over the
-// wave), then the winner's inlier list in ascending order (ballots again).  A ticket only: no workgroup waits for another.
-//   Hand-off to that workgroup: plain stores, every wave's vmcnt(0), a barrier, one lane's agent-scope release, the ticket; behind the
-// ticket one agent-scope acquire, a barrier, and loads that bypass the vector cache.
+//   The workgroup that takes the last ticket of a counter closes the call (lastWorkgroup, ransac_device.hpp): the selection walk over the
+// counts (a prefix maximum over the wave), then the winner's inlier list in ascending order (ballots again).
 //
 // The polar factor: a one-sided (Hestenes) Jacobi SVD of H — rotations of column pairs of G = H V until the columns are orthogonal to
 // rounding, G = U S — which is backward stable and needs no inverse, so a singular H is no special case up to here.  U is then rebuilt as
 // an orthonormal frame: u0 from the longest column, u1 from the second, re-orthogonalised, u2 = +-(u0 x u1) with the sign of the shortest
 // column.  For a well-conditioned H that changes U by rounding; for a vanishing smallest singular value it still yields a rotation.
-#include "common.hpp"
-
-#include <cfloat>
-#include <climits>
-#include <cmath>
-#include <memory>
+#include "ransac_device.hpp"
+#include "staged_call.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dsopp_hip {
 namespace {
+using namespace ransac;
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kMaxSweeps = 30;  // a 3 x 3 one-sided Jacobi converges in 4 .. 7 sweeps; the cap only bounds the loop for NaN input
 
-struct RansacParams {
-  double fx, fy, cx, cy, xmax, ymax, threshold, tolerance;
+struct RansacParams : PinholeRoi {
+  double threshold, tolerance;
   int n, iterations;
 };
-
-__device__ __forceinline__ bool insideRoi(double x, double y, const RansacParams &p) { return x >= 4.0 && x <= p.xmax && y >= 4.0 && y <= p.ymax; }
 
 /** all six points of triple i inside the ROI */
 __device__ __forceinline__ bool sampleValid(const double *__restrict__ A, const double *__restrict__ B, const int *__restrict__ samples, int i,
@@ -56,8 +47,6 @@ __device__ __forceinline__ bool sampleValid(const double *__restrict__ A, const 
   }
   return ok;
 }
-
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 __device__ __forceinline__ void swapColumns(double *ga, double *gb, double *va, double *vb, double &na, double &nb) {
   if (na < nb) {
@@ -191,11 +180,6 @@ __device__ __forceinline__ bool isInlier(const double *R, double ax, double ay, 
   return sqrt(dx * dx + dy * dy) < p.threshold;  // (false for a NaN)
 }
 
-template <typename T>
-__device__ __forceinline__ T freshLoad(const T *ptr) {
-  return __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ void __launch_bounds__(kBlock) rotationRansacKernel(const double *__restrict__ A, const double *__restrict__ B, const int *__restrict__ samples,
                                                                unsigned *ticket, int *hyp_counts, double *hyp_rotations, uint8_t *hyp_valid,
                                                                dsopp_hip_rotation_ransac_result *result, int *__restrict__ inliers,
@@ -233,21 +217,7 @@ __global__ void __launch_bounds__(kBlock) rotationRansacKernel(const double *__r
       for (int k = 0; k < 9; ++k) hyp_rotations[9 * static_cast<size_t>(hyp) + k] = R[k];
     }
   }
-  // the hand-off: the stores above have left every wave, then one release at device scope, then the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = drawn == gridDim.x - 1 ? 1u : 0u;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lastWorkgroup(ticket, s_last)) return;
 
   // the selection walk, by wave 0: before[i] = the greatest count ahead of i; the walk stops before the first i with before[i] / n >= tolerance
   if (wave == 0) {
@@ -295,24 +265,10 @@ __global__ void __launch_bounds__(kBlock) rotationRansacKernel(const double *__r
   if (best_iteration >= 0) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = freshLoad(hyp_rotations + 9 * static_cast<size_t>(best_iteration) + k);
-    // the winner's inliers in ascending order: 256 points per step, a wave's ballot places its lanes, the waves' counts place the waves
-    for (int base = 0; base < p.n; base += kBlock) {
-      const int j = base + tid;
-      bool in = false;
-      if (j < p.n) in = isInlier(R, A[2 * static_cast<size_t>(j)], A[2 * static_cast<size_t>(j) + 1], B[2 * static_cast<size_t>(j)], B[2 * static_cast<size_t>(j) + 1], p);
-      const unsigned long long mask = __ballot(in);
-      if (lane == 0) s_wave_count[wave] = __builtin_popcountll(mask);
-      __syncthreads();
-      int offset = total, step = 0;
-#pragma unroll
-      for (int w = 0; w < kWavesPerBlock; ++w) {
-        if (w < wave) offset += s_wave_count[w];
-        step += s_wave_count[w];
-      }
-      if (in) inliers[offset + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = j;
-      total += step;
-      __syncthreads();  // (s_wave_count is written again)
-    }
+    const auto inlier = [&](int j) {
+      return isInlier(R, A[2 * static_cast<size_t>(j)], A[2 * static_cast<size_t>(j) + 1], B[2 * static_cast<size_t>(j)], B[2 * static_cast<size_t>(j) + 1], p);
+    };
+    total = listInliers(p.n, inlier, s_wave_count, tid, inliers);
   }
   if (tid == 0) {
     result->iterations_run = s_run;
@@ -327,14 +283,7 @@ __global__ void __launch_bounds__(kBlock) rotationRansacKernel(const double *__r
 }  // namespace
 }  // namespace dsopp_hip
 
-struct dsopp_hip_rotation_ransac {
-  dsopp_hip::StreamRef sr;
-  dsopp_hip::Event done;
-  // the inputs and the results of an estimate(): one device block and one pinned mirror each, laid out by RansacLayout; they grow geometrically
-  dsopp_hip::DeviceMem<uint8_t> d_in, d_out;
-  dsopp_hip::PinnedMem<uint8_t> h_in, h_out;
-  size_t in_capacity = 0, out_capacity = 0;
-};
+struct dsopp_hip_rotation_ransac : dsopp_hip::StagedCall {};
 
 namespace dsopp_hip {
 namespace {
@@ -357,12 +306,6 @@ struct RansacLayout {
   }
 };
 
-size_t grown(size_t capacity, size_t need) {
-  size_t cap = capacity ? capacity : 4096;
-  while (cap < need) cap *= 2;
-  return cap;
-}
-
 void estimate(dsopp_hip_rotation_ransac *h, double fx, double fy, double cx, double cy, int width, int height, int n, const double *points_a,
               const double *points_b, int iterations, const int32_t *samples, double threshold, double inliers_tolerance,
               dsopp_hip_rotation_ransac_result *result, int32_t *inlier_indices, int32_t *hyp_counts, double *hyp_rotations, uint8_t *hyp_valid) {
@@ -380,31 +323,12 @@ void estimate(dsopp_hip_rotation_ransac *h, double fx, double fy, double cx, dou
   // n = 0: 0 / 0 < tolerance is false and the reference's loop runs no iteration, whatever the triples are
   if (n == 0 || iterations == 0) return;
   if (n < 3) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d points: a triple of distinct indices needs 3", n);
-  if (!samples) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  for (int i = 0; i < iterations; ++i) {
-    const int32_t *s = samples + 3 * static_cast<size_t>(i);
-    for (int k = 0; k < 3; ++k)
-      if (s[k] < 0 || s[k] >= n) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d holds index %d of %d points", i, s[k], n);
-    if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d repeats an index", i);
-  }
+  checkSamples<3, true>(samples, iterations, n, "points");
   h->sr.use();
   const hipStream_t st = h->sr.stream;
   const size_t count = static_cast<size_t>(n), hyps = static_cast<size_t>(iterations);
   const RansacLayout lay(count, hyps);
-  if (h->in_capacity < lay.in_bytes) {
-    const size_t cap = grown(h->in_capacity, lay.in_bytes);
-    h->in_capacity = 0;
-    h->d_in.alloc(cap);
-    h->h_in.reserve(cap);
-    h->in_capacity = cap;
-  }
-  if (h->out_capacity < lay.out_bytes) {
-    const size_t cap = grown(h->out_capacity, lay.out_bytes);
-    h->out_capacity = 0;
-    h->d_out.alloc(cap);
-    h->h_out.reserve(cap);
-    h->out_capacity = cap;
-  }
+  h->ensure(lay.in_bytes, lay.out_bytes);
   uint8_t *hi = h->h_in.get(), *di = h->d_in.get(), *ho = h->h_out.get(), *dout = h->d_out.get();
   std::memset(hi, 0, 16);  // (the ticket is armed by the upload)
   std::memcpy(hi + lay.a, points_a, 16 * count);
@@ -447,21 +371,9 @@ using namespace dsopp_hip;
 
 extern "C" {
 
-int dsopp_hip_rotation_ransac_create(int device, void *stream, dsopp_hip_rotation_ransac **out) {
-  return guarded([&] {
-    if (!out) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    auto r = std::make_unique<dsopp_hip_rotation_ransac>();
-    r->sr.init(device, stream);
-    *out = r.release();
-  });
-}
+int dsopp_hip_rotation_ransac_create(int device, void *stream, dsopp_hip_rotation_ransac **out) { return createHandle(device, stream, out); }
 
-void dsopp_hip_rotation_ransac_destroy(dsopp_hip_rotation_ransac *r) {
-  if (!r) return;
-  (void)hipSetDevice(r->sr.device);
-  if (r->sr.stream) (void)hipStreamSynchronize(r->sr.stream);
-  delete r;
-}
+void dsopp_hip_rotation_ransac_destroy(dsopp_hip_rotation_ransac *r) { destroyHandle(r); }
 
 int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
                                        const double *points_a, const double *points_b, int iterations, const int32_t *samples, double threshold,

@@ -20,37 +20,30 @@
 //   the hidden-variable form                  det B(z), a lane per coefficient: a polynomial of degree 10 in z;
 //   its real roots                            bracketed through the chain of its derivatives, from the linear one upwards: at every level
 //                                             lane b owns the interval between the critical points b - 1 and b and runs the safeguarded
-//                                             Newton iteration of pnp_ransac.hip in it; a ballot compacts the roots for the next level;
+//                                             Newton iteration (bracketedRoot) in it; a ballot compacts the roots for the next level;
 //   per root, one lane                        (x, y) from the null vector of B(z), Gauss-Newton on the ten cubics until the point stops
 //                                             moving, the pose of E in closed form (R = Cof(E) -+ hat(t) E, t the unit normal of E's
 //                                             columns), the four candidates tried against the five pairs.
 // The poses are ranked by their trace into LDS slots and read from there with a uniform index; the lanes then stride over the points and
 // the wave counts by ballot.  Nothing is indexed dynamically in registers.
-//   The workgroup that takes the last ticket closes the call as in pnp_ransac.hip (the same hand-off): selection, the refinement over the
-// winner's inliers, the re-selection, the refinement over its inliers, the ascending inlier list.  Sums are thread-strided partials, a
-// butterfly over the wave, the four waves added in wave order: the same input gives the same bits.
-#include "common.hpp"
+//   The workgroup that takes the last ticket closes the call with the tools of ransac_device.hpp, as pnp_ransac.hip does: selection, the
+// refinement over the winner's inliers, the re-selection, the refinement over its inliers, the ascending inlier list.
+#include "ransac_device.hpp"
 #include "se3_math.hpp"
-
-#include <cfloat>
-#include <climits>
-#include <cmath>
-#include <memory>
+#include "staged_call.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dsopp_hip {
 namespace {
+using namespace ransac;
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kMaxSolutions = 10;
-constexpr int kMaxRootSteps = 200;  // a bracket of doubles is exhausted by ~64 bisections (geometric ones across magnitudes); the cap only bounds the loop
 constexpr int kPolishSteps = 12;
 constexpr double kConstraintTolerance = 1e-9;
 
-struct TwoViewParams {
-  double fx, fy, cx, cy, xmax, ymax, t_ang;
+struct TwoViewParams : PinholeRoi {
+  double t_ang;
   double a, lambda_0, function_tolerance, parameter_tolerance, decrease_factor, increase_factor;
   int n, iterations, max_iterations;
 };
@@ -77,27 +70,6 @@ __device__ __forceinline__ void waveSync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-__device__ __forceinline__ bool insideRoi(double x, double y, const TwoViewParams &p) { return x >= 4.0 && x <= p.xmax && y >= 4.0 && y <= p.ymax; }
-
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-/** f = normalize(unproject(x, y)) */
-__device__ __forceinline__ void bearing(double x, double y, const TwoViewParams &p, double *f) {
-  const double ux = (x - p.cx) / p.fx, uy = (y - p.cy) / p.fy;
-  const double norm = sqrt(ux * ux + uy * uy + 1.0);
-  f[0] = ux / norm;
-  f[1] = uy / norm;
-  f[2] = 1.0 / norm;
-}
-
-__device__ __forceinline__ bool isFinite(double v) { return fabs(v) <= DBL_MAX; }
 
 // ---- the ten constraints
 
@@ -172,42 +144,6 @@ __device__ __forceinline__ double evalLevel(const WaveShared &s, int level, doub
   return v;
 }
 
-__device__ __forceinline__ double middlePositive(double lo, double hi) {
-  if (lo == 0.0) return hi > 2.0 ? 1.0 : 0.5 * hi;
-  if (hi > 4.0 * lo) return sqrt(lo) * sqrt(hi);
-  return 0.5 * (lo + hi);
-}
-
-/** the middle of a bracket lo < hi: zero when it straddles zero, else geometric where the ends differ in magnitude, so that a bracket up
- *  to a polynomial's root bound is exhausted as fast as a narrow one */
-__device__ __forceinline__ double middle(double lo, double hi) {
-  if (lo < 0.0 && hi > 0.0) return 0.0;
-  if (lo >= 0.0) return middlePositive(lo, hi);
-  return -middlePositive(-hi, -lo);
-}
-
-/** the root inside (lo, hi), where the level's polynomial has the sign of flo at lo and the other sign at hi */
-__device__ double bracketedRoot(const WaveShared &s, int level, double lo, double hi, double flo) {
-  double x = middle(lo, hi), last_step = hi - lo;
-  for (int it = 0; it < kMaxRootSteps; ++it) {
-    const double f = evalLevel(s, level, x);
-    if (f == 0.0) return x;
-    if ((f > 0.0) == (flo > 0.0)) {
-      lo = x;
-    } else {
-      hi = x;
-    }
-    const double mid = middle(lo, hi);
-    if (!(mid > lo && mid < hi)) break;  // neighbouring doubles
-    double next = x - f / evalLevel(s, level + 1, x);
-    if (!(next > lo && next < hi) || !(fabs(next - x) <= 0.5 * fabs(last_step))) next = mid;
-    if (next == x) break;
-    last_step = next - x;
-    x = next;
-  }
-  return x;
-}
-
 /** the real roots of det B(z), one per lane (NaN = none), through the chain of derivatives */
 __device__ __forceinline__ double realRoots(WaveShared &s, int lane) {
   int ncrit = 0, cur = 0;
@@ -228,7 +164,7 @@ __device__ __forceinline__ double realRoots(WaveShared &s, int lane) {
         if (fhi == 0.0 && !last) {
           root = hi;  // (a root on a critical point belongs to the bracket below it)
         } else if (flo != 0.0 && fhi != 0.0 && (flo > 0.0) != (fhi > 0.0)) {
-          root = bracketedRoot(s, level, lo, hi, flo);
+          root = bracketedRoot([&](double x) { return evalLevel(s, level, x); }, [&](double x) { return evalLevel(s, level + 1, x); }, lo, hi, flo);
         }
       }
     }
@@ -638,36 +574,7 @@ __device__ __forceinline__ int solveFivePoint(WaveShared &s, int lane) {
   return solutions < kMaxSolutions ? solutions : kMaxSolutions;
 }
 
-template <typename T>
-__device__ __forceinline__ T freshLoad(const T *ptr) {
-  return __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- the closing workgroup's tools
-
-/** every thread's v[k] becomes the sum over the workgroup, in one fixed order: a butterfly over the wave (both partners add the same two
- *  numbers), then the waves' sums in wave order.  s_sum: kWavesPerBlock x K doubles */
-template <int K>
-__device__ __forceinline__ void blockSum(double (&v)[K], double *s_sum, int lane, int wave) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_sum[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double total = s_sum[k];
-#pragma unroll
-    for (int w = 1; w < kWavesPerBlock; ++w) total += s_sum[w * K + k];
-    v[k] = total;
-  }
-  __syncthreads();  // (s_sum is written again)
-}
+// ---- the refinement: what refinePose (ransac_device.hpp) minimises
 
 /** E = hat(t) R */
 __device__ __forceinline__ void essentialOfPose(const double *T, double *E) {
@@ -719,214 +626,111 @@ __device__ __forceinline__ void sampsonTerms(const double *E, const double *__re
 
 __device__ __forceinline__ double sampsonResidual(const SampsonTerms &s) { return s.bottom < 1e-16 ? s.top : s.top / sqrt(s.bottom); }
 
-/** 1/2 sum rho(r^2) and the number of pairs over the inliers of `Tsel`, at pose T: (cost, count) on every thread */
-__device__ __forceinline__ void blockCost(const double *T, const double *Tsel, const double *__restrict__ A, const double *__restrict__ B,
-                                          const TwoViewParams &p, double *s_sum, int tid, double &cost, double &count) {
-  double E[9];
-  essentialOfPose(T, E);
-  double v[2] = {0.0, 0.0};
-  for (int j = tid; j < p.n; j += kBlock) {
-    if (!isInlier(Tsel, A, B, j, p)) continue;
-    SampsonTerms st;
-    sampsonTerms(E, A, B, j, p, st);
-    const double r = sampsonResidual(st), sq = r * r;
-    v[0] += sq > p.a * p.a ? 2.0 * p.a * sqrt(sq) - p.a * p.a : sq;
-    v[1] += 1.0;
-  }
-  blockSum<2>(v, s_sum, tid & 63, tid >> 6);
-  cost = 0.5 * v[0];
-  count = v[1];
-}
+/** the Huber loss of the Sampson error over the five degrees of freedom of (R, t / |t|); s_sum: kWavesPerBlock x 20 doubles */
+struct TwoViewRefinement {
+  static constexpr int kUnknowns = 5;
+  const double *A, *B;
+  const TwoViewParams &p;
+  double *s_sum;
+  int tid;
 
-/** H (upper triangle, row by row: 15) and b (5) over the inliers of `Tsel`, at pose T, with the Huber weights */
-__device__ __forceinline__ void blockLinearise(const double *T, const double *Tsel, const double *__restrict__ A, const double *__restrict__ B,
-                                               const TwoViewParams &p, double *s_sum, int tid, double (&Hb)[20]) {
-  double E[9], dE[5][9], b1[3], b2[3];
-  essentialOfPose(T, E);
-  sphereBasis(T + 9, b1, b2);
-  // dE / d alpha = hat(b1) R, dE / d beta = hat(b2) R, dE / d omega_k = E hat(e_k)
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    dE[0][j] = b1[1] * T[6 + j] - b1[2] * T[3 + j];
-    dE[0][3 + j] = b1[2] * T[j] - b1[0] * T[6 + j];
-    dE[0][6 + j] = b1[0] * T[3 + j] - b1[1] * T[j];
-    dE[1][j] = b2[1] * T[6 + j] - b2[2] * T[3 + j];
-    dE[1][3 + j] = b2[2] * T[j] - b2[0] * T[6 + j];
-    dE[1][6 + j] = b2[0] * T[3 + j] - b2[1] * T[j];
+  /** 1/2 sum rho(r^2) and the number of pairs over the inliers of `Tsel`, at pose T: (cost, count) on every thread */
+  __device__ __forceinline__ void cost(const double *T, const double *Tsel, double &value, double &count) const {
+    double E[9];
+    essentialOfPose(T, E);
+    double v[2] = {0.0, 0.0};
+    for (int j = tid; j < p.n; j += kBlock) {
+      if (!isInlier(Tsel, A, B, j, p)) continue;
+      SampsonTerms st;
+      sampsonTerms(E, A, B, j, p, st);
+      const double r = sampsonResidual(st), sq = r * r;
+      v[0] += sq > p.a * p.a ? 2.0 * p.a * sqrt(sq) - p.a * p.a : sq;
+      v[1] += 1.0;
+    }
+    blockSum<2>(v, s_sum, tid & 63, tid >> 6);
+    value = 0.5 * v[0];
+    count = v[1];
   }
+
+  /** H (upper triangle, row by row: 15) and b (5) over the inliers of `Tsel`, at pose T, with the Huber weights */
+  __device__ __forceinline__ void linearise(const double *T, const double *Tsel, double (&Hb)[20]) const {
+    double E[9], dE[5][9], b1[3], b2[3];
+    essentialOfPose(T, E);
+    sphereBasis(T + 9, b1, b2);
+    // dE / d alpha = hat(b1) R, dE / d beta = hat(b2) R, dE / d omega_k = E hat(e_k)
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    // E hat(e_0) = (0, E_i2, -E_i1), E hat(e_1) = (-E_i2, 0, E_i0), E hat(e_2) = (E_i1, -E_i0, 0), row i
-    dE[2][3 * i] = 0.0;
-    dE[2][3 * i + 1] = E[3 * i + 2];
-    dE[2][3 * i + 2] = -E[3 * i + 1];
-    dE[3][3 * i] = -E[3 * i + 2];
-    dE[3][3 * i + 1] = 0.0;
-    dE[3][3 * i + 2] = E[3 * i];
-    dE[4][3 * i] = E[3 * i + 1];
-    dE[4][3 * i + 1] = -E[3 * i];
-    dE[4][3 * i + 2] = 0.0;
-  }
+    for (int j = 0; j < 3; ++j) {
+      dE[0][j] = b1[1] * T[6 + j] - b1[2] * T[3 + j];
+      dE[0][3 + j] = b1[2] * T[j] - b1[0] * T[6 + j];
+      dE[0][6 + j] = b1[0] * T[3 + j] - b1[1] * T[j];
+      dE[1][j] = b2[1] * T[6 + j] - b2[2] * T[3 + j];
+      dE[1][3 + j] = b2[2] * T[j] - b2[0] * T[6 + j];
+      dE[1][6 + j] = b2[0] * T[3 + j] - b2[1] * T[j];
+    }
 #pragma unroll
-  for (int k = 0; k < 20; ++k) Hb[k] = 0.0;
-  for (int j = tid; j < p.n; j += kBlock) {
-    if (!isInlier(Tsel, A, B, j, p)) continue;
-    SampsonTerms st;
-    sampsonTerms(E, A, B, j, p, st);
-    const bool small = st.bottom < 1e-16;
-    const double r = sampsonResidual(st), sq = r * r;
-    const double w = sq > p.a * p.a ? p.a / sqrt(sq) : 1.0;
-    const double root = sqrt(small ? 1.0 : st.bottom), safe = small ? 1.0 : st.bottom;
-    double J[5];
+    for (int i = 0; i < 3; ++i) {
+      // E hat(e_0) = (0, E_i2, -E_i1), E hat(e_1) = (-E_i2, 0, E_i0), E hat(e_2) = (E_i1, -E_i0, 0), row i
+      dE[2][3 * i] = 0.0;
+      dE[2][3 * i + 1] = E[3 * i + 2];
+      dE[2][3 * i + 2] = -E[3 * i + 1];
+      dE[3][3 * i] = -E[3 * i + 2];
+      dE[3][3 * i + 1] = 0.0;
+      dE[3][3 * i + 2] = E[3 * i];
+      dE[4][3 * i] = E[3 * i + 1];
+      dE[4][3 * i + 1] = -E[3 * i];
+      dE[4][3 * i + 2] = 0.0;
+    }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      double du[3], dv[3];
+    for (int k = 0; k < 20; ++k) Hb[k] = 0.0;
+    for (int j = tid; j < p.n; j += kBlock) {
+      if (!isInlier(Tsel, A, B, j, p)) continue;
+      SampsonTerms st;
+      sampsonTerms(E, A, B, j, p, st);
+      const bool small = st.bottom < 1e-16;
+      const double r = sampsonResidual(st), sq = r * r;
+      const double w = sq > p.a * p.a ? p.a / sqrt(sq) : 1.0;
+      const double root = sqrt(small ? 1.0 : st.bottom), safe = small ? 1.0 : st.bottom;
+      double J[5];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        du[i] = dE[k][3 * i] * st.xb[0] + dE[k][3 * i + 1] * st.xb[1] + dE[k][3 * i + 2] * st.xb[2];
-        dv[i] = dE[k][i] * st.xa[0] + dE[k][3 + i] * st.xa[1] + dE[k][6 + i] * st.xa[2];
+      for (int k = 0; k < 5; ++k) {
+        double du[3], dv[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          du[i] = dE[k][3 * i] * st.xb[0] + dE[k][3 * i + 1] * st.xb[1] + dE[k][3 * i + 2] * st.xb[2];
+          dv[i] = dE[k][i] * st.xa[0] + dE[k][3 + i] * st.xa[1] + dE[k][6 + i] * st.xa[2];
+        }
+        const double dtop = st.xa[0] * du[0] + st.xa[1] * du[1] + st.xa[2] * du[2];
+        const double dbottom = 2.0 * (st.u[0] * du[0] + st.u[1] * du[1] + st.v[0] * dv[0] + st.v[1] * dv[1]) / (p.fx * p.fx);
+        J[k] = small ? dtop : dtop / root - 0.5 * st.top * dbottom / (safe * root);
       }
-      const double dtop = st.xa[0] * du[0] + st.xa[1] * du[1] + st.xa[2] * du[2];
-      const double dbottom = 2.0 * (st.u[0] * du[0] + st.u[1] * du[1] + st.v[0] * dv[0] + st.v[1] * dv[1]) / (p.fx * p.fx);
-      J[k] = small ? dtop : dtop / root - 0.5 * st.top * dbottom / (safe * root);
+      int at = 0;
+#pragma unroll
+      for (int a = 0; a < 5; ++a)
+#pragma unroll
+        for (int b = a; b < 5; ++b) Hb[at++] += w * J[a] * J[b];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) Hb[15 + a] += w * J[a] * r;
     }
-    int at = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-      for (int b = a; b < 5; ++b) Hb[at++] += w * J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) Hb[15 + a] += w * J[a] * r;
+    blockSum<20>(Hb, s_sum, tid & 63, tid >> 6);
   }
-  blockSum<20>(Hb, s_sum, tid & 63, tid >> 6);
-}
 
-/** (H + lambda diag H) delta = -b by an unblocked right-looking Cholesky; false when a pivot is <= 0 or not finite */
-__device__ __forceinline__ bool dampedSolve(const double (&Hb)[20], double lambda, double (&delta)[5]) {
-  double L[5][5];
-  int at = 0;
+  /** R <- R Exp(omega), t <- normalize(t + alpha b1 + beta b2) */
+  __device__ __forceinline__ void retract(const double *T, const double (&delta)[5], double *C) const {
+    double b1[3], b2[3], tn[3];
+    sphereBasis(T + 9, b1, b2);
 #pragma unroll
-  for (int a = 0; a < 5; ++a)
+    for (int k = 0; k < 3; ++k) tn[k] = T[9 + k] + delta[0] * b1[k] + delta[1] * b2[k];
+    const double norm = sqrt(dot3(tn, tn));
+    const double xi[6] = {0.0, 0.0, 0.0, delta[2], delta[3], delta[4]};
+    const Rigid e = rigidExp(xi);
 #pragma unroll
-    for (int b = a; b < 5; ++b) {
-      const double h = Hb[at++];
-      L[b][a] = a == b ? h + lambda * h : h;
-    }
-  bool ok = true;
+    for (int i = 0; i < 3; ++i)
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const double d = L[k][k];
-    ok = ok && d > 0.0 && d <= DBL_MAX;
-    const double root = sqrt(d);
-    L[k][k] = root;
+      for (int j = 0; j < 3; ++j) C[3 * i + j] = T[3 * i] * e.R[j] + T[3 * i + 1] * e.R[3 + j] + T[3 * i + 2] * e.R[6 + j];
 #pragma unroll
-    for (int i = k + 1; i < 5; ++i) L[i][k] /= root;
-#pragma unroll
-    for (int i = k + 1; i < 5; ++i)
-#pragma unroll
-      for (int j = k + 1; j <= i; ++j) L[i][j] -= L[i][k] * L[j][k];
+    for (int k = 0; k < 3; ++k) C[9 + k] = tn[k] / norm;
   }
-  if (!ok) return false;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) delta[k] = -Hb[15 + k];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    delta[k] /= L[k][k];
-#pragma unroll
-    for (int i = k + 1; i < 5; ++i) delta[i] -= L[i][k] * delta[k];
-  }
-#pragma unroll
-  for (int k = 4; k >= 0; --k) {
-    delta[k] /= L[k][k];
-#pragma unroll
-    for (int i = 0; i < k; ++i) delta[i] -= L[k][i] * delta[k];
-  }
-  return true;
-}
-
-/** R <- R Exp(omega), t <- normalize(t + alpha b1 + beta b2) */
-__device__ __forceinline__ void retract(const double *T, const double (&delta)[5], double *C) {
-  double b1[3], b2[3], tn[3];
-  sphereBasis(T + 9, b1, b2);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) tn[k] = T[9 + k] + delta[0] * b1[k] + delta[1] * b2[k];
-  const double norm = sqrt(dot3(tn, tn));
-  const double xi[6] = {0.0, 0.0, 0.0, delta[2], delta[3], delta[4]};
-  const Rigid e = rigidExp(xi);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = T[3 * i] * e.R[j] + T[3 * i + 1] * e.R[3 + j] + T[3 * i + 2] * e.R[6 + j];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) C[9 + k] = tn[k] / norm;
-}
-
-/** the LM driver of the PnP over the five degrees of freedom, over the inliers of `Tsel`; T is refined in place */
-__device__ __forceinline__ void refineStage(double *T, const double *Tsel, const double *__restrict__ A, const double *__restrict__ B,
-                                            const TwoViewParams &p, double *s_sum, int tid, int &iterations, int &flags, double &cost_initial,
-                                            double &cost) {
-  double counting, lambda = p.lambda_0;
-  iterations = 0;
-  flags = 0;
-  blockCost(T, Tsel, A, B, p, s_sum, tid, cost, counting);
-  cost_initial = cost;
-  if (counting == 0.0) flags = DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL;
-  bool linearise = true;
-  double Hb[20];
-  while (iterations < p.max_iterations && flags == 0) {
-    if (linearise) blockLinearise(T, Tsel, A, B, p, s_sum, tid, Hb);
-    linearise = false;
-    double delta[5];
-    ++iterations;
-    if (!dampedSolve(Hb, lambda, delta)) {
-      lambda *= p.increase_factor;
-      continue;
-    }
-    double C[12], candidate_cost, candidate_counting;
-    retract(T, delta, C);
-    blockCost(C, Tsel, A, B, p, s_sum, tid, candidate_cost, candidate_counting);
-    int reason = fabs(cost - candidate_cost) / cost < p.function_tolerance ? DSOPP_HIP_GEOMETRIC_BA_FUNCTION_TOLERANCE : 0;
-    if (candidate_cost < cost) {
-      double step = 0.0;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) step += delta[k] * delta[k];
-      const double state = T[9] * T[9] + T[10] * T[10] + T[11] * T[11] + 1.0;
-      if (step < p.parameter_tolerance * (state + p.parameter_tolerance)) reason |= DSOPP_HIP_GEOMETRIC_BA_PARAMETER_TOLERANCE;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) T[e] = C[e];
-      cost = candidate_cost;
-      linearise = true;
-      lambda /= p.decrease_factor;
-    } else {
-      lambda *= p.increase_factor;
-    }
-    flags = reason;
-  }
-}
-
-/** the inliers of pose T in ascending order: 256 pairs per step, a wave's ballot places its lanes, the waves' counts place the waves */
-__device__ __forceinline__ int listInliers(const double *T, const double *__restrict__ A, const double *__restrict__ B, const TwoViewParams &p,
-                                           int *s_wave_count, int tid, int *__restrict__ inliers) {
-  const int lane = tid & 63, wave = tid >> 6;
-  int total = 0;
-  for (int base = 0; base < p.n; base += kBlock) {
-    const int j = base + tid;
-    const bool in = j < p.n && isInlier(T, A, B, j, p);
-    const unsigned long long mask = __ballot(in);
-    if (lane == 0) s_wave_count[wave] = __builtin_popcountll(mask);
-    __syncthreads();
-    int offset = total, step = 0;
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) {
-      if (w < wave) offset += s_wave_count[w];
-      step += s_wave_count[w];
-    }
-    if (in) inliers[offset + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = j;
-    total += step;
-    __syncthreads();  // (s_wave_count is written again)
-  }
-  return total;
-}
+};
 
 __global__ void __launch_bounds__(kBlock) twoViewRansacKernel(const double *__restrict__ A, const double *__restrict__ B, const int *__restrict__ samples,
                                                               unsigned *ticket, int *hyp_num_solutions, double *hyp_poses, int *hyp_counts,
@@ -989,55 +793,9 @@ __global__ void __launch_bounds__(kBlock) twoViewRansacKernel(const double *__re
     if (lane < kMaxSolutions) hyp_counts[kMaxSolutions * static_cast<size_t>(hyp) + lane] = count;
     for (int e = lane; e < kMaxSolutions * 12; e += 64) hyp_poses[kMaxSolutions * 12 * static_cast<size_t>(hyp) + e] = s.pose[e / 12][e % 12];
   }
-  // the hand-off: the stores above have left every wave, then one release at device scope, then the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = drawn == gridDim.x - 1 ? 1u : 0u;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lastWorkgroup(ticket, s_last)) return;
 
-  // the selection, by wave 0: the greatest count, the lowest hypothesis among equals, the lowest solution among that one's
-  if (wave == 0) {
-    int best = 0, best_i = INT_MAX;
-    for (int i = lane; i < p.iterations; i += 64) {
-      int c = 0;
-      for (int k = 0; k < kMaxSolutions; ++k) {
-        const int ck = freshLoad(hyp_counts + kMaxSolutions * static_cast<size_t>(i) + k);
-        c = ck > c ? ck : c;
-      }
-      if (c > best) {
-        best = c;
-        best_i = i;
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int c = __shfl_xor(best, o, 64), i = __shfl_xor(best_i, o, 64);
-      if (c > best || (c == best && i < best_i)) {
-        best = c;
-        best_i = i;
-      }
-    }
-    if (lane == 0) {
-      int solution = -1;
-      if (best > 0) {
-        for (int k = kMaxSolutions - 1; k >= 0; --k)
-          if (freshLoad(hyp_counts + kMaxSolutions * static_cast<size_t>(best_i) + k) == best) solution = k;
-      }
-      s_best_iteration = best > 0 ? best_i : -1;
-      s_best_solution = solution;
-      s_best_count = best;
-    }
-  }
+  if (wave == 0) selectBest<kMaxSolutions>(hyp_counts, p.iterations, lane, s_best_iteration, s_best_solution, s_best_count);
   __syncthreads();
   const int best_iteration = s_best_iteration, best_solution = s_best_solution;
   double T0[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, T1[12], T2[12];
@@ -1051,11 +809,12 @@ __global__ void __launch_bounds__(kBlock) twoViewRansacKernel(const double *__re
   int iterations[2] = {0, 0}, flags[2] = {0, 0}, total = 0;
   double cost_initial[2] = {0.0, 0.0}, cost[2] = {0.0, 0.0};
   if (best_iteration >= 0) {
-    refineStage(T1, T0, A, B, p, s_sum, tid, iterations[0], flags[0], cost_initial[0], cost[0]);
+    const TwoViewRefinement problem{A, B, p, s_sum, tid};
+    refinePose(problem, T1, T0, iterations[0], flags[0], cost_initial[0], cost[0]);
 #pragma unroll
     for (int e = 0; e < 12; ++e) T2[e] = T1[e];
-    refineStage(T2, T1, A, B, p, s_sum, tid, iterations[1], flags[1], cost_initial[1], cost[1]);
-    total = listInliers(T1, A, B, p, s_wave_count, tid, inliers);
+    refinePose(problem, T2, T1, iterations[1], flags[1], cost_initial[1], cost[1]);
+    total = listInliers(p.n, [&](int j) { return isInlier(T1, A, B, j, p); }, s_wave_count, tid, inliers);
   }
   if (tid == 0) {
     result->matches = 0;  // (the host counts them)
@@ -1112,14 +871,7 @@ __global__ void __launch_bounds__(kBlock) twoViewTriangulateKernel(const double 
 }  // namespace
 }  // namespace dsopp_hip
 
-struct dsopp_hip_two_view_ransac {
-  dsopp_hip::StreamRef sr;
-  dsopp_hip::Event done;
-  // the inputs and the results of a call: one device block and one pinned mirror each, laid out by TwoViewLayout; they grow geometrically
-  dsopp_hip::DeviceMem<uint8_t> d_in, d_out;
-  dsopp_hip::PinnedMem<uint8_t> h_in, h_out;
-  size_t in_capacity = 0, out_capacity = 0;
-};
+struct dsopp_hip_two_view_ransac : dsopp_hip::StagedCall {};
 
 namespace dsopp_hip {
 namespace {
@@ -1147,14 +899,6 @@ struct TwoViewLayout {
   }
 };
 
-size_t grown(size_t capacity, size_t need) {
-  size_t cap = capacity ? capacity : 4096;
-  while (cap < need) cap *= 2;
-  return cap;
-}
-
-bool finiteHost(double v) { return std::fabs(v) <= DBL_MAX; }
-
 void defaultOptions(dsopp_hip_two_view_ransac_options *o) {
   o->a = 1.5;
   o->lambda_0 = 1e-4;
@@ -1166,33 +910,16 @@ void defaultOptions(dsopp_hip_two_view_ransac_options *o) {
   o->reserved = 0;
 }
 
-void reserve(dsopp_hip_two_view_ransac *h, const TwoViewLayout &lay) {
-  if (h->in_capacity < lay.in_bytes) {
-    const size_t cap = grown(h->in_capacity, lay.in_bytes);
-    h->in_capacity = 0;
-    h->d_in.alloc(cap);
-    h->h_in.reserve(cap);
-    h->in_capacity = cap;
-  }
-  if (h->out_capacity < lay.out_bytes) {
-    const size_t cap = grown(h->out_capacity, lay.out_bytes);
-    h->out_capacity = 0;
-    h->d_out.alloc(cap);
-    h->h_out.reserve(cap);
-    h->out_capacity = cap;
-  }
-}
-
 /** the checks both calls share; returns the matches */
 int checkPairs(double fx, double fy, double cx, double cy, int width, int height, int n, const double *points_a, const double *points_b) {
   if (n < 0 || n > (1 << 24)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d pairs", n);
-  if (!finiteHost(fx) || !finiteHost(fy) || !finiteHost(cx) || !finiteHost(cy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "an intrinsic is not finite");
+  if (!finite(fx) || !finite(fy) || !finite(cx) || !finite(cy)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "an intrinsic is not finite");
   if (n > 0 && (!points_a || !points_b)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const double xmax = static_cast<double>(width) - 5.0, ymax = static_cast<double>(height) - 5.0;
   int matches = 0;
   for (size_t j = 0; j < static_cast<size_t>(n); ++j) {
     const double ax = points_a[2 * j], ay = points_a[2 * j + 1], bx = points_b[2 * j], by = points_b[2 * j + 1];
-    if (!finiteHost(ax) || !finiteHost(ay) || !finiteHost(bx) || !finiteHost(by)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "pair %zu is not finite", j);
+    if (!finite(ax) || !finite(ay) || !finite(bx) || !finite(by)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "pair %zu is not finite", j);
     if (ax >= 4.0 && ax <= xmax && ay >= 4.0 && ay <= ymax && bx >= 4.0 && bx <= xmax && by >= 4.0 && by <= ymax) ++matches;
   }
   return matches;
@@ -1216,29 +943,21 @@ void estimate(dsopp_hip_two_view_ransac *h, double fx, double fy, double cx, dou
   if (!h) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null two-view ransac");
   if (!result) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (iterations < 0 || iterations > (1 << 24)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d iterations", iterations);
-  if (!finiteHost(threshold_px)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the threshold is not finite");
+  if (!finite(threshold_px)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the threshold is not finite");
   if (min_matches < 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "min_matches %d", min_matches);
   const int matches = checkPairs(fx, fy, cx, cy, width, height, n, points_a, points_b);
   if (n > 0 && !inlier_indices) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   dsopp_hip_two_view_ransac_options o;
   defaultOptions(&o);
   if (options) o = *options;
-  if (!finiteHost(o.a) || !finiteHost(o.lambda_0) || !finiteHost(o.function_tolerance) || !finiteHost(o.parameter_tolerance) ||
-      !finiteHost(o.decrease_factor) || !finiteHost(o.increase_factor) || !(o.a > 0.0) || o.lambda_0 < 0.0 || !(o.decrease_factor > 0.0) ||
+  if (!finite(o.a) || !finite(o.lambda_0) || !finite(o.function_tolerance) || !finite(o.parameter_tolerance) ||
+      !finite(o.decrease_factor) || !finite(o.increase_factor) || !(o.a > 0.0) || o.lambda_0 < 0.0 || !(o.decrease_factor > 0.0) ||
       !(o.increase_factor > 0.0) || o.max_iterations < 0)
     fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a refinement option is out of range");
   const bool enough = matches >= min_matches;  // (estimate_so3xs2.cpp:48: below it the samples are not looked at)
   if (enough && n > 0 && iterations > 0) {
     if (n < 5) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d pairs: a sample of distinct indices needs 5", n);
-    if (!samples) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    for (int i = 0; i < iterations; ++i) {
-      const int32_t *s = samples + 5 * static_cast<size_t>(i);
-      for (int k = 0; k < 5; ++k) {
-        if (s[k] < 0 || s[k] >= n) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d holds index %d of %d pairs", i, s[k], n);
-        for (int l = 0; l < k; ++l)
-          if (s[l] == s[k]) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "sample %d repeats an index", i);
-      }
-    }
+    checkSamples<5, false>(samples, iterations, n, "pairs");
   }
   std::memset(result, 0, sizeof(*result));
   result->matches = matches;
@@ -1253,7 +972,7 @@ void estimate(dsopp_hip_two_view_ransac *h, double fx, double fy, double cx, dou
   h->sr.use();
   const hipStream_t st = h->sr.stream;
   const TwoViewLayout lay(count, hyps);
-  reserve(h, lay);
+  h->ensure(lay.in_bytes, lay.out_bytes);
   uint8_t *hi = h->h_in.get(), *di = h->d_in.get(), *ho = h->h_out.get(), *dout = h->d_out.get();
   std::memset(hi, 0, lay.a);  // (the ticket is armed by the upload)
   std::memcpy(hi + lay.a, points_a, 16 * count);
@@ -1299,13 +1018,13 @@ void triangulate(dsopp_hip_two_view_ransac *h, double fx, double fy, double cx, 
   if (n > 0 && (!positions || !keep)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (cos_threshold != cos_threshold) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the threshold is not a number");
   for (int e = 0; e < 12; ++e)
-    if (!finiteHost(pose_a_b[e]) || !finiteHost(pose_world_a[e])) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a pose is not finite");
+    if (!finite(pose_a_b[e]) || !finite(pose_world_a[e])) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a pose is not finite");
   if (n == 0) return;
   h->sr.use();
   const hipStream_t st = h->sr.stream;
   const size_t count = static_cast<size_t>(n);
   const TwoViewLayout lay(count, 0);
-  reserve(h, lay);
+  h->ensure(lay.in_bytes, lay.out_bytes);
   uint8_t *hi = h->h_in.get(), *di = h->d_in.get(), *ho = h->h_out.get(), *dout = h->d_out.get();
   std::memset(hi, 0, 16);
   std::memcpy(hi + lay.poses, pose_a_b, 96);
@@ -1340,21 +1059,9 @@ void dsopp_hip_two_view_ransac_default_options(dsopp_hip_two_view_ransac_options
   if (options) defaultOptions(options);
 }
 
-int dsopp_hip_two_view_ransac_create(int device, void *stream, dsopp_hip_two_view_ransac **out) {
-  return guarded([&] {
-    if (!out) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    auto r = std::make_unique<dsopp_hip_two_view_ransac>();
-    r->sr.init(device, stream);
-    *out = r.release();
-  });
-}
+int dsopp_hip_two_view_ransac_create(int device, void *stream, dsopp_hip_two_view_ransac **out) { return createHandle(device, stream, out); }
 
-void dsopp_hip_two_view_ransac_destroy(dsopp_hip_two_view_ransac *r) {
-  if (!r) return;
-  (void)hipSetDevice(r->sr.device);
-  if (r->sr.stream) (void)hipStreamSynchronize(r->sr.stream);
-  delete r;
-}
+void dsopp_hip_two_view_ransac_destroy(dsopp_hip_two_view_ransac *r) { destroyHandle(r); }
 
 int dsopp_hip_two_view_ransac_estimate(dsopp_hip_two_view_ransac *r, double fx, double fy, double cx, double cy, int width, int height, int n,
                                        const double *points_a, const double *points_b, int iterations, const int32_t *samples, double threshold_px,
