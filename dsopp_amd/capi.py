@@ -62,6 +62,21 @@ class TwoViewRansacResult(C.Structure):
                 ("pose_reselect", C.c_double * 12), ("pose", C.c_double * 12)]
 
 
+MAX_FRAMES = 16  # DSOPP_HIP_MAX_FRAMES
+MARGINALIZATION_SPARSE, MARGINALIZATION_MAXIMUM_SIZE = 0, 1
+
+
+class MarginalizationOptions(C.Structure):
+    _fields_ = [("strategy", C.c_int32), ("minimum_size", C.c_int32), ("maximum_size", C.c_int32), ("maximum_share_marginalized", C.c_double)]
+
+
+class MarginalizationResult(C.Structure):
+    _fields_ = [("n_active", C.c_int32), ("active_ids", C.c_int32 * MAX_FRAMES), ("n_selected", C.c_int32), ("selected", C.c_int32 * MAX_FRAMES),
+                ("n_marginalized", C.c_int32), ("marginalized_ids", C.c_int32 * MAX_FRAMES), ("scores", C.c_double * MAX_FRAMES),
+                ("n_active_landmarks", C.c_int32 * MAX_FRAMES), ("n_marginalized_landmarks", C.c_int32 * MAX_FRAMES),
+                ("n_newly_marginalized", C.c_int32), ("n_newly_outlier", C.c_int32)]
+
+
 class GeometricBAProblem(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
                 ("num_frames", C.c_int32), ("num_landmarks", C.c_int32), ("num_observations", C.c_int32), ("reserved", C.c_int32),
@@ -152,6 +167,8 @@ SYMBOLS = [
     "dsopp_hip_pnp_ransac_estimate",
     "dsopp_hip_two_view_ransac_default_iterations", "dsopp_hip_two_view_ransac_default_options", "dsopp_hip_two_view_ransac_create",
     "dsopp_hip_two_view_ransac_destroy", "dsopp_hip_two_view_ransac_estimate", "dsopp_hip_two_view_ransac_triangulate",
+    "dsopp_hip_window_note_optimization", "dsopp_hip_window_get_optimization_counts", "dsopp_hip_marginalization_default_options",
+    "dsopp_hip_window_choose_marginalization",
 ]
 
 _lib = None
@@ -217,6 +234,14 @@ def default_pba_options(**kw) -> Options:
             o.affine_brightness_regularizer[0], o.affine_brightness_regularizer[1] = v
         else:
             setattr(o, k, v)
+    return o
+
+
+def default_marginalization_options(**kw) -> MarginalizationOptions:
+    o = MarginalizationOptions()
+    lib().dsopp_hip_marginalization_default_options(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
     return o
 
 
@@ -1321,6 +1346,40 @@ class HipWindow:
         H, b, e, sz = np.zeros((K, K)), np.zeros(K), C.c_double(), C.c_int32()
         _chk(lib().dsopp_hip_window_get_marginalized(self._h, _p(H), _p(b), C.byref(e), C.byref(sz)))
         return H, b, e.value
+
+    def note_optimization(self):
+        """the counting half of updateFrame: numberOfSuccessfulOptimizations += n_inliers > 3 for every landmark not flagged marginalised"""
+        _chk(lib().dsopp_hip_window_note_optimization(self._h))
+
+    def get_optimization_counts(self, frame_id):
+        counts = np.zeros(self.num_landmarks(frame_id), dtype=np.int32)
+        _chk(lib().dsopp_hip_window_get_optimization_counts(self._h, int(frame_id), _p(counts, np.int32)))
+        return counts
+
+    def choose_marginalization(self, options: "MarginalizationOptions | None" = None, camera_frame_ids=None, immature_sets=None, apply=False):
+        """FrameMarginalizationStrategy::marginalize on the window's state.  camera_frame_ids / immature_sets: one entry per window frame
+        (None: the window's ids / no immature landmarks).  Returns dict(active_ids, selected, marginalized_ids, scores, n_active_landmarks,
+        n_marginalized_landmarks, n_newly_marginalized, n_newly_outlier, flags={frame id: bytes, bit0 marginalised, bit1 outlier})."""
+        options = options or default_marginalization_options()
+        ids = self.frame_ids() if self.num_frames else []
+        cam = None if camera_frame_ids is None else np.ascontiguousarray(camera_frame_ids, dtype=np.int32)
+        assert cam is None or len(cam) == len(ids)
+        sets = None
+        if immature_sets is not None:
+            assert len(immature_sets) == len(ids)
+            sets = (C.c_void_p * max(1, len(ids)))(*[s._h if s is not None else None for s in immature_sets])
+        counts = [self.num_landmarks(i) for i in ids]
+        flags = np.zeros(max(1, sum(counts)), dtype=np.uint8)
+        res = MarginalizationResult()
+        _chk(lib().dsopp_hip_window_choose_marginalization(self._h, C.byref(options), _p(cam, np.int32), sets, int(bool(apply)), C.byref(res),
+                                                           _p(flags, np.uint8)))
+        A = res.n_active
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+        return dict(active_ids=list(res.active_ids[:A]), selected=list(res.selected[:res.n_selected]),
+                    marginalized_ids=list(res.marginalized_ids[:res.n_marginalized]), scores=np.array(res.scores[:A]),
+                    n_active_landmarks=list(res.n_active_landmarks[:A]), n_marginalized_landmarks=list(res.n_marginalized_landmarks[:A]),
+                    n_newly_marginalized=res.n_newly_marginalized, n_newly_outlier=res.n_newly_outlier,
+                    flags={fid: flags[offsets[k]:offsets[k + 1]].copy() for k, fid in enumerate(ids)})
 
     def get_covariance(self, ref_id, tgt_id):
         cov = np.zeros((6, 6))

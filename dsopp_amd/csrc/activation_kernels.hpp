@@ -21,13 +21,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_geom.hpp"
+#include "immature_set.hpp"
 #include "pba_types.hpp"
 #include "pyramid.hpp"
 
 namespace dsopp_hip {
 
 enum : uint8_t { kActActivate = 0, kActSkip = 1, kActDelete = 2 };                 // ImmatureLandmarkActivationStatus, active_keyframe.hpp:40-44
-enum : uint8_t { kImmGood = 0, kImmOutOfBoundary = 1, kImmOutlier = 2, kImmSkipped = 3, kImmIllConditioned = 4, kImmDelete = 6 };
 enum : int { kCandNone = -1, kCandUndecided = 0, kCandAccepted = 1, kCandBlocked = 2 };
 constexpr int kActSelectThreads = 1024;
 constexpr double kActMinCell = 4.0;  // grid cell edge = max(distance, kActMinCell) pixels of the sparsity level
@@ -145,8 +145,7 @@ __global__ void __launch_bounds__(256) activationProjectKernel(ActArgs a) {
     if (st == kImmDelete || !kf.traced[i] || st == kImmOutlier) {
       act = kActDelete;
     } else {
-      const bool ready = (st == kImmGood || st == kImmSkipped || st == kImmIllConditioned || st == kImmOutOfBoundary) &&
-                         (kf.search_pixel_interval[i] < 8.0) && (kf.uniqueness[i] > 3.0) && (idepth > 0);  // readyForActivation
+      const bool ready = immatureReadyForActivation(st, kf.search_pixel_interval[i], kf.uniqueness[i], idepth);
       if (!ready) {
         act = st == kImmOutOfBoundary ? kActDelete : kActSkip;
       } else {

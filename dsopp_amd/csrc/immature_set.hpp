@@ -20,6 +20,14 @@ struct dsopp_hip_immature_set {
 };
 
 namespace dsopp_hip {
+// ImmatureStatus (immature_tracking_landmark.hpp:14-22) as the sets' status bytes hold it
+enum : uint8_t { kImmGood = 0, kImmOutOfBoundary = 1, kImmOutlier = 2, kImmSkipped = 3, kImmIllConditioned = 4, kImmDelete = 6 };
+/** ImmatureTrackingLandmark::readyForActivation (src/track/landmarks/src/immature_tracking_landmark.cpp:46-52); idepth = the mean of the
+ *  landmark's interval, ImmatureTrackingLandmark::idepth() */
+__host__ __device__ inline bool immatureReadyForActivation(uint8_t status, double search_pixel_interval, double uniqueness, double idepth) {
+  return (status == kImmGood || status == kImmSkipped || status == kImmIllConditioned || status == kImmOutOfBoundary) &&
+         (search_pixel_interval < 8.0) && (uniqueness > 3.0) && (idepth > 0);
+}
 struct ImmatureSetDeleter {
   void operator()(dsopp_hip_immature_set *s) const { dsopp_hip_immature_set_destroy(s); }
 };

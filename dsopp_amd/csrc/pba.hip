@@ -21,6 +21,7 @@
 #include "activation_kernels.hpp"
 #include "immature_set.hpp"
 #include "semantic_observation_kernels.hpp"
+#include "marginalization.hpp"
 
 namespace dsopp_hip {
 namespace {
@@ -67,6 +68,9 @@ struct HostFrame {
   // class observations (dsopp_hip_window_add_semantic_observations): 256 counters per landmark, rows in the CALLER's order — no internal
   // re-ordering moves them —, allocated by the first add that reaches this frame; rows past the landmarks counted so far are zero
   DeviceBuffer<uint8_t> sem_hist;
+  // numberOfSuccessfulOptimizations() of the landmarks (dsopp_hip_window_note_optimization): kept like sem_hist — rows in the CALLER's
+  // order, allocated by the first note, zero past the landmarks noted so far
+  DeviceBuffer<int32_t> successes;
   int internalOf(int caller) const { return to_internal.empty() ? caller : to_internal[static_cast<size_t>(caller)]; }
 };
 
@@ -197,6 +201,7 @@ struct dsopp_hip_window {
   std::vector<std::unique_ptr<HostFrame>> frame_pool;
   std::vector<std::unique_ptr<ResidualTable>> table_pool;
   DeviceBuffer<uint8_t> d_sem_args;  // job and partner tables of dsopp_hip_window_add_semantic_observations
+  DeviceBuffer<uint8_t> d_marg;      // dsopp_hip_window_choose_marginalization: [ticket | counts | decision | flag bytes]
   DeviceBuffer<double> dm_tmp;  // undilated reference depth maps, all levels (temporaries of createReferenceDepthMaps)
   std::vector<dsopp_hip_depth_maps *> live_maps;          // maps this window produced and that still borrow its stream
   struct ActivationScratch {            // work buffers of dsopp_hip_window_activate_landmarks
@@ -2454,6 +2459,7 @@ int dsopp_hip_window_push_frame(dsopp_hip_window *w, int32_t frame_id, int64_t t
       f->batch_end.clear();
       f->to_marginalize = false;
       f->sem_hist.release();  // (the counters of the keyframe that left)
+      f->successes.release();
     } else {
       f = std::make_unique<HostFrame>();
     }
@@ -4141,5 +4147,154 @@ int dsopp_hip_window_activate_landmarks(dsopp_hip_window *w, int32_t n_keyframes
       if (idepth && idepth[k]) std::memcpy(idepth[k], h_id + kf.immature_offset, static_cast<size_t>(kf.n_immature) * 8);
     }
     if (result) *result = res;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the keyframes and landmarks that leave the window (marginalization.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+int dsopp_hip_window_note_optimization(dsopp_hip_window *w) {
+  return guarded([&] {
+    if (!w) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null window");
+    w->sr.use();
+    flushAppends(*w);
+    for (auto &fp : w->frames) {
+      HostFrame &f = *fp;
+      if (f.n <= 0) continue;
+      f.successes.reserve(static_cast<size_t>(f.n), f.successes.capacity, w->sr.stream);
+      launchNoteOptimization(f.dflags.ptr, f.n_inliers.ptr, f.permuted() ? f.d_to_internal.ptr : nullptr, f.successes.ptr, f.n, w->sr.stream);
+    }
+  });
+}
+
+int dsopp_hip_window_get_optimization_counts(dsopp_hip_window *w, int32_t frame_id, int32_t *counts) {
+  return guarded([&] {
+    if (!w || !counts) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    w->sr.use();
+    HostFrame &f = w->frameById(frame_id);
+    if (f.n <= 0) return;
+    if (!f.successes.ptr) {  // no note has reached this frame
+      std::memset(counts, 0, static_cast<size_t>(f.n) * sizeof(int32_t));
+      return;
+    }
+    f.successes.reserve(static_cast<size_t>(f.n), f.successes.capacity, w->sr.stream);
+    f.successes.download(counts, static_cast<size_t>(f.n), 0, w->sr.stream);
+    w->sr.sync();
+  });
+}
+
+int dsopp_hip_window_choose_marginalization(dsopp_hip_window *w, const dsopp_hip_marginalization_options *options,
+                                            const int32_t *camera_frame_ids, dsopp_hip_immature_set *const *immature, int32_t apply,
+                                            dsopp_hip_marginalization_result *result, uint8_t *flags) {
+  return guarded([&] {
+    if (!w || !options || !result) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (options->strategy != DSOPP_HIP_MARGINALIZATION_SPARSE && options->strategy != DSOPP_HIP_MARGINALIZATION_MAXIMUM_SIZE)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "unknown marginalisation strategy %d", options->strategy);
+    if (options->minimum_size < 0 || options->maximum_size < 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "negative window size");
+    std::memset(result, 0, sizeof(*result));
+    for (double &s : result->scores) s = std::nan("");
+    w->sr.use();
+    flushAppends(*w);
+    downloadState(*w);  // the poses of the score
+    hipStream_t st = w->sr.stream;
+    const int F = w->F();
+    MargArgs a;
+    std::memset(&a, 0, sizeof(a));
+    int n_active = 0, n_flags = 0, blocks = 0;
+    for (int s = 0; s < F; ++s)
+      if (!w->frames[static_cast<size_t>(s)]->is_marginalized) {
+        result->active_ids[n_active++] = w->frames[static_cast<size_t>(s)]->id;
+        a.last_slot = s;
+      }
+    result->n_active = n_active;
+    if (!n_active) return;  // (the reference reads activeFrames().back())
+    const int last_id = w->frames[static_cast<size_t>(a.last_slot)]->id;
+    n_active = 0;
+    for (int s = 0; s < F; ++s) {
+      HostFrame &f = *w->frames[static_cast<size_t>(s)];
+      MargFrame &m = a.frame[s];
+      m.n = f.n;
+      m.active = f.is_marginalized ? -1 : n_active++;
+      m.camera_id = camera_frame_ids ? camera_frame_ids[s] : f.id;
+      const Rigid T = poseOf(*w, s);
+      for (int i = 0; i < 3; ++i) m.t[i] = T.t[i];
+      m.flags = hbm(f.dflags.ptr);
+      m.n_inliers = hbm(f.n_inliers.ptr);
+      m.idepth = hbm(f.idepth.ptr);
+      m.inv_hdd = hbm(f.inv_hdd.ptr);
+      m.to_internal = f.permuted() ? hbm(f.d_to_internal.ptr) : nullptr;
+      if (f.successes.ptr && f.n > 0) {
+        f.successes.reserve(static_cast<size_t>(f.n), f.successes.capacity, st);
+        m.successes = hbm(f.successes.ptr);
+      }
+      auto it = f.residuals.find(last_id);
+      if (it != f.residuals.end() && it->second->n > 0) {
+        m.n_last = std::min(it->second->n, f.n);
+        m.status_last = hbm(it->second->status.ptr);
+      }
+      if (const dsopp_hip_immature_set *set = (immature && !f.is_marginalized) ? immature[s] : nullptr) {
+        if (set->sr.device != w->sr.device) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "frame %d: the immature set lives on another device", f.id);
+        if (set->sr.stream != st) set->sr.sync();  // the depth estimator may still be writing the state
+        if (set->n > 0) {
+          m.n_immature = set->n;
+          m.imm_status = hbm(set->d_flags.ptr);
+          m.imm_io = hbm(set->d_io.ptr);
+        }
+      }
+      m.first_block = blocks;
+      m.flags_offset = n_flags;
+      blocks += std::max(1, (std::max(m.n, m.n_immature) + kMargBlock - 1) / kMargBlock);
+      n_flags += f.n;
+    }
+    a.n_frames = F;
+    a.n_blocks = blocks;
+    a.strategy = options->strategy;
+    a.minimum_size = options->minimum_size;
+    a.maximum_size = options->maximum_size;
+    a.maximum_share_marginalized = options->maximum_share_marginalized;
+    // [ticket, pad | counts 2 per slot | decision | flag bytes]: the head is cleared by one fill, decision + flags come back in one copy
+    constexpr size_t head = (2 + 2 * kMaxFrames) * sizeof(int);
+    static_assert(head % 8 == 0 && sizeof(MargDecision) % 8 == 0, "the decision holds doubles");
+    const size_t bytes = sizeof(MargDecision) + static_cast<size_t>(n_flags);
+    w->d_marg.reserve(head + bytes, 0, st);
+    HIP_CHECK(hipMemsetAsync(w->d_marg.ptr, 0, head + sizeof(MargDecision), st));
+    a.ticket = reinterpret_cast<unsigned *>(w->d_marg.ptr);
+    a.counts = reinterpret_cast<int *>(w->d_marg.ptr) + 2;
+    a.decision = reinterpret_cast<MargDecision *>(w->d_marg.ptr + head);
+    a.new_flags = hbm(w->d_marg.ptr + head + sizeof(MargDecision));
+    launchChooseMarginalization(a, st);
+    reserveGeometric(w->h_export, bytes);
+    char *h = static_cast<char *>(w->h_export.get());
+    HIP_CHECK(hipMemcpyAsync(h, w->d_marg.ptr + head, bytes, hipMemcpyDeviceToHost, st));
+    w->sr.sync();
+    MargDecision d;
+    std::memcpy(&d, h, sizeof(d));
+    const uint8_t *new_flags = reinterpret_cast<const uint8_t *>(h + sizeof(MargDecision));
+    result->n_selected = d.n_selected;
+    result->n_marginalized = d.n_marginalized;
+    result->n_newly_marginalized = d.newly_marginalized;
+    result->n_newly_outlier = d.newly_outlier;
+    for (int i = 0; i < d.n_selected; ++i) result->selected[i] = d.selected[i];
+    for (int i = 0; i < d.n_marginalized; ++i) result->marginalized_ids[i] = w->frames[static_cast<size_t>(d.marginalized_slot[i])]->id;
+    for (int i = 0; i < d.n_active; ++i) {
+      result->scores[i] = d.score[i];
+      result->n_active_landmarks[i] = d.n_kept[i];
+      result->n_marginalized_landmarks[i] = d.n_gone[i];
+    }
+    if (flags && n_flags) std::memcpy(flags, new_flags, static_cast<size_t>(n_flags));
+    if (!apply) return;
+    // the window's one writer of landmark flags is the refresh of dsopp_hip_window_set_landmarks: the bytes go through it, frame by frame
+    // (an update that appends nothing reads no coordinate, inverse depth or patch), then the frame flags through their own entry point
+    const std::vector<uint8_t> bytes_copy(new_flags, new_flags + n_flags);  // (the refresh may reuse the pinned buffer)
+    const double none = 0;
+    for (int s = 0; s < F; ++s) {
+      const HostFrame &f = *w->frames[static_cast<size_t>(s)];
+      if (a.frame[s].active < 0 || f.n <= 0) continue;
+      if (dsopp_hip_window_set_landmarks(w, f.id, f.n, &none, &none, &none, bytes_copy.data() + a.frame[s].flags_offset) != DSOPP_HIP_OK)
+        fail(DSOPP_HIP_ERR_STATE, "flag refresh of frame %d: %s", f.id, std::string(lastError()).c_str());
+    }
+    for (int i = 0; i < d.n_marginalized; ++i)
+      if (dsopp_hip_window_mark_frame_marginalized(w, result->marginalized_ids[i]) != DSOPP_HIP_OK)
+        fail(DSOPP_HIP_ERR_STATE, "frame %d: %s", result->marginalized_ids[i], std::string(lastError()).c_str());
   });
 }

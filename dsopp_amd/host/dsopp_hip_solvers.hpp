@@ -976,6 +976,89 @@ class HipLandmarksActivator {
   dsopp_hip_activation_result last_{};
 };
 
+/**
+ * marginalization::FrameMarginalizationStrategy<Motion> (src/marginalization/include/marginalization/frame_marginalization_strategy.hpp),
+ * both kinds the fabric builds (src/marginalization/src/fabric.cpp:25-50), decided on the device from the solver's own state.
+ * marginalize(track) replaces the whole of monocular_tracker.cpp:505 and :507 for the frames concerned — the strategy, updateLocalFrame of
+ * the frames it marginalised (:317) and of the frames that stay (updateSolver): the solver is refreshed by the call, the views receive
+ * the flags.  Do NOT send updateLocalFrame for these frames again before the next pushFrame: a second update clears to_marginalize, as
+ * it does in the reference, and the landmarks would never reach the prior.  numberOfSuccessfulOptimizations lives in the solver: call
+ * noteOptimization() once after every solve() (what updateFrame does for every landmark, photometric_bundle_adjustment.cpp:256).
+ */
+class HipFrameMarginalizationStrategy {
+ public:
+  struct Track {
+    HipPhotometricBundleAdjustment *solver;     // single-device; holds every frame of activeFrames()
+    std::vector<KeyframeView *> active_frames;  // track.activeFrames(), oldest first
+    std::vector<int32_t> camera_frame_ids;      // ActiveKeyframe::id() per active frame; empty = the keyframe ids
+    std::vector<DeviceImmatureSet *> immature;  // per active frame, nullptr = no immature landmarks; empty = none at all
+  };
+  /** SparseFrameMarginalizationStrategy(minimum_size, maximum_size, maximum_number_of_marginalized) */
+  HipFrameMarginalizationStrategy(size_t minimum_size, size_t maximum_size, double maximum_share_marginalized) {
+    dsopp_hip_marginalization_default_options(&options_);
+    options_.minimum_size = static_cast<int32_t>(minimum_size);
+    options_.maximum_size = static_cast<int32_t>(maximum_size);
+    options_.maximum_share_marginalized = maximum_share_marginalized;
+  }
+  /** MaximumSizeFrameMarginalizationStrategy(maximum_size) */
+  explicit HipFrameMarginalizationStrategy(size_t maximum_size) {
+    dsopp_hip_marginalization_default_options(&options_);
+    options_.strategy = DSOPP_HIP_MARGINALIZATION_MAXIMUM_SIZE;
+    options_.maximum_size = static_cast<int32_t>(maximum_size);
+  }
+  /** the counting half of updateFrame for every frame of the solver */
+  static void noteOptimization(HipPhotometricBundleAdjustment &solver) { check(dsopp_hip_window_note_optimization(window(solver))); }
+  /** marginalize(track): the keyframe ids marginalised, in the order marginalizeFrame() hit them (what addSemanticObservations takes) */
+  std::vector<int32_t> marginalize(const Track &track) {
+    dsopp_hip_window *w = window(*track.solver);
+    int32_t nf = 0;
+    check(dsopp_hip_window_num_frames(w, &nf));
+    std::vector<int32_t> ids(static_cast<size_t>(std::max(nf, 1)));
+    check(dsopp_hip_window_frame_ids(w, nf, ids.data(), &nf));
+    // the C-ABI takes one entry per frame of the window, which may still hold frames marginalised earlier
+    std::vector<int32_t> camera_ids(ids.begin(), ids.begin() + nf), counts(static_cast<size_t>(nf), 0);
+    std::vector<dsopp_hip_immature_set *> sets(static_cast<size_t>(nf), nullptr);
+    std::vector<KeyframeView *> views(static_cast<size_t>(nf), nullptr);
+    size_t total = 0;
+    for (int32_t s = 0; s < nf; ++s) {
+      check(dsopp_hip_window_num_landmarks(w, ids[static_cast<size_t>(s)], &counts[static_cast<size_t>(s)]));
+      total += static_cast<size_t>(counts[static_cast<size_t>(s)]);
+      for (size_t a = 0; a < track.active_frames.size(); ++a) {
+        if (track.active_frames[a]->keyframe_id != ids[static_cast<size_t>(s)]) continue;
+        views[static_cast<size_t>(s)] = track.active_frames[a];
+        if (a < track.camera_frame_ids.size()) camera_ids[static_cast<size_t>(s)] = track.camera_frame_ids[a];
+        if (a < track.immature.size() && track.immature[a]) sets[static_cast<size_t>(s)] = track.immature[a]->handle();
+      }
+    }
+    std::vector<uint8_t> flags(std::max<size_t>(total, 1));
+    check(dsopp_hip_window_choose_marginalization(w, &options_, camera_ids.data(), sets.data(), 1, &last_, flags.data()));
+    size_t offset = 0;
+    for (int32_t s = 0; s < nf; ++s) {
+      const size_t n = static_cast<size_t>(counts[static_cast<size_t>(s)]);
+      if (KeyframeView *view = views[static_cast<size_t>(s)])
+        for (size_t i = 0; i < n && i < view->active_landmarks.size(); ++i) {
+          view->active_landmarks[i].is_marginalized = (flags[offset + i] & 1) != 0;
+          if (flags[offset + i] & 2) view->active_landmarks[i].is_outlier = true;
+        }
+      offset += n;
+    }
+    std::vector<int32_t> marginalized(last_.marginalized_ids, last_.marginalized_ids + last_.n_marginalized);
+    for (KeyframeView *view : track.active_frames)
+      for (int32_t id : marginalized)
+        if (view->keyframe_id == id) view->is_marginalized = true;
+    return marginalized;
+  }
+  const dsopp_hip_marginalization_result &lastResult() const { return last_; }
+
+ private:
+  static dsopp_hip_window *window(const HipPhotometricBundleAdjustment &solver) {
+    if (!solver.handle()) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the marginalisation strategy needs a single-device solver");
+    return solver.handle();
+  }
+  dsopp_hip_marginalization_options options_;
+  dsopp_hip_marginalization_result last_{};
+};
+
 /** features::Correspondence (feature_based_slam/features/correspondence.hpp:12-19) */
 struct FlowCorrespondence {
   bool is_inlier;

@@ -1334,6 +1334,94 @@ int dsopp_hip_window_activate_landmarks(dsopp_hip_window *w, int32_t n_keyframes
                                         int32_t refine, double sigma_huber_loss, uint8_t *const *activation_status, double *const *idepth,
                                         dsopp_hip_activation_result *result);
 
+/* ---- the keyframes and landmarks that leave the window (marginalisation strategy) ----
+ * marginalize(solver, track, marginalizer) — src/tracker/tracker/src/monocular_tracker.cpp:308-321, called at :505 after every
+ * bundle adjustment of a new keyframe — decided on the window's own state: landmark flags, n_inliers, the connection statuses towards
+ * the newest keyframe, inverse depths, 1 / H_dd, the poses, and the immature sets' estimator state.
+ *
+ * The counting half of updateFrame: ActiveTrackingLandmark::setNumberOfInlierResidualsInTheLastOptimization
+ * (src/track/landmarks/src/active_tracking_landmark.cpp:42-49, called by photometric_bundle_adjustment.cpp:256 for every landmark
+ * that is not marginalised) increments numberOfSuccessfulOptimizations() when the landmark had more than 3 inlier residuals.
+ * note_optimization does that for every landmark of every frame of the window that is not flagged marginalised, from the window's
+ * n_inliers; call it once after each solve (no solve calls it).  The counters live with the frame like the class observations above:
+ * rows in the caller's landmark order, allocated by the first call, zero for landmarks appended later, untouched by internal
+ * re-ordering and by dsopp_hip_window_snapshot / _restore, released when the frame leaves the window. */
+int dsopp_hip_window_note_optimization(dsopp_hip_window *w);
+/* numberOfSuccessfulOptimizations() of every landmark of a frame (n_landmarks values, the caller's order; zero before the first note) */
+int dsopp_hip_window_get_optimization_counts(dsopp_hip_window *w, int32_t frame_id, int32_t *counts);
+
+/* marginalization_strategy of the tracker's configuration (src/marginalization/src/fabric.cpp):
+ * `sparse` = SparseFrameMarginalizationStrategy(minimum_size, maximum_size, maximum_percentage_of_marginalized_points_in_frame),
+ * `maximum_size` = MaximumSizeFrameMarginalizationStrategy(maximum_size).  Defaults: sparse, 5, 7, 0.95
+ * (test/test_data/tummono/mono.yaml:39-43). */
+enum { DSOPP_HIP_MARGINALIZATION_SPARSE = 0, DSOPP_HIP_MARGINALIZATION_MAXIMUM_SIZE = 1 };
+typedef struct dsopp_hip_marginalization_options {
+  int32_t strategy;
+  int32_t minimum_size, maximum_size;
+  double maximum_share_marginalized;
+} dsopp_hip_marginalization_options;
+void dsopp_hip_marginalization_default_options(dsopp_hip_marginalization_options *o);
+
+/* Everything below is indexed by ACTIVE frame: the window's frames that are not flagged marginalised, oldest first
+ * (track.activeFrames()); n_active of them. */
+typedef struct dsopp_hip_marginalization_result {
+  int32_t n_active;
+  int32_t active_ids[DSOPP_HIP_MAX_FRAMES]; /* window ids of the active frames */
+  int32_t n_selected;
+  int32_t selected[DSOPP_HIP_MAX_FRAMES]; /* the strategy's set `to_marginalize`: active indices, ascending */
+  int32_t n_marginalized;
+  int32_t marginalized_ids[DSOPP_HIP_MAX_FRAMES]; /* window ids of the frames marginalizeFrame() hit, in erase order */
+  double scores[DSOPP_HIP_MAX_FRAMES]; /* distance_score of findFramesToMarginalize; NaN where it computes none */
+  int32_t n_active_landmarks[DSOPP_HIP_MAX_FRAMES];       /* numberOfActiveAndImmatureLandmarks */
+  int32_t n_marginalized_landmarks[DSOPP_HIP_MAX_FRAMES]; /* numberOfMarginalizedLandmarks */
+  int32_t n_newly_marginalized, n_newly_outlier;          /* landmarks of the whole window */
+} dsopp_hip_marginalization_result;
+
+/* FrameMarginalizationStrategy::marginalize(track) for the window's active frames.
+ *
+ * sparse (src/marginalization/src/sparse_frame_marginalization_strategy.cpp):
+ *  - findFramesWithSmallNumberOfActivePoints (:38-53, counts :16-35): frame i (i + 2 < n_active) joins the set when
+ *    kept < (1 - maximum_share_marginalized) * (kept + gone) and n_active - |set| > minimum_size, serially in i; kept = landmarks that
+ *    are neither outlier nor marginalised + immature landmarks with readyForActivation(), gone = outlier or marginalised landmarks.
+ *  - findFramesToMarginalize (:101-140), only when n_active > maximum_size + |set|: kEps 1e-5, kKeepFramesFromStart 2, kMinFrameAge 1;
+ *    score(r) = sqrt(|t_r - t_last|) * sum over t != r of 1 / (kEps + |t_r - t_t|), r and t over the active frames but the last two, the
+ *    sum in window order; the first r with score > max_score (from 0) wins, and index 0 joins the set when no score exceeds 0 —
+ *    also when every candidate was skipped.  The age test reads camera_frame_ids (the keyframes' frame ids, one per WINDOW frame,
+ *    ids >= 0); NULL = the window's own ids.
+ *  - marginalizeLandmarks (:56-91), when n_active > 2, for every active frame but the last and every landmark that is neither
+ *    marginalised nor outlier: out_of_boundary = the frame is in the set, or the landmark's status towards the last active keyframe is
+ *    not kOk; valid = n_inliers >= (minimum_size + 1) / 2 and successful optimisations > 2 * maximum_size; sufficient = successful
+ *    optimisations > 0.  out_of_boundary and not sufficient: outlier.  Else out_of_boundary or valid: marginalize().
+ *    A landmark without an entry in that connection (the list is shorter than the frame, or there is no connection) counts as not
+ *    kOk; the reference's .at() would throw.
+ *  - ActiveTrackingLandmark::marginalize() (active_tracking_landmark.cpp:55-63) also marks the landmark outlier when
+ *    variance / idepth > 1e-3 or idepth < 0.  As the class observations above, the window reads its own values, in binary64: its
+ *    inverse depth and variance = 1 / H_dd (what updateFrame hands the keyframe with estimate_uncertainty, :252), not the keyframe's
+ *    copies in Precision, which lag for landmarks whose solved inverse depth went negative or below 1e-8 in magnitude.
+ *  - the erase loop (:165-167, ActiveOdometryTrack::marginalizeFrame, src/track/track/src/active_odometry_track.cpp:70-75) erases
+ *    the set's indices in ascending order from a list that shrinks as it goes: the second index of a set hits the frame one place
+ *    later.  `selected` is the set, `marginalized_ids` the frames hit (an index past the end of the shrunken list, undefined in the
+ *    reference, hits nothing).  ActiveKeyframe::marginalize (src/track/frames/src/active_keyframe.cpp:176-184) calls marginalize()
+ *    on EVERY landmark of a frame hit, whatever its flags.
+ * maximum_size (src/marginalization/src/maximum_size_frame_marginalization_strategy.cpp:16-20): marginalizeFrame(0) until
+ * n_active <= maximum_size; `selected` lists the active indices of those oldest frames, no landmark rule but ActiveKeyframe::marginalize.
+ *
+ * immature: one set per WINDOW frame (entries or the array may be NULL: no immature landmarks); their state is read behind
+ * whatever their streams hold.  flags (may be NULL): the new flag byte of every landmark of every window frame, frame after frame in
+ * window order, each frame in the caller's landmark order — bit0 marginalised, bit1 outlier; the frames flagged earlier report
+ * the bits they have.
+ * apply = 0 changes nothing in the window.  apply != 0 leaves the window as one dsopp_hip_window_set_landmarks flag refresh with
+ * those bytes would, for every frame that was active (to_marginalize = newly marginalised and not outlier, assigned for each of them),
+ * followed by dsopp_hip_window_mark_frame_marginalized for the frames in marginalized_ids: updateLocalFrame of monocular_tracker.cpp
+ * :317 and :507.  As in that refresh (PBA_INT/local_frame.hpp:492-497) the outlier bit of a landmark the window already holds only
+ * decides to_marginalize; the window's own outlier flags are the solver's.  A second refresh of those frames would clear
+ * to_marginalize, as it does in the reference.
+ * One launch counts and lets the workgroup that finishes last choose, a second writes the landmarks' flags; nothing waits on the host
+ * in between, and one pinned transfer brings everything back. */
+int dsopp_hip_window_choose_marginalization(dsopp_hip_window *w, const dsopp_hip_marginalization_options *options,
+                                            const int32_t *camera_frame_ids, dsopp_hip_immature_set *const *immature, int32_t apply,
+                                            dsopp_hip_marginalization_result *result, uint8_t *flags);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Two-frame direct image alignment of one pyramid level
  * (replaces EigenPoseAlignment<SE3, PinholeCamera, 1, PixelMap, 1, true>, PROB_SRC/eigen_pose_alignment.cpp:26-329)
