@@ -16,9 +16,8 @@ import test_landmark_activation as tla  # noqa: E402
 def main():
     from dsopp_amd import capi
     from oracle import pyoracle as po
-    tla.W, tla.H = 640, 480
     n_imm = int(os.environ.get("ACT_IMMATURE", "1500"))
-    _, frames, intr = tla.build_case(num_frames=7, per_frame=100 + n_imm, seed=3)
+    _, frames, intr = tla.build_case(num_frames=7, per_frame=100 + n_imm, seed=3, width=640, height=480)
     # build_case keeps 100 active landmarks per keyframe; the timing wants ~286: reuse immature uv as extra actives is not
     # needed for the cost picture (the refinement dominates), so only the counts are reported
     n_imm_total = sum(len(f["immature"]["status"]) for f in frames[:-1])

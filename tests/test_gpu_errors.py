@@ -148,3 +148,55 @@ def test_empty_and_degenerate_inputs_of_the_tracker_side_calls(tiny_window):
     assert r["lm_iterations"] == 0 and not r["success"]
     for o in [a, maps, s_empty, g] + pyrs:
         o.close()
+
+
+def test_activation_refusals_leave_the_window_usable():
+    """dsopp_hip_window_activate_landmarks: every refusal of its argument and state checks comes back with its code, and the same window
+    still activates afterwards exactly as before"""
+    import activation_scenes as asc
+    from dsopp_amd import capi
+    sc = asc.scenes("selection")["counts_small"]
+    frames, intr = sc["frames"], sc["intr"]
+    height, width = frames[-1]["pixelinfo"].shape[:2]
+    g = capi.HipWindow(capi.default_pba_options())
+    sets = asc.load_gpu(g, frames, intr)
+    pyr = asc.newest_pyramid(frames, None, capi.F64)
+    new = frames[-1]
+    call = lambda ids, ss, p, desired=sc["desired"]: g.activate_landmarks(ids, ss, p, new["T_w"], 1.0, (0, 0), desired, sc["dist0"], False)   # noqa: E731
+    before = asc.activate_gpu(g, frames, sets, pyr, sc["desired"], sc["dist0"], False)
+    for s, f in zip(sets, frames[:-1]):
+        s.upload(f["immature"])
+    one_level, other_size, other_type = capi.Pyramid(width, height, 1), capi.Pyramid(width + 2, height, 2), capi.Pyramid(width, height, 2, capi.F32)
+    refusals = [(([], [], pyr), -1, ""),                                         # no keyframe
+                ((list(range(16)), [None] * 16, pyr), -1, "n_keyframes"),        # more than the window can hold beside the newest
+                (([0, 1], sets, pyr, -1), -1, "number_of_desired_points"),       # negative desired count
+                (([1, 0], sets[::-1], pyr), -3, "oldest first"),                 # frames not oldest first
+                (([0, 0], sets, pyr), -3, "oldest first"),                       # ... nor one of them twice
+                (([0, 99], sets, pyr), -2, "not in the window"),                 # unknown frame id
+                (([0, 1], sets, one_level), -1, "level 1"),                      # newest pyramid without the sparsity level
+                (([0, 1], sets, other_size), -1, "does not match"),              # size mismatch
+                (([0, 1], sets, other_type), -1, "does not match")]              # dtype mismatch
+    for args, code, text in refusals:
+        with pytest.raises(capi.HipError) as e:
+            call(*args)
+        assert _code(e) == code and text in str(e.value), (args[0], str(e.value))
+    # a window whose frames are not level-0 frames
+    g1 = capi.HipWindow(capi.default_pba_options())
+    two = capi.Pyramid(width, height, 2)
+    two.set_level(0, new["pixelinfo"])
+    g1.push_frame(0, 1000, None, None, intr / 2, new["T_w"], 1.0, np.zeros(2), True, False, pyramid=two, level=1)
+    g1.set_landmarks(0, np.zeros((0, 2)), np.zeros(0), np.zeros((0, 8)), np.zeros(0, dtype=np.uint8))
+    with pytest.raises(capi.HipError) as e:
+        g1.activate_landmarks([0], [None], pyr, new["T_w"], 1.0, (0, 0), 0, 1.0, False)
+    assert _code(e) == -6 and "level-0" in str(e.value)
+    g1.close()
+    # none of the refusals touched the sets or the window
+    for s, f in zip(sets, frames[:-1]):
+        assert np.array_equal(s.download()["status"], f["immature"]["status"])
+    after = asc.activate_gpu(g, frames, sets, pyr, sc["desired"], sc["dist0"], False)
+    m = asc.model(sc)
+    for a, b, c in zip(before[0], after[0], m.statuses):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+    assert before[2] == after[2] and after[2]["number_of_active_points"] == m.n_active and after[2]["n_activated"] > 0
+    for o in sets + [pyr, one_level, other_size, other_type, two, g]:
+        o.close()

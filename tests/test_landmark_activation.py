@@ -9,51 +9,8 @@ import pytest
 
 from dsopp_amd import synthetic as syn
 
-W, H = 320, 240
-
-
-def _rel(T_w_t, T_w_r):
-    return np.linalg.inv(T_w_t) @ T_w_r
-
-
-def build_case(num_frames=5, per_frame=260, seed=83, observe=True):
-    """a window of `num_frames` keyframes (the last one is the new keyframe without landmarks); the first 100 landmarks of
-    every older keyframe are active, the others immature with the estimator state two depth-estimation passes leave"""
-    from oracle import pyoracle as po
-    win = syn.make_window(num_frames=num_frames, num_points=num_frames * per_frame, width=W, height=H, seed=seed, pose_noise=False,
-                          affine_jitter=True)
-    intr = win.scene.intrinsics
-    rng = np.random.default_rng(seed)
-    frames = []
-    for i, f in enumerate(win.frames):
-        # the images are rendered as exp(a) * texture + b with exposure 1; a non-trivial exposure is folded out of `a` so that
-        # (e_t / e_r) * exp(a_t - a_r) stays the true brightness ratio
-        expo = 1.0 + 0.05 * i
-        d = dict(pixelinfo=f.pixelinfo, mask=None, T_w=syn.mat_to_params(f.T_w_c_gt), exposure=expo,
-                 affine=np.array([f.affine_gt[0] - np.log(expo), f.affine_gt[1]]), syn=f)
-        if i + 1 < num_frames:
-            na = 100
-            d["active_uv"], d["active_idepth"] = f.uv[:na].copy(), f.idepth_init[:na].copy()
-            skip = np.zeros(na, dtype=np.uint8)
-            skip[rng.choice(na, 7, replace=False)] = 1
-            d["active_skip"] = skip
-            d["active_patch"] = f.patch[:na].copy()
-            uv = f.uv[na:]
-            ui, vi = uv[:, 0].astype(int), uv[:, 1].astype(int)
-            grad = np.stack([f.pixelinfo[vi, ui, 1], f.pixelinfo[vi, ui, 2]], axis=1)
-            direction = np.stack([(uv[:, 0] - intr[2]) / intr[0], (uv[:, 1] - intr[3]) / intr[1], np.ones(len(uv))], axis=1)
-            lms = po.new_immature_landmarks(uv, direction, f.patch[na:], grad)
-            if observe:   # two observations from later keyframes give the intervals / uniqueness a realistic spread
-                for j in (i + 1, num_frames - 1):
-                    if j == i or j >= num_frames:
-                        continue
-                    g = win.frames[j]
-                    po.estimate_depths(lms, g.pixelinfo, None, intr, syn.mat_to_params(_rel(g.T_w_c_gt, f.T_w_c_gt)), d["exposure"], d["affine"],
-                                       1.0 + 0.05 * j, np.array([g.affine_gt[0] - np.log(1.0 + 0.05 * j), g.affine_gt[1]]))
-            d["immature"] = lms
-            d["idepth_gt"] = f.idepth_gt[na:].copy()
-        frames.append(d)
-    return win, frames, intr
+from activation_scenes import H, W, _rel, build_case
+from activation_scenes import run_gpu as _run_gpu
 
 
 def _reproject_half(intr, T, uv, rho):
@@ -178,39 +135,6 @@ def test_masks_delete_and_block(case):
     st_0, _, _ = po.activate_landmarks(copy.deepcopy(frames), intr, 20.0, 372, 1.2, refine=True)
     a, b = np.concatenate(st_m), np.concatenate(st_0)
     assert (a == 2).sum() > (b == 2).sum() + 10   # candidates that land on the masked corner are deleted (:112-115)
-
-
-def _run_gpu(frames, intr, ms, desired, dist0, refine, dtype=None):
-    from dsopp_amd import capi
-    opts = capi.default_pba_options()
-    if dtype is not None:
-        opts.dtype = dtype
-    g = capi.HipWindow(opts)
-    sets = []
-    for i, f in enumerate(frames[:-1]):
-        g.push_frame(i, 1000 * (i + 1), f["pixelinfo"], f.get("mask"), intr, f["T_w"], f["exposure"], f["affine"], i == 0, False)
-        g.set_landmarks(i, f["active_uv"], f["active_idepth"], f["active_patch"], (f["active_skip"] * (1 + (np.arange(len(f["active_skip"])) % 2))).astype(np.uint8))
-        s = capi.ImmatureSet(f["immature"])
-        s.upload(f["immature"])
-        sets.append(s)
-    for i in range(len(frames) - 1):
-        for j in range(len(frames) - 1):
-            if i != j:
-                g.set_connection(i, j, np.zeros(len(frames[i]["active_idepth"]), dtype=np.uint8))
-    new = frames[-1]
-    pyr = capi.Pyramid(W, H, 2, opts.dtype)
-    pyr.set_level(0, new["pixelinfo"])
-    if new.get("mask") is not None:
-        pyr.set_mask(0, new["mask"])
-    if ms is not None:
-        pyr.set_mask(1, ms)
-    st, idp, res = g.activate_landmarks(list(range(len(frames) - 1)), sets, pyr, new["T_w"], new["exposure"], new["affine"], desired, dist0, refine)
-    states = [s.download() for s in sets]
-    for s in sets:
-        s.close()
-    pyr.close()
-    g.close()
-    return st, idp, res, states
 
 
 @pytest.mark.gpu
