@@ -169,6 +169,9 @@ SYMBOLS = [
     "dsopp_hip_two_view_ransac_destroy", "dsopp_hip_two_view_ransac_estimate", "dsopp_hip_two_view_ransac_triangulate",
     "dsopp_hip_window_note_optimization", "dsopp_hip_window_get_optimization_counts", "dsopp_hip_marginalization_default_options",
     "dsopp_hip_window_choose_marginalization",
+    "dsopp_hip_debug_views_create", "dsopp_hip_debug_views_destroy", "dsopp_hip_debug_views_frame", "dsopp_hip_debug_views_frame_device",
+    "dsopp_hip_debug_views_keyframe", "dsopp_hip_debug_views_keyframe_device", "dsopp_hip_debug_views_keyframe_planes",
+    "dsopp_hip_debug_views_get_maximum_idepth", "dsopp_hip_debug_views_set_maximum_idepth",
 ]
 
 _lib = None
@@ -1018,6 +1021,81 @@ class DepthMaps:
         ids, wgt = np.zeros((h, w)), np.zeros((h, w))
         _chk(lib().dsopp_hip_depth_maps_get_level(self._h, int(level), _p(ids), _p(wgt)))
         return ids, wgt
+
+
+class DebugViews:
+    """The tracker's two debug views on the device (dsopp_hip_debug_views): debugCurrentFrame and debugCurrentKeyframe as (height, width, 3)
+    uint8 BGR images.  colormap = 256 x {B, G, R} (None = the library's jet), stencil = 7 x 7 bytes, a circle's footprint (None = radius 3)."""
+
+    def __init__(self, width, height, colormap=None, stencil=None, device=0, stream=None):
+        self._h = C.c_void_p()
+        self.width, self.height, self.device = int(width), int(height), device
+        cm, st = _u8(colormap), _u8(stencil)
+        assert cm is None or cm.size == 768, cm.shape
+        assert st is None or st.size == 49, st.shape
+        _chk(lib().dsopp_hip_debug_views_create(int(device), C.c_void_p(stream or 0), self.width, self.height, _p(cm, np.uint8), _p(st, np.uint8),
+                                                C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_debug_views_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _grey(self, grey):
+        g = _u8(grey)
+        assert g is None or g.shape == (self.height, self.width), g.shape
+        return g
+
+    def _out(self):
+        return np.zeros((self.height, self.width, 3), dtype=np.uint8)
+
+    def frame(self, pyramid: "Pyramid", grey=None):
+        """debugCurrentFrame: the pyramid's kept grey image (or `grey`) and its level-0 mask -> BGR; blocking"""
+        out = self._out()
+        _chk(lib().dsopp_hip_debug_views_frame(self._h, pyramid._h if pyramid is not None else None, _p(self._grey(grey), np.uint8), _p(out, np.uint8)))
+        return out
+
+    def frame_device(self, grey_ptr, mask_ptr, bgr_out_ptr, stream=None):
+        """the same between device buffers (addresses as integers; mask_ptr None = all valid); only enqueues"""
+        _chk(lib().dsopp_hip_debug_views_frame_device(self._h, C.c_void_p(grey_ptr or 0), C.c_void_p(mask_ptr or 0), C.c_void_p(bgr_out_ptr or 0),
+                                                      C.c_void_p(stream or 0)))
+
+    def keyframe(self, pyramid: "Pyramid", maps: "DepthMaps", grey=None):
+        """debugCurrentKeyframe over level 0 of device-resident maps -> (BGR, the new maximum idepth, qualifying cells); blocking"""
+        out, M, cells = self._out(), C.c_double(), C.c_int64()
+        _chk(lib().dsopp_hip_debug_views_keyframe(self._h, pyramid._h if pyramid is not None else None, _p(self._grey(grey), np.uint8),
+                                                  maps._h if maps is not None else None, _p(out, np.uint8), C.byref(M), C.byref(cells)))
+        return out, M.value, cells.value
+
+    def keyframe_device(self, grey_ptr, maps: "DepthMaps", bgr_out_ptr, stream=None):
+        """the same from a device grey image into a device BGR image; only enqueues; maximum_idepth waits for it"""
+        _chk(lib().dsopp_hip_debug_views_keyframe_device(self._h, C.c_void_p(grey_ptr or 0), maps._h if maps is not None else None,
+                                                         C.c_void_p(bgr_out_ptr or 0), C.c_void_p(stream or 0)))
+
+    def keyframe_planes(self, grey, idepth_sum, weight):
+        """the same from two host planes in DepthMaps.get_level's layout; blocking"""
+        ids, wgt = _f64(idepth_sum), _f64(weight)
+        assert ids.shape == wgt.shape == (self.height, self.width), (ids.shape, wgt.shape)
+        out, M, cells = self._out(), C.c_double(), C.c_int64()
+        _chk(lib().dsopp_hip_debug_views_keyframe_planes(self._h, _p(self._grey(grey), np.uint8), _p(ids), _p(wgt), _p(out, np.uint8), C.byref(M),
+                                                         C.byref(cells)))
+        return out, M.value, cells.value
+
+    @property
+    def maximum_idepth(self):
+        M = C.c_double()
+        _chk(lib().dsopp_hip_debug_views_get_maximum_idepth(self._h, C.byref(M)))
+        return M.value
+
+    @maximum_idepth.setter
+    def maximum_idepth(self, value):
+        _chk(lib().dsopp_hip_debug_views_set_maximum_idepth(self._h, C.c_double(value)))
 
 
 class Comm:

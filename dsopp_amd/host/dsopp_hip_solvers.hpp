@@ -389,6 +389,47 @@ class DeviceDepthMaps {
   dsopp_hip_depth_maps *m_;
 };
 
+/** The two images MonocularTracker::tick pushes to its camera_output_interface_, rendered on the device as interleaved 8-bit BGR:
+ *  frame() stands where debugCurrentFrame(features) is called (monocular_tracker.cpp:485-487), keyframe() where
+ *  debugCurrentKeyframe(features, reference_frame_depth_map_[0], maximum_visualized_idepth_) is (:511-514).  The object holds
+ *  maximum_visualized_idepth_ (one per tracker); the depth maps are read where they lie.  A caller that links OpenCV passes its JET table
+ *  (cv::applyColorMap of a 0 .. 255 ramp) and its radius-3 circle (cv::circle on a 7 x 7 image); nullptr = the library's own. */
+class HipDebugViews {
+ public:
+  HipDebugViews(int width, int height, const uint8_t *colormap_bgr256 = nullptr, const uint8_t *stencil7x7 = nullptr, int device = 0,
+                void *stream = nullptr)
+      : width_(width), height_(height) {
+    check(dsopp_hip_debug_views_create(device, stream, width, height, colormap_bgr256, stencil7x7, &v_));
+  }
+  ~HipDebugViews() { dsopp_hip_debug_views_destroy(v_); }
+  HipDebugViews(const HipDebugViews &) = delete;
+  HipDebugViews &operator=(const HipDebugViews &) = delete;
+  /** debugCurrentFrame: the grey image the pyramid keeps, red where its level-0 mask is 0; height x width x 3 bytes.  Blocking. */
+  std::vector<uint8_t> frame(const DevicePyramid &pyramid) {
+    std::vector<uint8_t> bgr(size());
+    check(dsopp_hip_debug_views_frame(v_, pyramid.handle(), nullptr, bgr.data()));
+    return bgr;
+  }
+  /** debugCurrentKeyframe: the kept grey image under the jet-coloured circles of level 0 of `maps`; updates maximumIdepth().  Blocking. */
+  std::vector<uint8_t> keyframe(const DevicePyramid &pyramid, const DeviceDepthMaps &maps) {
+    std::vector<uint8_t> bgr(size());
+    check(dsopp_hip_debug_views_keyframe(v_, pyramid.handle(), nullptr, maps.handle(), bgr.data(), nullptr, nullptr));
+    return bgr;
+  }
+  /** maximum_visualized_idepth_ (0 = not set yet) */
+  double maximumIdepth() const {
+    double m = 0;
+    check(dsopp_hip_debug_views_get_maximum_idepth(v_, &m));
+    return m;
+  }
+  dsopp_hip_debug_views *handle() const { return v_; }
+
+ private:
+  size_t size() const { return 3 * static_cast<size_t>(width_) * static_cast<size_t>(height_); }
+  int width_, height_;
+  dsopp_hip_debug_views *v_ = nullptr;
+};
+
 class HipPhotometricBundleAdjustment {
  public:
   /** EigenPhotometricBundleAdjustment(options, estimate_uncertainty, force_accept) — eigen_photometric_bundle_adjustment.cpp:47-57 */

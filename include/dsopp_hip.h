@@ -1507,6 +1507,74 @@ int dsopp_hip_aligner_set_hypothesis_width(dsopp_hip_aligner *a, int32_t width);
 int dsopp_hip_aligner_set_lm_path(dsopp_hip_aligner *a, int path);
 int dsopp_hip_aligner_num_points(dsopp_hip_aligner *a, int32_t *n);
 
+/* ---- the tracker's debug views (row o-1) ----
+ * The two images MonocularTracker::tick pushes to its camera_output_interface_ (the viewer), as interleaved 8-bit BGR of width x height:
+ *   debugCurrentFrame(features), every frame                                   src/tracker/tracker/src/monocular_tracker.cpp:323-333, 485-487
+ *   debugCurrentKeyframe(features, depth_map[0], maximum_visualized_idepth_)   src/tracker/tracker/src/monocular_tracker.cpp:335-374, 511-514
+ * The arithmetic is stated here as the library's own (parity with OpenCV's circle rasteriser and colour table is NOT pinned: both are
+ * creation parameters, see below).  tests/debug_views_model.py is the NumPy statement the kernels are held to byte for byte.
+ *
+ * Frame view.  g = the grey byte, m = (the level-0 mask byte is 0; a pyramid's mask lane is 0).  BGR = (g, g, g) where !m and
+ * (max(g - 128, 0), max(g - 128, 0), g) where m: `debug - ((mask == 0) - Scalar(0, 0, 255)) / 2` in saturating 8-bit arithmetic with
+ * 127.5 rounded to 128.  Without a mask every pixel is valid and the view is plain grey.
+ *
+ * Keyframe view, over the level-0 map {idepth_sum, weight} (two row-major height x width planes, as dsopp_hip_depth_maps_get_level
+ * returns them) and the state M (the tracker's maximum_visualized_idepth_, 0 = unset, 0 at creation):
+ *   1 the cells with idepth_sum > 0 qualify; q = idepth_sum / weight; avg = (sum of q) / cells.  (A map the library fills has weight > 0
+ *     wherever idepth_sum > 0; a caller's cell with idepth_sum > 0 and weight 0 has q = inf, as in the reference.)  The sum is taken in a
+ *     FIXED order, whatever the device does: with i = y * width + x and q = 0.0 for a cell that does not qualify,
+ *       chunk b (4096 cells), thread t < 256:  s = 0; for k = 0 .. 15: s += q[4096 b + 256 k + t]
+ *       64 consecutive threads (a wave):       for off = 32, 16, 8, 4, 2, 1: s[l] += s[l + off], l < off; the wave's sum is s[0]
+ *       the chunk:                             ((wave 0 + wave 1) + wave 2) + wave 3
+ *     and the chunks' sums are added the same way: thread j < 256 adds chunks j, j + 256, j + 512, ... in that order, then the waves and
+ *     the four wave sums as above.
+ *   2 if M == 0: M = 2 avg.  Then M = 0.9 M + 0.1 (2 avg): binary64, single operations, the two products first.
+ *   3 a qualifying cell's level = rint(clamp((255 q) / M, 0, 255)) with the NEW M: half to even, a NaN gives 0.
+ *   4 the cells are painted in raster order (y outer, x inner), each as the stencil's footprint around (x, y), clipped to the image,
+ *     later over earlier.  (The device gathers instead: a pixel p takes, among the cells p - offset of the set stencil taps, the
+ *     occupied one with the largest (y, x) — the same image, in any execution order.)
+ *   5 a covered pixel is colormap[level of the last footprint over it], every other pixel (g, g, g).
+ * With NO qualifying cell the reference divides 0 by 0 and its M is NaN from then on.  The library instead leaves M as it is, returns the
+ * plain grey view and reports cells = 0.
+ *
+ * create: colormap_bgr = 256 x {B, G, R}, the colour of every level; NULL = the library's jet, x = v / 255,
+ *   r = clamp(1.5 - |4 x - 3|, 0, 1), g = clamp(1.5 - |4 x - 2|, 0, 1), b = clamp(1.5 - |4 x - 1|, 0, 1), each channel rint(255 c)
+ * — NOT claimed to be OpenCV's COLORMAP_JET table: a caller that links OpenCV passes cv::applyColorMap of a 0 .. 255 ramp.
+ * stencil = 7 x 7 bytes, a circle's footprint: a nonzero byte at (dy + 3, dx + 3) means the circle at c covers c + (dx, dy); NULL =
+ * dx^2 + dy^2 <= 9 (29 pixels); need not be symmetric (a caller that links OpenCV passes one cv::circle of radius 3 on a 7 x 7 image).
+ * `stream` NULL = a stream of the object's own.  All buffers are sized here from width x height; only the staging planes of
+ * keyframe_planes are allocated by its first call.
+ *
+ * frame: blocking.  Reads the 8-bit grey image `pyramid` keeps (the one dsopp_hip_pyramid_get_image(p, 1, ...) returns) and the mask lane
+ * of its level-0 texels behind the pyramid's stream; grey_host, unless NULL, is width * height bytes that replace the kept image.
+ * frame_device: enqueues only, on `stream` (NULL = the object's); mask_dev NULL = all valid; bgr_out_dev must be 4-byte aligned.
+ * keyframe: blocking.  Reads level 0 of `maps` where it lies (the planes are never copied to the host), ordered behind the pyramid's and
+ * the maps' streams by events; grey_host as for frame.  maximum_idepth and cells (either may be NULL) receive the new M and the number
+ * of qualifying cells.
+ * keyframe_device: enqueues only (both launches), ordered behind the maps' stream and, on another stream than the object's previous
+ * keyframe view, behind that view (they share M and the partial sums); the new M is read with get_maximum_idepth, which waits for it.
+ * keyframe_planes: blocking; the two planes from the host in the layout dsopp_hip_depth_maps_get_level returns, for callers whose maps
+ * live on the host and for exact test inputs; the same kernels.
+ * get_ / set_maximum_idepth: the state M (set 0 for "unset"); both wait for a keyframe view in flight.
+ * One thread drives an object at a time.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: a NULL handle, image or output, a pyramid or maps of another size or on another device than the object,
+ * a pyramid that keeps no grey image while grey_host is NULL, a stencil whose centre byte is 0, an unaligned device output, width or
+ * height < 1 or more than 2^31 - 1 pixels.  There is no CPU path: without a device create fails with DSOPP_HIP_ERR_HIP. */
+typedef struct dsopp_hip_debug_views dsopp_hip_debug_views;
+int dsopp_hip_debug_views_create(int device, void *stream, int width, int height, const uint8_t *colormap_bgr, const uint8_t *stencil,
+                                 dsopp_hip_debug_views **out);
+void dsopp_hip_debug_views_destroy(dsopp_hip_debug_views *v);
+int dsopp_hip_debug_views_frame(dsopp_hip_debug_views *v, const dsopp_hip_pyramid *pyramid, const uint8_t *grey_host, uint8_t *bgr_out_host);
+int dsopp_hip_debug_views_frame_device(dsopp_hip_debug_views *v, const void *grey_dev, const void *mask_dev, void *bgr_out_dev, void *stream);
+int dsopp_hip_debug_views_keyframe(dsopp_hip_debug_views *v, const dsopp_hip_pyramid *pyramid, const uint8_t *grey_host,
+                                   const dsopp_hip_depth_maps *maps, uint8_t *bgr_out_host, double *maximum_idepth, int64_t *cells);
+int dsopp_hip_debug_views_keyframe_device(dsopp_hip_debug_views *v, const void *grey_dev, const dsopp_hip_depth_maps *maps, void *bgr_out_dev,
+                                          void *stream);
+int dsopp_hip_debug_views_keyframe_planes(dsopp_hip_debug_views *v, const uint8_t *grey_host, const double *idepth_sum_host,
+                                          const double *weight_host, uint8_t *bgr_out_host, double *maximum_idepth, int64_t *cells);
+int dsopp_hip_debug_views_get_maximum_idepth(dsopp_hip_debug_views *v, double *maximum_idepth);
+int dsopp_hip_debug_views_set_maximum_idepth(dsopp_hip_debug_views *v, double maximum_idepth);
+
 #ifdef __cplusplus
 }
 #endif
