@@ -77,6 +77,15 @@ class MarginalizationResult(C.Structure):
                 ("n_newly_marginalized", C.c_int32), ("n_newly_outlier", C.c_int32)]
 
 
+class MapOptions(C.Structure):
+    _fields_ = [("estimate_uncertainty", C.c_int32), ("channels", C.c_int32), ("min_relative_baseline", C.c_double)]
+
+
+class MapExportOptions(C.Structure):
+    _fields_ = [("classes", C.c_int32), ("apply_filters", C.c_int32), ("max_idepth_variance", C.c_double),
+                ("min_relative_baseline_filter", C.c_double), ("frame", C.c_int32), ("colours", C.c_int32)]
+
+
 class GeometricBAProblem(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
                 ("num_frames", C.c_int32), ("num_landmarks", C.c_int32), ("num_observations", C.c_int32), ("reserved", C.c_int32),
@@ -172,6 +181,9 @@ SYMBOLS = [
     "dsopp_hip_debug_views_create", "dsopp_hip_debug_views_destroy", "dsopp_hip_debug_views_frame", "dsopp_hip_debug_views_frame_device",
     "dsopp_hip_debug_views_keyframe", "dsopp_hip_debug_views_keyframe_device", "dsopp_hip_debug_views_keyframe_planes",
     "dsopp_hip_debug_views_get_maximum_idepth", "dsopp_hip_debug_views_set_maximum_idepth",
+    "dsopp_hip_map_default_options", "dsopp_hip_map_default_export_options", "dsopp_hip_map_create", "dsopp_hip_map_destroy",
+    "dsopp_hip_map_add_keyframe", "dsopp_hip_map_update", "dsopp_hip_map_set_records", "dsopp_hip_map_set_pose", "dsopp_hip_map_num_keyframes",
+    "dsopp_hip_map_keyframe_ids", "dsopp_hip_map_num_records", "dsopp_hip_map_get_records", "dsopp_hip_map_export", "dsopp_hip_map_export_device",
 ]
 
 _lib = None
@@ -244,6 +256,15 @@ def default_marginalization_options(**kw) -> MarginalizationOptions:
     o = MarginalizationOptions()
     lib().dsopp_hip_marginalization_default_options(C.byref(o))
     for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_map_options(**kw) -> MapOptions:
+    o = MapOptions()
+    lib().dsopp_hip_map_default_options(C.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
         setattr(o, k, v)
     return o
 
@@ -1096,6 +1117,129 @@ class DebugViews:
     @maximum_idepth.setter
     def maximum_idepth(self, value):
         _chk(lib().dsopp_hip_debug_views_set_maximum_idepth(self._h, C.c_double(value)))
+
+
+class Map:
+    """The map on the device (dsopp_hip_map): keyframe landmark records that outlive the window, exported as a filtered, coloured point
+    cloud.  include/dsopp_hip.h states the rules; tests/point_cloud_model.py is their NumPy statement."""
+    FLAG_MARGINALIZED, FLAG_OUTLIER = 1, 2
+    CLASS_ACTIVE, CLASS_MARGINALIZED, CLASS_OUTLIER = 1, 2, 4
+    FRAME_KEYFRAME, FRAME_WORLD = 0, 1
+    COLOURS_LANDMARK_TYPE, COLOURS_CONSTANT, COLOURS_SEMANTIC, COLOURS_IMAGE = 0, 1, 2, 3
+    OUTPUTS = (("xyz", np.float64, 3), ("rgb", np.uint8, 3), ("type", np.uint8, 1), ("relative_baseline", np.float64, 1),
+               ("idepth_variance", np.float64, 1), ("keyframe_index", np.int32, 1), ("record_index", np.int32, 1))
+
+    def __init__(self, options: "MapOptions | None" = None, device=0, stream=None, **option_fields):
+        self._h = C.c_void_p()
+        self.options = options or default_map_options(**option_fields)
+        self.device = device
+        _chk(lib().dsopp_hip_map_create(int(device), C.c_void_p(stream or 0), C.byref(self.options), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().dsopp_hip_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _window(window):
+        if not isinstance(window, HipWindow):  # (a HipWindowGroup has no single window behind it: the group form is not built)
+            raise HipError(f"dsopp_hip error -1: a map takes a HipWindow, not a {type(window).__name__}")
+        return window._h
+
+    def add_keyframe(self, window: "HipWindow", frame_id, pyramid: "Pyramid | None" = None):
+        """after window.push_frame(frame_id, ...): a live keyframe; the pyramid's kept 8-bit image (colour before grey) is copied"""
+        _chk(lib().dsopp_hip_map_add_keyframe(self._h, self._window(window), int(frame_id), pyramid._h if pyramid is not None else None))
+
+    def update(self, window: "HipWindow", weights=None):
+        """one launch over the landmarks of all window frames the map knows; keyframes the window dropped are finalised; only enqueues"""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        assert w is None or w.size == 256, w.shape
+        _chk(lib().dsopp_hip_map_update(self._h, self._window(window), _p(w, np.uint64)))
+
+    def set_records(self, frame_id, intrinsics, T_world_agent, uv, idepth, variance, relative_baseline, flags, type=None, rgb=None):
+        """loads or replaces a finalised keyframe from host arrays"""
+        n = len(idepth)
+        uv, idepth, variance, rb = _f64(uv), _f64(idepth), _f64(variance), _f64(relative_baseline)
+        flags, type, rgb = _u8(flags), _u8(type), _u8(rgb)
+        assert uv.size == 2 * n and variance.size == n and rb.size == n and flags.size == n, (uv.shape, n)
+        assert (type is None or type.size == n) and (rgb is None or rgb.size == 3 * n)
+        _chk(lib().dsopp_hip_map_set_records(self._h, int(frame_id), _p(_f64(intrinsics)), _p(_f64(T_world_agent)), n, _p(uv), _p(idepth), _p(variance),
+                                             _p(rb), _p(flags, np.uint8), _p(type, np.uint8), _p(rgb, np.uint8)))
+
+    def set_pose(self, frame_id, T_world_agent):
+        _chk(lib().dsopp_hip_map_set_pose(self._h, int(frame_id), _p(_f64(T_world_agent))))
+
+    @property
+    def num_keyframes(self) -> int:
+        n = C.c_int32()
+        _chk(lib().dsopp_hip_map_num_keyframes(self._h, C.byref(n)))
+        return n.value
+
+    def keyframe_ids(self):
+        cap = max(1, self.num_keyframes)
+        ids, n = np.zeros(cap, dtype=np.int32), C.c_int32()
+        _chk(lib().dsopp_hip_map_keyframe_ids(self._h, cap, _p(ids, np.int32), C.byref(n)))
+        return [int(x) for x in ids[:min(n.value, cap)]]
+
+    def num_records(self, frame_id) -> int:
+        n = C.c_int32()
+        _chk(lib().dsopp_hip_map_num_records(self._h, int(frame_id), C.byref(n)))
+        return n.value
+
+    def records(self, frame_id):
+        """one keyframe's raw records: dict(uv, idepth, variance, relative_baseline, flags, type, rgb, intrinsics, pose, has_image,
+        finalised); blocking"""
+        n = self.num_records(frame_id)
+        out = dict(uv=np.zeros((n, 2)), idepth=np.zeros(n), variance=np.zeros(n), relative_baseline=np.zeros(n), flags=np.zeros(n, dtype=np.uint8),
+                   type=np.zeros(n, dtype=np.uint8), rgb=np.zeros((n, 3), dtype=np.uint8), intrinsics=np.zeros(4), pose=np.zeros(7))
+        state = np.zeros(2, dtype=np.int32)
+        _chk(lib().dsopp_hip_map_get_records(self._h, int(frame_id), _p(out["uv"]), _p(out["idepth"]), _p(out["variance"]), _p(out["relative_baseline"]),
+                                             _p(out["flags"], np.uint8), _p(out["type"], np.uint8), _p(out["rgb"], np.uint8), _p(out["intrinsics"]),
+                                             _p(out["pose"]), _p(state, np.int32)))
+        out["has_image"], out["finalised"] = bool(state[0]), bool(state[1])
+        return out
+
+    @staticmethod
+    def export_options(**fields) -> "MapExportOptions":
+        o = MapExportOptions()
+        lib().dsopp_hip_map_default_export_options(C.byref(o))
+        for k, v in fields.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def export_raw(self, options, frame_ids, capacity, outputs, count=True, per_keyframe_counts=None, device=False):
+        """dsopp_hip_map_export / _export_device as they are: `outputs` maps the names of OUTPUTS to arrays (device=True: to addresses);
+        returns (return code, count or None)"""
+        ids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32)
+        n = C.c_int64(-1)
+        args = [outputs.get(name) for name, _, _ in self.OUTPUTS]
+        args = [C.c_void_p(a or 0) for a in args] if device else [None if a is None else a.ctypes.data_as(C.c_void_p) for a in args]
+        fn = lib().dsopp_hip_map_export_device if device else lib().dsopp_hip_map_export
+        rc = fn(self._h, C.byref(options) if options is not None else None, 0 if ids is None else len(ids), _p(ids, np.int32), C.c_int64(int(capacity)),
+                *args, C.byref(n) if count else None, _p(per_keyframe_counts, np.int32))
+        return rc, (n.value if count else None)
+
+    def export(self, frame_ids=None, outputs=None, options: "MapExportOptions | None" = None, **option_fields):
+        """the records that pass, packed, in the canonical order: dict of NumPy arrays (the names of OUTPUTS, all of them unless
+        `outputs` lists some), count and per_keyframe_counts; blocking"""
+        o = options or self.export_options(**option_fields)
+        ids = self.keyframe_ids() if frame_ids is None else [int(i) for i in frame_ids]
+        capacity = sum(self.num_records(i) for i in ids)
+        wanted = [name for name, _, _ in self.OUTPUTS] if outputs is None else list(outputs)
+        arrays = {name: np.zeros((capacity, k) if k > 1 else capacity, dtype=dt) for name, dt, k in self.OUTPUTS if name in wanted}
+        per_kf = np.zeros(max(1, len(ids)), dtype=np.int32)
+        rc, n = self.export_raw(o, None if frame_ids is None else ids, capacity, arrays, per_keyframe_counts=per_kf)
+        _chk(rc)
+        out = {name: a[:n] for name, a in arrays.items()}
+        out["count"], out["per_keyframe_counts"] = n, per_kf[:len(ids)]
+        return out
 
 
 class Comm:

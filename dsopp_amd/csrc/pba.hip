@@ -22,6 +22,7 @@
 #include "immature_set.hpp"
 #include "semantic_observation_kernels.hpp"
 #include "marginalization.hpp"
+#include "point_cloud.hpp"
 
 namespace dsopp_hip {
 namespace {
@@ -3324,6 +3325,41 @@ int dsopp_hip_window_get_semantic_types(dsopp_hip_window *w, int32_t frame_id, c
     w->sr.sync();
   });
 }
+
+}  // extern "C"
+
+namespace dsopp_hip {
+/** the window as dsopp_hip_map_add_keyframe / _update read it (point_cloud.hpp) */
+void mapWindowView(dsopp_hip_window *w, MapWindowView &view) {
+  if (!w) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null window");
+  if (w->allreduce && w->world > 1)
+    fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the window holds one landmark shard of %d: a map takes a whole window, not a window group's", w->world);
+  w->sr.use();
+  flushAppends(*w);
+  downloadState(*w);
+  view.device = w->sr.device;
+  view.stream = w->sr.stream;
+  view.n_frames = w->F();
+  for (int s = 0; s < view.n_frames; ++s) {
+    HostFrame &f = *w->frames[static_cast<size_t>(s)];
+    MapWindowFrame &m = view.frame[s];
+    m.id = f.id;
+    m.n = f.n;
+    for (int i = 0; i < 4; ++i) m.intr[i] = f.intr[i];
+    rigidToParams(poseOf(*w, s), m.T_world_agent);
+    m.uv = f.uv.ptr;
+    m.idepth = f.idepth.ptr;
+    m.inv_hdd = f.inv_hdd.ptr;
+    m.relative_baseline = f.relative_baseline.ptr;
+    m.flags = f.dflags.ptr;
+    m.to_internal = f.permuted() ? f.d_to_internal.ptr : nullptr;
+    if (f.sem_hist.ptr && f.n > 0) ensureSemanticRows(*w, f);
+    m.sem_hist = f.sem_hist.ptr;
+  }
+}
+}  // namespace dsopp_hip
+
+extern "C" {
 
 int dsopp_hip_window_get_marginalized(dsopp_hip_window *w, double *H, double *b, double *energy, int32_t *size) {
   return guarded([&] {

@@ -10,11 +10,11 @@
 #pragma once
 #include "device_geom.hpp"
 #include "pba_kernels.hpp"
+#include "semantic_type.hpp"
 
 namespace dsopp_hip {
 
 constexpr int kSemBlock = 256;
-constexpr int kSemClasses = 256;
 
 /** one direction (reference -> target) of a frame pair */
 struct SemPartner {
@@ -82,31 +82,7 @@ __global__ void __launch_bounds__(kSemBlock) semanticTypesKernel(const uint8_t *
                                                                  uint8_t *__restrict__ type) {
   const int c = static_cast<int>(blockIdx.x) * kSemBlock + static_cast<int>(threadIdx.x);
   if (c >= n) return;
-  const uint4 *row = reinterpret_cast<const uint4 *>(hist + static_cast<size_t>(c) * kSemClasses);
-  unsigned best_count = 0, best_i = 0;              // std::max_element: the first maximal count
-  unsigned long long best_w = 0;                    // max_weight, max_weight_element
-  unsigned best_wi = 0;
-  for (int q = 0; q < kSemClasses / 16; ++q) {
-    const uint4 w4 = row[q];
-    const unsigned words[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      const unsigned i = static_cast<unsigned>(16 * q + b);
-      const unsigned count = (words[b >> 2] >> (8 * (b & 3))) & 255u;
-      if (count > best_count) {
-        best_count = count;
-        best_i = i;
-      }
-      if (weights) {
-        const unsigned long long wgt = count * weights[i];  // size_t arithmetic, as the reference
-        if (wgt > best_w) {
-          best_w = wgt;
-          best_wi = i;
-        }
-      }
-    }
-  }
-  type[c] = static_cast<uint8_t>((weights && best_w != 0) ? best_wi : best_i);
+  type[c] = semanticTypeOfRow(hist + static_cast<size_t>(c) * kSemClasses, weights);
 }
 
 }  // namespace dsopp_hip

@@ -1100,6 +1100,124 @@ class HipFrameMarginalizationStrategy {
   dsopp_hip_marginalization_result last_{};
 };
 
+/** storage::PointStorageType and one class of storage::PointsStorage (the viewer's input, one sensor): what Frame::buildPoints fills
+ *  (src/track/frames/src/frame.cpp:190-216) */
+enum class PointStorageType { kActive = DSOPP_HIP_MAP_CLASS_ACTIVE, kMarginalized = DSOPP_HIP_MAP_CLASS_MARGINALIZED, kOutlier = DSOPP_HIP_MAP_CLASS_OUTLIER };
+struct PointsStorage {
+  std::vector<std::array<double, 3>> points;                                   // keyframe-local: direction / idepth
+  std::vector<std::array<uint8_t, 3>> colors, default_colors, semantics_colors;  // getColor(landmark, true, false) | (false, false) | (false, true)
+  std::vector<double> idepth_variances, relative_baselines;
+};
+
+/** a packed export of the map (dsopp_hip_map_export) */
+struct PointCloud {
+  std::vector<std::array<double, 3>> xyz;
+  std::vector<std::array<uint8_t, 3>> rgb;
+  std::vector<uint8_t> type;
+  std::vector<double> relative_baseline, idepth_variance;
+  std::vector<int32_t> keyframe_index, record_index, per_keyframe_counts;
+};
+
+/** The track's side of the map on the device: the ActiveTrackingLandmark records of every keyframe, kept where the bundle adjustment
+ *  leaves them and for good once the keyframe left the window, and their point cloud — what Frame::buildPoints hands the viewer
+ *  (points()) and what pydsopp/utils/point_cloud_exporter.py writes (exportWorld()).  Call order of a keyframe step:
+ *    solver.pushFrame(new keyframe); map.addKeyframe(solver, id, &pyramid); ... solver.solve(); map.update(solver);
+ *    strategy.marginalize(track); map.update(solver);   (then the next pushFrame, which erases the marginalised keyframes) */
+class HipMap {
+ public:
+  explicit HipMap(bool estimate_uncertainty = true, int channels = 1, double min_relative_baseline = 0.1, int device = 0, void *stream = nullptr) {
+    dsopp_hip_map_options o;
+    dsopp_hip_map_default_options(&o);
+    o.estimate_uncertainty = estimate_uncertainty ? 1 : 0;
+    o.channels = channels;
+    o.min_relative_baseline = min_relative_baseline;
+    check(dsopp_hip_map_create(device, stream, &o, &m_));
+  }
+  ~HipMap() { dsopp_hip_map_destroy(m_); }
+  HipMap(const HipMap &) = delete;
+  HipMap &operator=(const HipMap &) = delete;
+  /** after solver.pushFrame of that keyframe; the pyramid's kept 8-bit image (colour before grey) is copied, nullptr = no image colours */
+  void addKeyframe(const HipPhotometricBundleAdjustment &solver, int32_t keyframe_id, const DevicePyramid *pyramid = nullptr) {
+    check(dsopp_hip_map_add_keyframe(m_, window(solver), keyframe_id, pyramid ? pyramid->handle() : nullptr));
+  }
+  /** the landmark half of updateFrame for every keyframe of the window at once (photometric_bundle_adjustment.cpp:223-263), on the device;
+   *  legend_weights = SemanticLegend::weights_ (256) or nullptr */
+  void update(const HipPhotometricBundleAdjustment &solver, const uint64_t *legend_weights = nullptr) {
+    check(dsopp_hip_map_update(m_, window(solver), legend_weights));
+  }
+  void setPose(int32_t keyframe_id, const Motion &t_world_agent) { check(dsopp_hip_map_set_pose(m_, keyframe_id, t_world_agent.data())); }
+  std::vector<int32_t> keyframeIds() const {
+    int32_t n = 0;
+    check(dsopp_hip_map_num_keyframes(m_, &n));
+    std::vector<int32_t> ids(static_cast<size_t>(std::max(n, 1)));
+    check(dsopp_hip_map_keyframe_ids(m_, n, ids.data(), &n));
+    ids.resize(static_cast<size_t>(n));
+    return ids;
+  }
+  int32_t numRecords(int32_t keyframe_id) const {
+    int32_t n = 0;
+    check(dsopp_hip_map_num_records(m_, keyframe_id, &n));
+    return n;
+  }
+  /** the packed export of `keyframe_ids` (empty = every keyframe, in insertion order) under `options` */
+  PointCloud exportCloud(const dsopp_hip_map_export_options &options, const std::vector<int32_t> &keyframe_ids = {}) const {
+    const std::vector<int32_t> ids = keyframe_ids.empty() ? keyframeIds() : keyframe_ids;
+    int64_t capacity = 0;
+    for (int32_t id : ids) capacity += numRecords(id);
+    const size_t cap = static_cast<size_t>(capacity);
+    PointCloud c;
+    c.xyz.resize(cap), c.rgb.resize(cap), c.type.resize(cap), c.relative_baseline.resize(cap), c.idepth_variance.resize(cap);
+    c.keyframe_index.resize(cap), c.record_index.resize(cap), c.per_keyframe_counts.resize(std::max<size_t>(ids.size(), 1));
+    int64_t count = 0;
+    check(dsopp_hip_map_export(m_, &options, static_cast<int32_t>(ids.size()), ids.data(), capacity, cap ? c.xyz[0].data() : nullptr,
+                               cap ? c.rgb[0].data() : nullptr, c.type.data(), c.relative_baseline.data(), c.idepth_variance.data(),
+                               c.keyframe_index.data(), c.record_index.data(), &count, c.per_keyframe_counts.data()));
+    const size_t n = static_cast<size_t>(count);
+    c.xyz.resize(n), c.rgb.resize(n), c.type.resize(n), c.relative_baseline.resize(n), c.idepth_variance.resize(n);
+    c.keyframe_index.resize(n), c.record_index.resize(n), c.per_keyframe_counts.resize(ids.size());
+    return c;
+  }
+  /** the exporter's cloud (point_cloud_exporter.py:83-107): world coordinates, image colours (or the semantic ones), active and
+   *  marginalised landmarks, with `filtration` the confident filter at the exporter's thresholds */
+  PointCloud exportWorld(bool filtration, bool semantic_colours = false, double max_idepth_variance = 5e-8, double min_relative_baseline = 0.15) const {
+    dsopp_hip_map_export_options o;
+    dsopp_hip_map_default_export_options(&o);
+    o.apply_filters = filtration ? 1 : 0;
+    o.max_idepth_variance = max_idepth_variance;
+    o.min_relative_baseline_filter = min_relative_baseline;
+    o.frame = DSOPP_HIP_MAP_FRAME_WORLD;
+    o.colours = semantic_colours ? DSOPP_HIP_MAP_COLOURS_SEMANTIC : DSOPP_HIP_MAP_COLOURS_IMAGE;
+    return exportCloud(o);
+  }
+  /** Frame::buildPoints of one keyframe and one class, appended to `storage`: three exports, one per colour set */
+  void points(int32_t keyframe_id, PointStorageType type, PointsStorage &storage) const {
+    dsopp_hip_map_export_options o;
+    dsopp_hip_map_default_export_options(&o);
+    o.classes = static_cast<int32_t>(type);
+    o.frame = DSOPP_HIP_MAP_FRAME_KEYFRAME;
+    o.colours = DSOPP_HIP_MAP_COLOURS_LANDMARK_TYPE;
+    const PointCloud by_type = exportCloud(o, {keyframe_id});
+    o.colours = DSOPP_HIP_MAP_COLOURS_CONSTANT;
+    const PointCloud constant = exportCloud(o, {keyframe_id});
+    o.colours = DSOPP_HIP_MAP_COLOURS_SEMANTIC;
+    const PointCloud semantic = exportCloud(o, {keyframe_id});
+    storage.points.insert(storage.points.end(), by_type.xyz.begin(), by_type.xyz.end());
+    storage.colors.insert(storage.colors.end(), by_type.rgb.begin(), by_type.rgb.end());
+    storage.default_colors.insert(storage.default_colors.end(), constant.rgb.begin(), constant.rgb.end());
+    storage.semantics_colors.insert(storage.semantics_colors.end(), semantic.rgb.begin(), semantic.rgb.end());
+    storage.idepth_variances.insert(storage.idepth_variances.end(), by_type.idepth_variance.begin(), by_type.idepth_variance.end());
+    storage.relative_baselines.insert(storage.relative_baselines.end(), by_type.relative_baseline.begin(), by_type.relative_baseline.end());
+  }
+  dsopp_hip_map *handle() const { return m_; }
+
+ private:
+  static dsopp_hip_window *window(const HipPhotometricBundleAdjustment &solver) {
+    if (!solver.handle()) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the map needs a single-device solver");
+    return solver.handle();
+  }
+  dsopp_hip_map *m_ = nullptr;
+};
+
 /** features::Correspondence (feature_based_slam/features/correspondence.hpp:12-19) */
 struct FlowCorrespondence {
   bool is_inlier;

@@ -1575,6 +1575,123 @@ int dsopp_hip_debug_views_keyframe_planes(dsopp_hip_debug_views *v, const uint8_
 int dsopp_hip_debug_views_get_maximum_idepth(dsopp_hip_debug_views *v, double *maximum_idepth);
 int dsopp_hip_debug_views_set_maximum_idepth(dsopp_hip_debug_views *v, double maximum_idepth);
 
+/* ---- the map: keyframe landmark records that outlive the window, and their point cloud (row o-2) ----
+ * What the reference keeps in its track (ActiveTrackingLandmark of every keyframe) and hands to its viewer and its exporter:
+ *   PhotometricBundleAdjustment::updateFrame, the landmark rules        src/energy/problems/src/photometric_bundle_adjustment.cpp:223-263
+ *   ActiveTrackingLandmark::marginalize / semanticTypeId               src/track/landmarks/src/active_tracking_landmark.cpp:55-63, 71-88
+ *   Frame::buildPoints / validForVisualization / getColor              src/track/frames/src/frame.cpp:19-82, 190-216
+ *   initializeVisiblePointsStorage                                     src/output/visualizer/src/local_track.cpp:139-158
+ *   the exporter's loop                                                pydsopp/utils/point_cloud_exporter.py:83-107
+ * tests/point_cloud_model.py is the NumPy statement of everything below; the device is held to it exactly, positions bit for bit.
+ *
+ * A map holds keyframes in insertion order.  A keyframe holds its pinhole intrinsics (fx, fy, cx, cy), its pose T_world_agent and one
+ * RECORD per landmark, index = the caller's landmark index of the window:
+ *   uv, idepth, variance (the inverse depth's), relative_baseline, flags (DSOPP_HIP_MAP_FLAG_*), type (the semantic class), rgb
+ * and the bit has_image: its colours were sampled from an image.  A keyframe is LIVE while a window feeds it, then FINALISED for good.
+ *
+ * create: options NULL = the defaults (estimate_uncertainty 1, channels C = 1: the template parameter C of the bundle adjustment,
+ *   min_relative_baseline 0.1: validForVisualization's).  `stream` NULL = a stream of the map's own.
+ * add_keyframe(map, window, frame_id, pyramid or NULL), after dsopp_hip_window_push_frame of that frame: a live keyframe without records,
+ *   with the intrinsics and the pose the window holds.  If the pyramid keeps an 8-bit image (dsopp_hip_pyramid_get_image's rules; the
+ *   colour image if it is kept, else the grey one) the map copies it device to device, behind the pyramid's stream; the pyramid is not
+ *   borrowed.  The copy is freed when the keyframe is finalised.  The window must be a whole window: a landmark shard of a
+ *   dsopp_hip_window_group is DSOPP_HIP_ERR_INVALID_ARGUMENT (the group form is not built).  A frame the window does not hold:
+ *   DSOPP_HIP_ERR_NOT_FOUND; an id the map holds already: DSOPP_HIP_ERR_STATE.
+ * update(map, window, weights256 or NULL): ONE launch over all landmarks of all frames of the window that are live keyframes of the map,
+ *   on the map's stream behind the window's; the window's next work runs behind it.  Only enqueues (it waits for the window's stream
+ *   when the window's poses are newer on the device, and when a keyframe's records must grow).  A live keyframe the window no longer
+ *   holds is finalised: its records and pose stay as they are.  Frames of the window the map does not know are passed over.  A keyframe
+ *   takes the window's current pose estimate.  Per landmark, in this order, w_* = the window's values:
+ *     1 a landmark the map has not seen gets a record: uv from the window, idepth = w_idepth, variance = DBL_MAX, relative_baseline = 0,
+ *       flags = 0, type = 0, rgb = the kept image at [int(v), int(u)] (BGR -> RGB; a grey image replicated), (0, 0, 0) without an image
+ *       or outside it (not 0 <= u < width and 0 <= v < height)
+ *     2 w_flags & outlier: the record is an outlier                                                              (:229-231)
+ *     3 not w_flags & marginalized (:232-260): |w_idepth| < 1e-8: idepth = 0, else w_idepth < 0: outlier, else idepth = w_idepth;
+ *       variance = w_inv_hessian_idepth * C, or 1e-5 without estimate_uncertainty; relative_baseline = max(itself, w_relative_baseline)
+ *     4 w_flags & marginalized and the record not yet marginalised: marginalize(): variance / idepth > 1e-3 or idepth < 0: outlier;
+ *       then marginalised.  Such a record no longer follows the window's values (an outlier flag of the window still reaches it).
+ *     5 type = semanticTypeId by the rule of dsopp_hip_window_get_semantic_types (weights256 as there); 0 while no class observation
+ *       has reached the frame
+ *   Call order that makes the map the reference's track: update after every solve (updateFrame runs there), once more after
+ *   dsopp_hip_window_choose_marginalization(apply) — the flags it set marginalise the records, rule 4 — and before the next push_frame,
+ *   which erases the marginalised frames.  A caller that updates only after the choice loses rule 3 for every landmark the choice
+ *   marginalised in the same keyframe step: their records keep the idepth, variance and baseline of the update before (a landmark never
+ *   updated before keeps variance DBL_MAX and becomes an outlier under rule 4), and a frame that left the window before any update has
+ *   no records at all.
+ * set_records: loads or replaces a FINALISED keyframe from host arrays (a new id is appended) — how a stored map comes back.  n x 2 uv,
+ *   n idepth, variance, relative_baseline, flags; type and rgb (n x 3) may be NULL (zeros; has_image = rgb given).  Blocking.  A live id:
+ *   DSOPP_HIP_ERR_STATE; n < 0, a NULL array with n > 0 or a flag bit other than DSOPP_HIP_MAP_FLAG_*: DSOPP_HIP_ERR_INVALID_ARGUMENT.
+ * set_pose: replaces a keyframe's pose (a live keyframe's is overwritten by the next update).
+ * keyframe_ids: *n = the number of keyframes; at most `capacity` ids are written, in insertion order.
+ * get_records: one keyframe's raw records, blocking; every output may be NULL; state = {has_image, finalised}.
+ *
+ * export(map, options, n_ids, frame_ids or NULL = every keyframe in insertion order, capacity, outputs..., count, per_keyframe_counts):
+ *   the records that pass, in the canonical order — keyframes in the order of frame_ids (or of insertion), then record index — packed.
+ *   A record passes when
+ *     idepth != 0 and relative_baseline > min_relative_baseline (the map's), and its class — OUTLIER if flagged outlier, else MARGINALIZED
+ *       if flagged marginalised, else ACTIVE — is in options.classes                                   (validForVisualization)
+ *     with apply_filters: variance < max_idepth_variance and relative_baseline > min_relative_baseline_filter, both strict
+ *       (initializeVisiblePointsStorage, Landmark.confident; the defaults are the exporter's 5e-8 and 0.15)
+ *     with frame WORLD: not |idepth| < 1e-16                                                           (point_cloud_exporter.py:99-100)
+ *   xyz, binary64, every step a single IEEE operation in this order: ifx = 1 / fx, ify = 1 / fy; d = ((u - cx) ifx, (v - cy) ify, 1);
+ *     KEYFRAME: (d.x / idepth, d.y / idepth, 1 / idepth)                                    (frame.cpp:152, pinhole_camera.hpp:137-139)
+ *     WORLD: p_i = ((R_i0 d.x + R_i1 d.y) + R_i2) + t_i idepth; xyz_i = p_i / idepth, R from (qx, qy, qz, qw) as
+ *       R00 = 1 - 2 (yy + zz), R01 = 2 (xy - zw), R02 = 2 (xz + yw), R10 = 2 (xy + zw), R11 = 1 - 2 (xx + zz), R12 = 2 (yz - xw),
+ *       R20 = 2 (xz - yw), R21 = 2 (yz + xw), R22 = 1 - 2 (xx + yy)                                    (point_cloud_exporter.py:96-101)
+ *   rgb by options.colours: LANDMARK_TYPE (255, 0, 0) outlier, (255, 100, 100) marginalised, (100, 255, 100) active; CONSTANT 200;
+ *     SEMANTIC kSemanticColors[type % 14] (frame.cpp:19-26); IMAGE the record's rgb — DSOPP_HIP_ERR_STATE when an exported keyframe has
+ *     has_image = 0.
+ *   Outputs, any of which may be NULL: xyz f64 x 3, rgb u8 x 3, type u8, relative_baseline f64, idepth_variance f64, keyframe_index i32
+ *   (the keyframe's position in the exported list), record_index i32; each holds `capacity` entries.  *count is always the full count
+ *   and per_keyframe_counts (one per exported keyframe) the full counts; count > capacity writes the first `capacity` entries, nothing
+ *   beyond, and returns DSOPP_HIP_ERR_CAPACITY.  Blocking.  Two launches whatever the number of keyframes; integer counting only: the
+ *   result does not depend on the order in which workgroups run.  An id the map does not hold: DSOPP_HIP_ERR_NOT_FOUND; a class mask,
+ *   frame or colour scheme out of range, n_ids or capacity < 0: DSOPP_HIP_ERR_INVALID_ARGUMENT.
+ * export_device: the same into the caller's device buffers (aligned to their element; the colours to 4 bytes) on the map's stream.
+ *   With count and per_keyframe_counts both NULL it only enqueues; otherwise it waits and reports as export does.
+ * One thread drives a map at a time.  There is no CPU path: without a device create fails with DSOPP_HIP_ERR_HIP. */
+typedef struct dsopp_hip_map dsopp_hip_map;
+enum { DSOPP_HIP_MAP_FLAG_MARGINALIZED = 1, DSOPP_HIP_MAP_FLAG_OUTLIER = 2 };
+enum { DSOPP_HIP_MAP_CLASS_ACTIVE = 1, DSOPP_HIP_MAP_CLASS_MARGINALIZED = 2, DSOPP_HIP_MAP_CLASS_OUTLIER = 4 };
+enum { DSOPP_HIP_MAP_FRAME_KEYFRAME = 0, DSOPP_HIP_MAP_FRAME_WORLD = 1 };
+enum { DSOPP_HIP_MAP_COLOURS_LANDMARK_TYPE = 0, DSOPP_HIP_MAP_COLOURS_CONSTANT = 1, DSOPP_HIP_MAP_COLOURS_SEMANTIC = 2, DSOPP_HIP_MAP_COLOURS_IMAGE = 3 };
+typedef struct dsopp_hip_map_options {
+  int32_t estimate_uncertainty;
+  int32_t channels;
+  double min_relative_baseline;
+} dsopp_hip_map_options;
+typedef struct dsopp_hip_map_export_options {
+  int32_t classes; /* DSOPP_HIP_MAP_CLASS_* bits */
+  int32_t apply_filters;
+  double max_idepth_variance;
+  double min_relative_baseline_filter;
+  int32_t frame;   /* DSOPP_HIP_MAP_FRAME_* */
+  int32_t colours; /* DSOPP_HIP_MAP_COLOURS_* */
+} dsopp_hip_map_export_options;
+void dsopp_hip_map_default_options(dsopp_hip_map_options *o);
+/* active and marginalised records, no filters (the exporter's thresholds filled in), world frame, colours by landmark type */
+void dsopp_hip_map_default_export_options(dsopp_hip_map_export_options *o);
+int dsopp_hip_map_create(int device, void *stream, const dsopp_hip_map_options *options, dsopp_hip_map **out);
+void dsopp_hip_map_destroy(dsopp_hip_map *m);
+int dsopp_hip_map_add_keyframe(dsopp_hip_map *m, dsopp_hip_window *window, int32_t frame_id, const dsopp_hip_pyramid *pyramid);
+int dsopp_hip_map_update(dsopp_hip_map *m, dsopp_hip_window *window, const uint64_t *weights256);
+int dsopp_hip_map_set_records(dsopp_hip_map *m, int32_t frame_id, const double intrinsics[4], const double T_world_agent[7], int32_t n,
+                              const double *uv, const double *idepth, const double *variance, const double *relative_baseline,
+                              const uint8_t *flags, const uint8_t *type, const uint8_t *rgb);
+int dsopp_hip_map_set_pose(dsopp_hip_map *m, int32_t frame_id, const double T_world_agent[7]);
+int dsopp_hip_map_num_keyframes(dsopp_hip_map *m, int32_t *n);
+int dsopp_hip_map_keyframe_ids(dsopp_hip_map *m, int32_t capacity, int32_t *ids, int32_t *n);
+int dsopp_hip_map_num_records(dsopp_hip_map *m, int32_t frame_id, int32_t *n);
+int dsopp_hip_map_get_records(dsopp_hip_map *m, int32_t frame_id, double *uv, double *idepth, double *variance, double *relative_baseline,
+                              uint8_t *flags, uint8_t *type, uint8_t *rgb, double intrinsics[4], double T_world_agent[7], int32_t state[2]);
+int dsopp_hip_map_export(dsopp_hip_map *m, const dsopp_hip_map_export_options *options, int32_t n_ids, const int32_t *frame_ids,
+                         int64_t capacity, double *xyz, uint8_t *rgb, uint8_t *type, double *relative_baseline, double *idepth_variance,
+                         int32_t *keyframe_index, int32_t *record_index, int64_t *count, int32_t *per_keyframe_counts);
+int dsopp_hip_map_export_device(dsopp_hip_map *m, const dsopp_hip_map_export_options *options, int32_t n_ids, const int32_t *frame_ids,
+                                int64_t capacity, void *xyz_dev, void *rgb_dev, void *type_dev, void *relative_baseline_dev,
+                                void *idepth_variance_dev, void *keyframe_index_dev, void *record_index_dev, int64_t *count,
+                                int32_t *per_keyframe_counts);
+
 #ifdef __cplusplus
 }
 #endif
