@@ -9,9 +9,12 @@ more than one step.  What differs from synthetic.make_window is where the frames
                    reference side, of the target side and of the first-estimate-Jacobians item test all say "outside" somewhere
   mixed(sizes)     one 163 x 123 scene, every keyframe cropped at the origin to a size of its own (reference and target sizes differ)
   level(l)         327 x 245 8-bit frames through a photometric LUT and a 3-level pyramid, the window on level l (163 x 122, 81 x 61)
+  masked_border()  border(161, 121) with a camera mask of a few rectangles per keyframe where landmarks reproject, and non-zero affine
+                   brightness states
 
 tests/test_sweep_edge_scenes.py asserts on the CPU oracle alone that the scenes reach what they are for; tests/test_gpu_sweep_frame_edges.py
-compares the HIP window with the oracle on them.  The builders are cached: the tests share one copy of every scene and leave it unchanged.
+compares the HIP window with the oracle on them; tests/test_gpu_sweep_f32.py compares its fp32 mode with tests/sweep_f32_model.py on
+F32_EDGE_SCENES.  The builders are cached: the tests share one copy of every scene and leave it unchanged.
 """
 import dataclasses
 import functools
@@ -39,6 +42,7 @@ class EdgeScene:
     intrinsics: np.ndarray               # of the window's level
     level: int = 0
     lut: np.ndarray = None               # level scenes: the HIP window builds its own pyramid of frames[i].image_u8 through this LUT
+    masks: list = None                   # masked scenes: one H x W uint8 camera mask per keyframe (1 = valid, 0 = masked)
 
     def size(self, i):
         h, w = self.window.frames[i].pixelinfo.shape[:2]
@@ -191,12 +195,55 @@ F32_SCENES = ([(f"interior-{w}x{h}", functools.partial(interior, w, h)) for w, h
               + [("mixed", mixed), ("level1", functools.partial(level, 1))])
 
 
+MASK_RECTS, MASK_RECT_W, MASK_RECT_H = 5, 7, 5
+MASKED_AFFINE = ((0.0, 0.0), (0.02, 1.5), (-0.03, -2.5))     # (a, b) of the masked scene's keyframes: b_t, b_r and s are no longer 0, 0, 1
+
+
+@functools.lru_cache(maxsize=None)
+def masked_border(width=SIZES[0][0], height=SIZES[0][1]):
+    """border(width, height) whose keyframes carry a camera mask: MASK_RECTS rectangles of MASK_RECT_W x MASK_RECT_H masked pixels per
+    keyframe, each with a corner one pixel beside the reprojection of a landmark of another keyframe, so that patterns lie across a
+    mask edge (some of their 8 pixels masked, some not) as well as wholly inside and outside one.  The keyframes also start from the
+    affine brightness states MASKED_AFFINE: every other scene has a = b = 0, where a residual without its b_t is the same residual."""
+    base = border(width, height)
+    rng = np.random.default_rng(3000 + width + height)
+    frames = [dataclasses.replace(f, affine_init=np.array(MASKED_AFFINE[i])) for i, f in enumerate(base.window.frames)]
+    scene = EdgeScene(f"masked-border-{width}x{height}", syn.SyntheticWindow(base.window.scene, frames), base.intrinsics)
+    masks = []
+    for t in range(NUM_FRAMES):
+        mask = np.ones((height, width), dtype=np.uint8)
+        centres = []
+        for r in range(NUM_FRAMES):
+            if r != t:
+                tu, tv = reproject_centres(scene, r, t)
+                inside = (tu >= 12) & (tu <= width - 13) & (tv >= 12) & (tv <= height - 13)
+                centres.append(np.stack([tu[inside], tv[inside]], axis=1))
+        centres = np.concatenate(centres)
+        for cu, cv in centres[rng.choice(len(centres), MASK_RECTS, replace=False)]:
+            x0, y0 = int(np.rint(cu)) + 1, int(np.rint(cv)) - MASK_RECT_H // 2
+            mask[y0:y0 + MASK_RECT_H, x0:x0 + MASK_RECT_W] = 0
+        masks.append(mask)
+    scene.masks = masks
+    return scene
+
+
+# the scenes of the residual-by-residual f32 comparison (tests/sweep_f32_model.py judges every ROI decision by its margin, so the border
+# scenes are in): every size of the interior and border scenes, the mixed one, both levels and the masked border scene
+F32_EDGE_SCENES = ([(f"interior-{w}x{h}", functools.partial(interior, w, h)) for w, h in SIZES]
+                   + [(f"border-{w}x{h}", functools.partial(border, w, h)) for w, h in SIZES]
+                   + [("mixed", mixed), ("level1", functools.partial(level, 1)), ("level2", functools.partial(level, 2)),
+                      ("masked-border", masked_border)])
+
+
 def load(backend, scene, pyramids=None):
     """synthetic.load_window for an EdgeScene.  `pyramids`: one device pyramid per keyframe for the HIP window to borrow at scene.level
-    (build_pyramids); without them the backend is handed frames[i].pixelinfo, which is what the oracle always takes."""
+    (build_pyramids); without them the backend is handed frames[i].pixelinfo, which is what the oracle always takes.  A scene's camera
+    masks go with the pixelinfo (push_frame's mask argument); no scene has both masks and borrowed pyramids."""
     win = scene.window
+    assert scene.masks is None or pyramids is None
     for i, f in enumerate(win.frames):
-        args = (f.frame_id, f.timestamp, f.pixelinfo, None, scene.intrinsics, syn.mat_to_params(f.T_w_c_init), f.exposure, f.affine_init,
+        mask = None if scene.masks is None else scene.masks[i]
+        args = (f.frame_id, f.timestamp, f.pixelinfo, mask, scene.intrinsics, syn.mat_to_params(f.T_w_c_init), f.exposure, f.affine_init,
                 f.fixed, False)
         if pyramids is None:
             backend.push_frame(*args)
