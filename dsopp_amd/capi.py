@@ -117,6 +117,45 @@ class GeometricBADebug(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in GEOMETRIC_BA_DEBUG_FIELDS]
 
 
+CAMERA_SIMPLE_RADIAL, CAMERA_TUM_FOV, CAMERA_ATAN = 0, 1, 2
+CAMERA_MAX_K = 16  # DSOPP_HIP_CAMERA_MAX_K
+
+
+class CameraModel(C.Structure):
+    """dsopp_hip_camera_model; the class methods take the reference constructors' arguments, size = (width, height)"""
+    _fields_ = [("type", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("num_k", C.c_int32), ("params", C.c_double * 4),
+                ("k", C.c_double * CAMERA_MAX_K)]
+
+    @classmethod
+    def make(cls, type_, size, params, k):
+        m = cls(type=int(type_), width=int(size[0]), height=int(size[1]), num_k=len(k))
+        for i, v in enumerate(params):
+            m.params[i] = v
+        for i, v in enumerate(list(k)[:CAMERA_MAX_K]):
+            m.k[i] = v
+        return m
+
+    @classmethod
+    def simple_radial(cls, size, f, cx, cy, k1, k2):
+        return cls.make(CAMERA_SIMPLE_RADIAL, size, (f, cx, cy), (k1, k2))
+
+    @classmethod
+    def tum_fov(cls, size, fx, fy, cx, cy, fov):
+        return cls.make(CAMERA_TUM_FOV, size, (fx, fy, cx, cy), (fov,))
+
+    @classmethod
+    def atan(cls, size, fx, fy, cx, cy, polynomial=()):
+        return cls.make(CAMERA_ATAN, size, (fx, fy, cx, cy), tuple(polynomial))
+
+
+def camera_model_to_pinhole(model: CameraModel):
+    """dsopp_hip_camera_model_to_pinhole, no device needed: (pinhole intrinsics (fx, fy, cx, cy), derived (max_valid_radius,
+    line_after_radius 0 and 1; zeros unless simple-radial))"""
+    pinhole, derived = np.zeros(4), np.zeros(3)
+    _chk(lib().dsopp_hip_camera_model_to_pinhole(C.byref(model), _p(pinhole), _p(derived)))
+    return pinhole, derived
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 # every symbol include/dsopp_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -162,6 +201,7 @@ SYMBOLS = [
     "dsopp_hip_pyramid_build_transformed", "dsopp_hip_semantics_create_transformed",
     "dsopp_hip_undistorter_undistort_bgr_device", "dsopp_hip_transformer_transform_bgr_device", "dsopp_hip_pyramid_build_colour",
     "dsopp_hip_pyramid_get_image",
+    "dsopp_hip_camera_model_to_pinhole", "dsopp_hip_undistorter_create_from_model",
     "dsopp_hip_flow_tracker_create", "dsopp_hip_flow_tracker_destroy", "dsopp_hip_flow_tracker_num_levels",
     "dsopp_hip_flow_tracker_set_reference", "dsopp_hip_flow_tracker_set_reference_device", "dsopp_hip_flow_tracker_set_reference_from_pyramid",
     "dsopp_hip_flow_tracker_track", "dsopp_hip_flow_tracker_track_device", "dsopp_hip_flow_tracker_track_from_pyramid",
@@ -293,6 +333,21 @@ class Undistorter:
             assert m is None or m.shape == (self.out_size[1], self.out_size[0]), m.shape
         _chk(lib().dsopp_hip_undistorter_create(int(device), C.c_void_p(stream or 0), self.in_size[0], self.in_size[1], self.out_size[0],
                                                 self.out_size[1], _p(mx, np.float32), _p(my, np.float32), C.byref(self._h)))
+
+    @classmethod
+    def from_model(cls, model: CameraModel, maps=False, device=0, stream=None):
+        """dsopp_hip_undistorter_create_from_model: the undistorter of a distorted camera model, its tables built on the device.  With
+        maps the two float32 tables come back as .map_x / .map_y (else None); .pinhole_intrinsics = (fx, fy, cx, cy) of the target"""
+        u = cls.__new__(cls)
+        u._h = C.c_void_p()
+        u.in_size = u.out_size = (int(model.width), int(model.height))
+        u.device = device
+        u.map_x = np.zeros((model.height, model.width), dtype=np.float32) if maps else None
+        u.map_y = np.zeros((model.height, model.width), dtype=np.float32) if maps else None
+        u.pinhole_intrinsics = np.zeros(4)
+        _chk(lib().dsopp_hip_undistorter_create_from_model(int(device), C.c_void_p(stream or 0), C.byref(model), _p(u.map_x, np.float32),
+                                                           _p(u.map_y, np.float32), _p(u.pinhole_intrinsics), C.byref(u._h)))
+        return u
 
     def close(self):
         if self._h:

@@ -31,8 +31,10 @@ FLAGS_marginalization="-ffp-contract=off"
 FLAGS_debug_views="-ffp-contract=off"
 # point_cloud.hip: the positions of the exported cloud are single IEEE binary64 steps in the stated order, as the NumPy model takes them
 FLAGS_point_cloud="-ffp-contract=off"
+# camera_remap.hip: a map entry is a chain of single IEEE binary64 steps in the stated order (include/dsopp_hip.h), as the NumPy model takes them
+FLAGS_camera_remap="-ffp-contract=off"
 pids=()
-for src in pyramid undistort transform colour optical_flow rotation_ransac geometric_ba pnp_ransac two_view_ransac orb semantics marginalization debug_views point_cloud pba align depth_estimation features features_eigen comm calibration window_group; do
+for src in pyramid undistort camera_remap transform colour optical_flow rotation_ransac geometric_ba pnp_ransac two_view_ransac orb semantics marginalization debug_views point_cloud pba align depth_estimation features features_eigen comm calibration window_group; do
   if [ -f "$HERE/$src.hip" ]; then
     extra="FLAGS_$src"
     $HIPCC $FLAGS ${!extra:-} -c "$HERE/$src.hip" -o "$OUT/$src.o" &
@@ -41,7 +43,7 @@ for src in pyramid undistort transform colour optical_flow rotation_ransac geome
 done
 for p in "${pids[@]}"; do wait "$p"; done
 objs=()
-for src in pyramid undistort transform colour optical_flow rotation_ransac geometric_ba pnp_ransac two_view_ransac orb semantics marginalization debug_views point_cloud pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
+for src in pyramid undistort camera_remap transform colour optical_flow rotation_ransac geometric_ba pnp_ransac two_view_ransac orb semantics marginalization debug_views point_cloud pba align depth_estimation features features_eigen comm window_group; do [ -f "$OUT/$src.o" ] && objs+=("$OUT/$src.o"); done
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$OUT/libdsopp_hip.so"
 # measurement aids that are not part of the product (gather kernels of known geometry for the counter calibration, scripts/pmc_target.py)
 [ -f "$OUT/calibration.o" ] && $HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/calibration.o" -o "$OUT/libdsopp_hip_tools.so"

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "pyramid.hpp"
+#include "remap_fold.hpp"
 
 namespace dsopp_hip {
 namespace {
@@ -63,23 +64,6 @@ __global__ void __launch_bounds__(kBlock) undistortKernel(const unsigned *__rest
       reinterpret_cast<GlobalPtr<uint8_t>>(glb(out_))[first + k] = static_cast<uint8_t>(remapPixel(src, in_w, e.x, e.y));
     }
   }
-}
-
-/** BORDER_REFLECT_101 of any integer: period 2 (n - 1), ... c b | a b c d | c b ... */
-int reflect101(long c, int n) {
-  const long period = 2L * (n - 1);
-  long r = c % period;
-  if (r < 0) r += period;
-  return static_cast<int>(r >= n ? period - r : r);
-}
-
-/** one map coordinate -> the two reflected tap coordinates and the 5-bit fraction */
-void splitCoordinate(float c, int n, int &c0, int &c1, int &fraction) {
-  const long s = std::lrintf(c * 32.0f);  // exact product, rounded half to even (cvRound)
-  const long i = s >> kRemapFractionBits;       // arithmetic shift: the floor, also below zero
-  fraction = static_cast<int>(s & (kRemapOne - 1));
-  c0 = reflect101(i, n);
-  c1 = reflect101(i + 1, n);
 }
 
 bool usable(float c) { return std::isfinite(c) && std::fabs(c) <= kMaxCoordinate; }
@@ -124,11 +108,7 @@ int dsopp_hip_undistorter_create(int device, void *stream, int in_w, int in_h, i
       const float cx = map_x ? map_x[i] : static_cast<float>(i % out_w), cy = map_y ? map_y[i] : static_cast<float>(i / out_w);
       if (!usable(cx) || !usable(cy))
         fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "map entry %zu is (%g, %g): not finite or beyond 2^20", i, static_cast<double>(cx), static_cast<double>(cy));
-      int x0, x1, fx, y0, y1, fy;
-      splitCoordinate(cx, in_w, x0, x1, fx);
-      splitCoordinate(cy, in_h, y0, y1, fy);
-      table[2 * i] = static_cast<uint32_t>(y0) * static_cast<uint32_t>(in_w) + static_cast<uint32_t>(x0);
-      table[2 * i + 1] = static_cast<uint32_t>(fx) | (static_cast<uint32_t>(fy) << kRemapFyShift) | (x1 < x0 ? kRemapFlipX : 0u) | (y1 < y0 ? kRemapFlipY : 0u);
+      foldMapEntry(cx, cy, in_w, in_h, table[2 * i], table[2 * i + 1]);
     }
     auto u = std::make_unique<dsopp_hip_undistorter>();
     u->sr.init(device, stream);

@@ -23,6 +23,7 @@
 #include <deque>
 #include <map>
 #include <memory>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -55,14 +56,22 @@ inline void check(int rc) {
   if (rc != DSOPP_HIP_OK) throw SolverError(rc, dsopp_hip_last_error());
 }
 
-/** sensors::calibration::Undistorter (undistorter.hpp:24-152) on the device: the two remap tables of constructRemaps, which stays host
- *  code of the reference, folded into a device table once per camera.  No maps = Undistorter::Identity. */
+/** sensors::calibration::Undistorter (undistorter.hpp:24-152) on the device: either the two remap tables of constructRemaps as the
+ *  reference's host code fills them, folded into a device table once per camera (no maps = Undistorter::Identity), or constructRemaps
+ *  itself from the distorted camera model, evaluated and folded on the device (dsopp_hip_undistorter_create_from_model). */
 class HipUndistorter {
  public:
   HipUndistorter(int in_width, int in_height, int out_width, int out_height, const float *remap_x, const float *remap_y, int device = 0,
                  void *stream = nullptr)
       : out_width_(out_width), out_height_(out_height) {
     check(dsopp_hip_undistorter_create(device, stream, in_width, in_height, out_width, out_height, remap_x, remap_y, &u_));
+  }
+  /** Undistorter::constructRemaps(model) (undistorter.hpp:69-90): in size = out size = the model's; remap_x_out / remap_y_out (both or
+   *  neither) receive the two float tables, pinhole_out the target pinhole's (fx, fy, cx, cy) */
+  explicit HipUndistorter(const dsopp_hip_camera_model &model, int device = 0, void *stream = nullptr, float *remap_x_out = nullptr,
+                          float *remap_y_out = nullptr, double *pinhole_out = nullptr)
+      : out_width_(model.width), out_height_(model.height) {
+    check(dsopp_hip_undistorter_create_from_model(device, stream, &model, remap_x_out, remap_y_out, pinhole_out, &u_));
   }
   ~HipUndistorter() { dsopp_hip_undistorter_destroy(u_); }
   HipUndistorter(const HipUndistorter &) = delete;
@@ -138,6 +147,102 @@ class HipImageTransformer {
  private:
   dsopp_hip_transformer *t_ = nullptr;
   int out_width_ = 0, out_height_ = 0;
+};
+
+/** sensors::calibration::camera_calibration::create (src/sensors/camera_calibration/src/fabric.cpp:23-113) over the C-ABI: the text of a
+ *  calibration file becomes the calibration the tracker runs on and the undistorter in front of it.
+ *    pinhole        W H / fx fy cx cy            (:23-31)  a pinhole calibration, Undistorter::Identity: no undistorter here
+ *    simple_radial  W H / f cx cy k1 k2          (:33-51)  with transform_to_pinhole the pinhole of constructRemaps and its undistorter,
+ *                                                          else the simple-radial calibration itself and no undistorter
+ *    tum_fov        W H / fx fy cx cy fov        (:53-72)  focals and centre relative to the image size (:59-64); always to a pinhole
+ *  parse() needs no device; undistorter() builds the device table at its first call.  What the reference logs and answers with nullopt —
+ *  an unknown model type, tum_fov without transform_to_pinhole — and a text that ends early throw SolverError. */
+class HipCameraCalibration {
+ public:
+  enum class ModelType { kPinholeCamera, kSimpleRadialCamera };  // energy::model::ModelType of the resulting calibration
+
+  static HipCameraCalibration parse(const std::string &text, bool transform_to_pinhole = true) {
+    std::istringstream in(text);
+    std::string model_type;
+    in >> model_type;
+    HipCameraCalibration c;
+    double v[5] = {0, 0, 0, 0, 0};
+    const auto read = [&](int count) {
+      in >> c.image_size_[0] >> c.image_size_[1];
+      for (int i = 0; i < count; ++i) in >> v[i];
+      if (!in) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the " + model_type + " calibration ends early or holds no number");
+    };
+    if (model_type == "pinhole") {
+      read(4);
+      c.intrinsics_ = {v[0], v[1], v[2], v[3], 0.0};
+      return c;
+    }
+    if (model_type == "simple_radial") {
+      read(5);
+      if (!transform_to_pinhole) {
+        c.type_ = ModelType::kSimpleRadialCamera;
+        c.intrinsics_ = {v[0], v[1], v[2], v[3], v[4]};
+        return c;
+      }
+      c.model_.type = DSOPP_HIP_CAMERA_SIMPLE_RADIAL;
+      c.model_.num_k = 2;
+      for (int i = 0; i < 3; ++i) c.model_.params[i] = v[i];
+      c.model_.k[0] = v[3];
+      c.model_.k[1] = v[4];
+    } else if (model_type == "tum_fov") {
+      if (!transform_to_pinhole) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "can't create a TUM FOV model without an undistorter");
+      read(5);
+      c.model_.type = DSOPP_HIP_CAMERA_TUM_FOV;
+      c.model_.num_k = 1;
+      c.model_.params[0] = v[0] * c.image_size_[0];
+      c.model_.params[1] = v[1] * c.image_size_[1];
+      c.model_.params[2] = v[2] * c.image_size_[0];
+      c.model_.params[3] = v[3] * c.image_size_[1];
+      c.model_.k[0] = v[4];
+    } else {
+      throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "inappropriate model type for a camera sensor: '" + model_type + "'");
+    }
+    c.distorted_ = true;
+    c.model_.width = static_cast<int32_t>(c.image_size_[0]);  // the maps' size, as constructRemaps casts it (undistorter.hpp:82-83)
+    c.model_.height = static_cast<int32_t>(c.image_size_[1]);
+    double pinhole[4];
+    check(dsopp_hip_camera_model_to_pinhole(&c.model_, pinhole, nullptr));
+    c.intrinsics_ = {pinhole[0], pinhole[1], pinhole[2], pinhole[3], 0.0};
+    return c;
+  }
+
+  ModelType type() const { return type_; }
+  /** CameraCalibration::image_size() */
+  double imageWidth() const { return image_size_[0]; }
+  double imageHeight() const { return image_size_[1]; }
+  /** CameraCalibration's intrinsics: (fx, fy, cx, cy) of a pinhole calibration, (f, cx, cy, k1, k2) of a simple-radial one */
+  const std::array<double, 5> &intrinsics() const { return intrinsics_; }
+  /** the pinhole the tracker runs on (a kPinholeCamera calibration only) */
+  PinholeModel pinhole() const {
+    if (type_ != ModelType::kPinholeCamera) throw SolverError(DSOPP_HIP_ERR_STATE, "the calibration is not a pinhole");
+    return PinholeModel{intrinsics_[0], intrinsics_[1], intrinsics_[2], intrinsics_[3]};
+  }
+  /** whether an undistorter stands in front of the calibration, and the distorted model it is built from */
+  bool hasUndistorter() const { return distorted_; }
+  const dsopp_hip_camera_model &model() const {
+    if (!distorted_) throw SolverError(DSOPP_HIP_ERR_STATE, "the calibration has no distorted model");
+    return model_;
+  }
+  /** calibration.undistorter(): built from the model on the device by the first call; nullptr = Undistorter::Identity, which every
+   *  consumer of the library takes as "frames arrive undistorted" */
+  const HipUndistorter *undistorter(int device = 0, void *stream = nullptr) {
+    if (distorted_ && !undistorter_) undistorter_ = std::make_unique<HipUndistorter>(model_, device, stream);
+    return undistorter_.get();
+  }
+
+ private:
+  HipCameraCalibration() = default;
+  ModelType type_ = ModelType::kPinholeCamera;
+  double image_size_[2] = {0, 0};
+  std::array<double, 5> intrinsics_{};
+  bool distorted_ = false;
+  dsopp_hip_camera_model model_{};
+  std::unique_ptr<HipUndistorter> undistorter_;
 };
 
 /** The per-camera constants of the `segmentation:` block (camera_fabric.cpp:54-99,170-186) on the device: the static mask as the camera

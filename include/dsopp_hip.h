@@ -119,7 +119,8 @@ int dsopp_hip_pyramid_level_size(dsopp_hip_pyramid *p, int level, int *width, in
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dsopp_hip_undistorter dsopp_hip_undistorter;
 /* Undistorter(remapX, remapY, input_width, input_height) (undistorter.hpp:35-36): map_x / map_y are the two CV_32F remap tables
- * (out_h x out_w floats, row-major) that constructRemaps (undistorter.hpp:69-142) fills on the host; the reference has out == in,
+ * (out_h x out_w floats, row-major) that constructRemaps (undistorter.hpp:69-142) fills on the host (dsopp_hip_undistorter_create_from_model
+ * builds them from the camera model on the device instead); the reference has out == in,
  * both sizes are taken as cv::remap takes them.  NULL, NULL = Undistorter::Identity (undistorter.cpp:20-22; out must equal in).
  * The arithmetic of every later undistort is integer and fixed here, for a single-channel 8-bit image (cv::remap INTER_LINEAR,
  * BORDER_REFLECT_101, undistorter.cpp:16):
@@ -148,6 +149,68 @@ int dsopp_hip_undistorter_undistort_device(dsopp_hip_undistorter *u, const void 
  * device and the pyramid's size must be the undistorter's out size, else DSOPP_HIP_ERR_INVALID_ARGUMENT. */
 int dsopp_hip_pyramid_build_undistorted(dsopp_hip_pyramid *p, const dsopp_hip_undistorter *u, const uint8_t *distorted_host, const double *lut256,
                                         const uint8_t *vignetting_host);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The undistorter's remap tables from the camera model (replaces Undistorter::constructRemaps / estimateRemaps — src/sensors/
+ * camera_calibration/include/sensors/camera_calibration/undistorter/undistorter.hpp:69-142 —, which src/sensors/camera_calibration/src/
+ * fabric.cpp:45-49,67-71 runs once for every simple_radial and TUM-FOV calibration, with the projections of CAM = src/energy/camera_model/
+ * include/energy/camera_model: CAM/pinhole/pinhole_camera.hpp:129-141, CAM/pinhole/simple_radial.hpp:39-83,134-160,
+ * CAM/fisheye/tum_fov_model.hpp:72-82, CAM/fisheye/atan_camera.hpp:98-127, CAM/polynomial_solver.hpp:11-41).  The maps are evaluated on
+ * the device, one independent evaluation per pixel, and folded there into the table dsopp_hip_undistorter_create folds on the host.
+ *
+ * The arithmetic, binary64 in the order written, every product, sum, quotient and square root one IEEE step (nothing is fused):
+ *   the target pinhole (undistorter.hpp:70-80) is (focalX, focalY, width / 2, height / 2) at the model's own size (w, h);
+ *   per output pixel (x, y) (undistorter.hpp:124-141, pinhole_camera.hpp:129-141): the unprojection fails unless 4 <= x <= w - 5 and
+ *   4 <= y <= h - 5;  rx = (x - w / 2) * (1 / fx), ry = (y - h / 2) * (1 / fy) — a product with the inverse, not a division; the ray
+ *   is (rx, ry, 1).  "ROI" of a point p: 4 <= px <= w - 5 and 4 <= py <= h - 5 (camera_model_base.hpp:52-60).
+ *   simple-radial (simple_radial.hpp:134-160): r2 = rx rx + ry ry; fail if sqrt(r2) > max_valid_radius; d = (1 + k1 r2) + (k2 r2) r2;
+ *     p = ((rx d) f + cx, (ry d) f + cy); fail unless p is in the ROI.
+ *   TUM-FOV (tum_fov_model.hpp:72-82): ru = sqrt(rx rx + ry ry); ru < 1e-8: p = (cx, cy), success, no ROI test; else
+ *     rd = atan2((2 ru) T, 1) / fov with T = tan(fov / 2) computed once on the host; q = rd / ru; p = ((q rx) fx + cx, (q ry) fy + cy);
+ *     fail unless p is in the ROI.
+ *   atan (atan_camera.hpp:98-127): n = sqrt((rx rx + ry ry) + 1); a = (rx / n, ry / n, 1 / n); rho = sqrt(ax ax + ay ay); rho < 1e-6:
+ *     p = (cx, cy), success, no ROI test; else theta = atan2(rho, az); Horner from the top coefficient, s = 0, s = s theta + k[i];
+ *     s = theta (1 + s theta); p = (((ax s) / rho) fx + cx, ((ay s) / rho) fy + cy); fail unless p is in the ROI.
+ *   The map entry is ((float)px, (float)py), round to nearest even; either failure gives (-1, -1) (undistorter.hpp:134-140), which the
+ *   remap turns into src[1, 1] as stated at dsopp_hip_undistorter_create.  The fold into the table is the statement given there
+ *   (sx = rint(map * 32.0f), the split, the reflection), run by the same code on the host and on the device.
+ * What this does not pin: the reference's own build may contract products and sums into fused operations (the GCC default), so its last
+ * bit is not pinned by this statement; atan2 on the device is the device math library's (OCML), so TUM-FOV and atan maps are not
+ * bit-pinned to any host libm (simple-radial maps are: sqrt, products and sums only); and max_valid_radius below comes from this
+ * library's own root finder, whose parity with the eigenvalues of Eigen's companion matrix (polynomial_solver.hpp:23-28) is unpinned —
+ * both are roots of one polynomial to about an ulp, and a pixel whose radius lies between the two would differ.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define DSOPP_HIP_CAMERA_MAX_K 16
+enum { DSOPP_HIP_CAMERA_SIMPLE_RADIAL = 0, DSOPP_HIP_CAMERA_TUM_FOV = 1, DSOPP_HIP_CAMERA_ATAN = 2 };
+/* SimpleRadialCamera (simple_radial.hpp:39-46): params = (f, cx, cy), k = (k1, k2), num_k = 2.
+ * TUMFovModel (tum_fov_model.hpp:37-43): params = (fx, fy, cx, cy) in pixels, k = (fov), num_k = 1.
+ * AtanCamera (atan_camera.hpp:86-88): params = (fx, fy, cx, cy) in pixels, k = the polynomial data_[4 ...], num_k = 0 .. 16. */
+typedef struct dsopp_hip_camera_model {
+  int32_t type; /* DSOPP_HIP_CAMERA_* */
+  int32_t width, height;
+  int32_t num_k;
+  double params[4];
+  double k[DSOPP_HIP_CAMERA_MAX_K];
+} dsopp_hip_camera_model;
+/* The pinhole of constructRemaps (undistorter.hpp:70-80): pinhole_intrinsics = (focalX, focalY, width / 2, height / 2).  Needs no device.
+ * derived: for simple-radial the constructor's constants (simple_radial.hpp:47-82) max_valid_radius_, line_after_radius_(0),
+ * line_after_radius_(1); zeros for the other types.  max_valid_radius_ is the least positive root of k2 r^5 + k1 r^3 + r - R, R the
+ * corner radius (:47-50), found by bracketing between the roots of the derivative (a quadratic in r^2) and a safeguarded Newton
+ * iteration in the bracket; as in the reference the polynomial is normalised and its leading coefficients below 1e-8 are dropped
+ * (polynomial_solver.hpp:14-19), and no positive root gives +inf (:30-40).  The extremum rule (simple_radial.hpp:62-77) is applied as
+ * written in IEEE arithmetic: with k2 == 0 its divisions give NaN or inf and the comparisons decide.  Either output may be NULL.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: the model errors listed below. */
+int dsopp_hip_camera_model_to_pinhole(const dsopp_hip_camera_model *model, double pinhole_intrinsics[4], double derived[3]);
+/* constructRemaps(model) (undistorter.hpp:69-90): the undistorter of the model, in size = out size = (width, height) as in the
+ * reference.  One launch evaluates every pixel and writes the folded table; nothing but the kernel's arguments goes to the device.
+ * map_x_out / map_y_out (height x width floats each, row-major; both or neither) receive the two CV_32F tables when given, else
+ * nothing comes back; pinhole_intrinsics_out (may be NULL) as above.  Blocking.  The handle is the one dsopp_hip_undistorter_create
+ * returns and every consumer takes it unchanged.
+ * DSOPP_HIP_ERR_INVALID_ARGUMENT: an unknown type, a non-finite parameter or coefficient, a focal length <= 0, a principal point
+ * coordinate beyond 2^20 in magnitude (the bound on a map entry), fov outside (0, pi), num_k wrong for the type or above 16, width or
+ * height < 2, more than INT_MAX pixels, a NULL model or out, only one of the two map outputs. */
+int dsopp_hip_undistorter_create_from_model(int device, void *stream, const dsopp_hip_camera_model *model, float *map_x_out, float *map_y_out,
+                                            double pinhole_intrinsics_out[4], dsopp_hip_undistorter **out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Image transformers: the resize and the crop behind the undistortion (replaces CameraResizer — src/sensors/camera_transformers/src/
