@@ -117,6 +117,21 @@ class GeometricBADebug(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in GEOMETRIC_BA_DEBUG_FIELDS]
 
 
+GEOMETRIC_BA_PINHOLE, GEOMETRIC_BA_SIMPLE_RADIAL = 0, 1
+GEOMETRIC_BA_FIX_FOCAL, GEOMETRIC_BA_FIX_CENTER, GEOMETRIC_BA_FIX_MODEL_SPECIFIC, GEOMETRIC_BA_FIX_POSES, GEOMETRIC_BA_FIX_LANDMARKS = 1, 2, 4, 8, 16
+
+
+class GeometricBACamera(C.Structure):
+    _fields_ = [("model", C.c_int32), ("fixed", C.c_int32), ("intrinsics", C.c_double * 5), ("max_valid_radius", C.c_double)]
+
+
+GEOMETRIC_BA_CAMERA_DEBUG_FIELDS = ("obs_camera_jacobian", "candidate_intrinsics", "candidate_max_valid_radius")
+
+
+class GeometricBACameraDebug(C.Structure):
+    _fields_ = [("base", GeometricBADebug)] + [(name, C.c_void_p) for name in GEOMETRIC_BA_CAMERA_DEBUG_FIELDS]
+
+
 CAMERA_SIMPLE_RADIAL, CAMERA_TUM_FOV, CAMERA_ATAN = 0, 1, 2
 CAMERA_MAX_K = 16  # DSOPP_HIP_CAMERA_MAX_K
 
@@ -212,6 +227,7 @@ SYMBOLS = [
     "dsopp_hip_rotation_ransac_create", "dsopp_hip_rotation_ransac_destroy", "dsopp_hip_rotation_ransac_estimate",
     "dsopp_hip_geometric_ba_default_options", "dsopp_hip_geometric_ba_create", "dsopp_hip_geometric_ba_destroy", "dsopp_hip_geometric_ba_evaluate",
     "dsopp_hip_geometric_ba_solve", "dsopp_hip_geometric_ba_triangulate", "dsopp_hip_geometric_ba_flag_outliers",
+    "dsopp_hip_geometric_ba_evaluate_camera", "dsopp_hip_geometric_ba_solve_camera",
     "dsopp_hip_pnp_ransac_default_iterations", "dsopp_hip_pnp_ransac_default_options", "dsopp_hip_pnp_ransac_create", "dsopp_hip_pnp_ransac_destroy",
     "dsopp_hip_pnp_ransac_estimate",
     "dsopp_hip_two_view_ransac_default_iterations", "dsopp_hip_two_view_ransac_default_options", "dsopp_hip_two_view_ransac_create",
@@ -1039,6 +1055,73 @@ class GeometricBA:
             records = (GeometricBATrace * res.iterations).from_buffer_copy(bufs["trace"][:res.iterations * C.sizeof(GeometricBATrace)].tobytes())
             bufs["trace"] = [(t.cost_before, t.cost_candidate, t.accepted, t.lambda_) for t in records]
             bufs["system_lambda"] = float(bufs["system_lambda"][0])
+            out.update(bufs)
+        return out
+
+    @staticmethod
+    def camera_record(model, intrinsics, fixed):
+        values = [float(v) for v in intrinsics]
+        assert len(values) in (4, 5), values
+        return GeometricBACamera(int(model), int(fixed), (C.c_double * 5)(*(values + [0.0] * (5 - len(values)))), 0.0)
+
+    @staticmethod
+    def unknowns(model, fixed, num_frames):
+        """(pose unknowns, free intrinsics' indices) of solve_camera's reduced system"""
+        groups = ((GEOMETRIC_BA_FIX_FOCAL, GEOMETRIC_BA_FIX_FOCAL, GEOMETRIC_BA_FIX_CENTER, GEOMETRIC_BA_FIX_CENTER)
+                  if model == GEOMETRIC_BA_PINHOLE else
+                  (GEOMETRIC_BA_FIX_FOCAL, GEOMETRIC_BA_FIX_CENTER, GEOMETRIC_BA_FIX_CENTER, GEOMETRIC_BA_FIX_MODEL_SPECIFIC,
+                   GEOMETRIC_BA_FIX_MODEL_SPECIFIC))
+        return (0 if fixed & GEOMETRIC_BA_FIX_POSES else max(6 * (num_frames - 1) - 1, 0)), [k for k, g in enumerate(groups) if not fixed & g]
+
+    def evaluate_camera(self, size, model, intrinsics, poses, positions, landmark_offsets, obs_frame, obs_xy, fixed=0, a=1.5,
+                        with_observations=False):
+        """evaluate with the camera (model, intrinsics: pinhole fx fy cx cy | simple radial f cx cy k1 k2) on a size = (width, height)
+        image; the dict of evaluate and max_valid_radius; blocking"""
+        pr, keep = self.problem((0.0, 0.0, 0.0, 0.0, size[0], size[1]), poses, positions, landmark_offsets, obs_frame, obs_xy)
+        cam = self.camera_record(model, intrinsics, fixed)
+        m = pr.num_observations
+        cost, nvalid = C.c_double(), C.c_int32()
+        obs = (np.zeros(m, np.uint8), np.zeros((m, 2)), np.zeros(m)) if with_observations else (None, None, None)
+        _chk(lib().dsopp_hip_geometric_ba_evaluate_camera(self._h, C.byref(pr), C.byref(cam), C.c_double(a), C.byref(cost), C.byref(nvalid),
+                                                          _p(obs[0], np.uint8), _p(obs[1]), _p(obs[2])))
+        out = {"cost": cost.value, "valid_residuals": nvalid.value, "max_valid_radius": cam.max_valid_radius}
+        if with_observations:
+            out.update(obs_valid=obs[0], obs_residual=obs[1], obs_weight=obs[2])
+        return out
+
+    def solve_camera(self, size, model, intrinsics, poses, positions, landmark_offsets, obs_frame, obs_xy, fixed=0, options=None, debug=False,
+                     **option_fields):
+        """The LM solve with the camera as a parameter block: `fixed` holds the GEOMETRIC_BA_FIX_* bits.  Returns the dict of solve and
+        intrinsics (4 or 5), max_valid_radius; with debug also the outputs of dsopp_hip_geometric_ba_camera_debug (reduced_H (n, n) with the
+        free intrinsics' rows last, obs_camera_jacobian (M, 2, 5), candidate_intrinsics (5,), candidate_max_valid_radius); blocking"""
+        pr, keep = self.problem((0.0, 0.0, 0.0, 0.0, size[0], size[1]), poses, positions, landmark_offsets, obs_frame, obs_xy)
+        cam = self.camera_record(model, intrinsics, fixed)
+        opt = options if options is not None else default_geometric_ba_options()
+        for k, v in option_fields.items():
+            setattr(opt, k, v)
+        res = GeometricBAResult()
+        f, l, m = pr.num_frames, pr.num_landmarks, pr.num_observations
+        npose, free = self.unknowns(int(model), int(fixed), f)
+        n = npose + len(free)
+        dbg, bufs = None, {}
+        if debug:
+            bufs = dict(obs_valid=np.zeros(m, np.uint8), obs_residual=np.zeros((m, 2)), obs_weight=np.zeros(m), landmark_H=np.zeros((l, 6)),
+                        landmark_b=np.zeros((l, 3)), reduced_H=np.zeros((n, n)), reduced_b=np.zeros(n), pose_step=np.zeros(n),
+                        system_lambda=np.zeros(1), candidate_poses=np.zeros((f, 12)), candidate_positions=np.zeros((l, 3)),
+                        trace=np.zeros(max(int(opt.max_iterations), 1) * C.sizeof(GeometricBATrace), np.uint8),
+                        obs_camera_jacobian=np.zeros((m, 2, 5)), candidate_intrinsics=np.zeros(5), candidate_max_valid_radius=np.zeros(1))
+            dbg = GeometricBACameraDebug(GeometricBADebug(*[bufs[name].ctypes.data for name in GEOMETRIC_BA_DEBUG_FIELDS]),
+                                         *[bufs[name].ctypes.data for name in GEOMETRIC_BA_CAMERA_DEBUG_FIELDS])
+        _chk(lib().dsopp_hip_geometric_ba_solve_camera(self._h, C.byref(pr), C.byref(cam), C.byref(opt), C.byref(res),
+                                                       C.byref(dbg) if debug else None))
+        out = {"poses": keep[0], "positions": keep[1], "intrinsics": np.array(cam.intrinsics[:len(intrinsics)]),
+               "max_valid_radius": cam.max_valid_radius}
+        out.update({name: getattr(res, name) for name, _ in GeometricBAResult._fields_ if name != "reserved"})
+        if debug:
+            records = (GeometricBATrace * res.iterations).from_buffer_copy(bufs["trace"][:res.iterations * C.sizeof(GeometricBATrace)].tobytes())
+            bufs["trace"] = [(t.cost_before, t.cost_candidate, t.accepted, t.lambda_) for t in records]
+            bufs["system_lambda"] = float(bufs["system_lambda"][0])
+            bufs["candidate_max_valid_radius"] = float(bufs["candidate_max_valid_radius"][0])
             out.update(bufs)
         return out
 

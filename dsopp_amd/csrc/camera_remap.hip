@@ -22,6 +22,7 @@
 
 #include "pyramid.hpp"
 #include "remap_fold.hpp"
+#include "simple_radial_radius.hpp"
 #include "undistort.hpp"
 
 namespace dsopp_hip {
@@ -30,7 +31,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kBorder = 4;                   // CameraModelBase::kBorderSize (camera_model_base.hpp:34)
 constexpr double kMaxCentre = 1048576.0;     // 2^20, the bound dsopp_hip_undistorter_create puts on a map entry
-constexpr int kMaxRootSteps = 200;           // as ransac_device.hpp: a bracket of doubles is exhausted long before
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -154,95 +154,6 @@ __global__ void __launch_bounds__(kBlock) remapTableKernel(RemapArgs m, unsigned
 
 // ---- the host side: the model's constants
 
-double evalPolynomial(const double *c, int n, double x) {
-  double v = c[n];
-  for (int i = n - 1; i >= 0; --i) v = v * x + c[i];
-  return v;
-}
-
-double evalPolynomialDerivative(const double *c, int n, double x) {
-  double v = n * c[n];
-  for (int i = n - 1; i >= 1; --i) v = v * x + i * c[i];
-  return v;
-}
-
-/** the middle of a bracket 0 <= lo < hi, geometric where the ends differ in magnitude (ransac_device.hpp: middlePositive) */
-double middlePositive(double lo, double hi) {
-  if (lo == 0.0) return hi > 2.0 ? 1.0 : 0.5 * hi;
-  if (hi > 4.0 * lo) return std::sqrt(lo) * std::sqrt(hi);
-  return 0.5 * (lo + hi);
-}
-
-/** the root inside (lo, hi) of the polynomial, which has the sign of flo at lo and the other sign at hi: the safeguarded Newton iteration
- *  of ransac_device.hpp (bracketedRoot) on the host — bisection whenever Newton leaves the bracket or slows down, run to its fixed point */
-double bracketedRoot(const double *c, int n, double lo, double hi, double flo) {
-  double x = middlePositive(lo, hi), last_step = hi - lo;
-  for (int it = 0; it < kMaxRootSteps; ++it) {
-    const double f = evalPolynomial(c, n, x);
-    if (f == 0.0) return x;
-    if ((f > 0.0) == (flo > 0.0)) {
-      lo = x;
-    } else {
-      hi = x;
-    }
-    const double mid = middlePositive(lo, hi);
-    if (!(mid > lo && mid < hi)) break;  // neighbouring doubles
-    double next = x - f / evalPolynomialDerivative(c, n, x);
-    if (!(next > lo && next < hi) || !(std::fabs(next - x) <= 0.5 * std::fabs(last_step))) next = mid;
-    if (next == x) break;
-    last_step = next - x;
-    x = next;
-  }
-  return x;
-}
-
-/** minimalPositiveRoot (polynomial_solver.hpp:11-41) of c[0] + c[1] r + c[3] r^3 + c[5] r^5 (c[2] = c[4] = 0): the polynomial is
- *  normalised, its leading coefficients below 1e-8 are dropped (:14-19), no coefficient left = 0 (:20-22), no root >= 0 = +inf (:30-40).
- *  Where the reference takes the companion matrix's eigenvalues, the roots of the derivative — a quadratic in r^2, closed form — cut
- *  r >= 0 into stretches on which the polynomial is monotone; the first stretch over which its sign changes holds the least root. */
-double minimalPositiveRoot(double (&c)[6]) {
-  double norm = 0.0;
-  for (double v : c) norm += v * v;
-  norm = std::sqrt(norm);
-  for (double &v : c) v /= norm;
-  int n = 5;
-  while (n > 0 && std::fabs(c[n]) < 1e-8) --n;
-  if (n == 0) return 0.0;
-  if (c[0] == 0.0) return 0.0;
-  // the derivative in t = r^2: qa t^2 + qb t + qc
-  const double qa = n >= 5 ? 5.0 * c[5] : 0.0, qb = n >= 3 ? 3.0 * c[3] : 0.0, qc = c[1];
-  double t[2] = {-1.0, -1.0};
-  if (qa != 0.0) {
-    const double disc = qb * qb - 4.0 * qa * qc;
-    if (disc >= 0.0) {
-      const double q = -0.5 * (qb + std::copysign(std::sqrt(disc), qb));  // the root pair without cancellation
-      t[0] = q / qa;
-      if (q != 0.0) t[1] = qc / q;
-    }
-  } else if (qb != 0.0) {
-    t[0] = -qc / qb;
-  }
-  double stops[3];
-  int num_stops = 0;
-  for (double v : t)
-    if (v > 0.0 && std::isfinite(v)) stops[num_stops++] = std::sqrt(v);
-  if (num_stops == 2 && stops[1] < stops[0]) std::swap(stops[0], stops[1]);
-  double bound = 0.0;  // Cauchy: every root lies below 1 + max |c[i] / c[n]|
-  for (int i = 0; i < n; ++i) bound = std::fmax(bound, std::fabs(c[i] / c[n]));
-  stops[num_stops++] = std::fmin(1.0 + bound, DBL_MAX);
-  double lo = 0.0, flo = c[0];
-  for (int i = 0; i < num_stops; ++i) {
-    const double hi = stops[i];
-    if (!(hi > lo)) continue;
-    const double fhi = evalPolynomial(c, n, hi);
-    if (fhi == 0.0) return hi;
-    if ((fhi > 0.0) != (flo > 0.0)) return bracketedRoot(c, n, lo, hi, flo);
-    lo = hi;
-    flo = fhi;
-  }
-  return std::numeric_limits<double>::infinity();
-}
-
 int expectedNumK(int type) { return type == DSOPP_HIP_CAMERA_SIMPLE_RADIAL ? 2 : type == DSOPP_HIP_CAMERA_TUM_FOV ? 1 : -1; }
 
 /** the refusals of include/dsopp_hip.h */
@@ -278,24 +189,10 @@ void modelToPinhole(const dsopp_hip_camera_model *m, double pinhole[4], double d
   pinhole[3] = static_cast<double>(m->height) / 2;
   derived[0] = derived[1] = derived[2] = 0.0;
   if (!radial) return;
-  const double f = m->params[0], cx = m->params[1], cy = m->params[2], k1 = m->k[0], k2 = m->k[1];
-  const double max_x = std::fmax(cx, static_cast<double>(m->width) - cx), max_y = std::fmax(cy, static_cast<double>(m->height) - cy);
-  double radius = std::sqrt(max_x * max_x + max_y * max_y) / f;
-  double polynomial[6] = {-radius, 1.0, 0.0, k1, 0.0, k2};
-  radius = minimalPositiveRoot(polynomial);
-  // the first extremum of r + k1 r^3 + k2 r^5, as written (:62-77): with k2 == 0 the divisions give NaN or inf and the comparisons decide
-  const double discriminant = 9.0 * k1 * k1 - 20.0 * k2;
-  if (discriminant >= 0.0) {
-    const double root1_2 = (-3.0 * k1 - std::sqrt(discriminant)) / 10.0 / k2;
-    const double root2_2 = (-3.0 * k1 + std::sqrt(discriminant)) / 10.0 / k2;
-    double root = radius;
-    if (root1_2 > 0.0) {
-      root = std::sqrt(root1_2);
-    } else if (root2_2 > 0.0) {
-      root = std::sqrt(root2_2);
-    }
-    if (root < radius) radius = root - static_cast<double>(kBorder) / f;
-  }
+  const double k1 = m->k[0], k2 = m->k[1];
+  // the root finder and the extremum rule are simple_radial_radius.hpp's, shared with the geometric bundle adjustment's kernels
+  const double radius = dsopp_hip::radial::maxValidRadius(static_cast<double>(m->width), static_cast<double>(m->height), m->params[0], m->params[1],
+                                                          m->params[2], k1, k2);
   const double r2 = radius * radius, r4 = r2 * r2;
   derived[0] = radius;
   derived[1] = 1.0 + 3.0 * k1 * r2 + 5.0 * k2 * r4;

@@ -23,8 +23,21 @@
 //   decide     one workgroup: the fixed-order sums of the candidate cost and the norms, the LM driver's decision, the accepted state.
 // No workgroup waits for another, no floating-point atomics: two calls with the same inputs return the same bytes.  The host enqueues
 // the iterations in groups and reads the state record between groups.
+//
+// The camera block (dsopp_hip_geometric_ba_evaluate_camera / _solve_camera: optimizeTransformations<Model, OPTIMIZE_CAMERA>, the intrinsics
+// of a pinhole or simple-radial camera as a third parameter block, ParameterParameterization's five fix flags) is the CAM instance of
+// the same five kernels; what the entry points without a camera launch is the instance without it, whose arithmetic is untouched.
+//   linearise  also stores per observation dr/dc (2 x 5) and w J_x^T J_c (3 x 5), over all five parameter slots: which of them are free
+//              is decided where the system is assembled.
+//   reduce     behind the frame pairs a workgroup per free frame (H_pc and S_fc = sum_l Y_f^T Y_c) and one for the camera (H_cc, b_c,
+//              S_cc, s_c), each with its own 60 or 40 accumulators in place of the pairs' 84: the roles are uniform per workgroup.
+//              Without a free intrinsic nothing reads their sums and, with free poses, they are not launched.
+//   solve      up to 89 + 5 unknowns, the free intrinsics' rows last; the candidate camera, its max_valid_radius
+//              (simple_radial_radius.hpp, on one thread) and the rule that fails the step.
+//   update     adds W_lc delta_c and evaluates with the candidate camera; decide accepts it with the state.
 #include "common.hpp"
 #include "se3_math.hpp"
+#include "simple_radial_radius.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -39,6 +52,8 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxFrames = 16;
 constexpr int kMaxUnknowns = 6 * (kMaxFrames - 1) - 1;  // 89
+constexpr int kCam = 5;                                 // the intrinsics of the widest camera model
+constexpr int kFixPoses = DSOPP_HIP_GEOMETRIC_BA_FIX_POSES, kFixLandmarks = DSOPP_HIP_GEOMETRIC_BA_FIX_LANDMARKS;
 constexpr int kJacobiSweeps = 30;                       // a 4 x 4 Jacobi converges in 5 .. 8 sweeps; the cap bounds the loop for NaN input
 constexpr int kDefaultGroup = 8;
 
@@ -62,7 +77,30 @@ struct GbaParams {
   double *Spair, *Hpp, *bp, *rs, *delta6, *sysH, *sysb, *sysx;
   GbaState *st;
   dsopp_hip_geometric_ba_trace *trace;
+  // the camera block (the *_camera entry points; the kernels' CAM instances): the model, the fixed bits, the pose unknowns (0 with fixed
+  // poses), the free intrinsics in parameter order
+  int model, fixed, npose, ncam, cidx[kCam];
+  double width, height;
+  double *camrec;  // intrinsics[5], max_valid_radius, 2 unused; the candidate's likewise
+  double *Jc, *Wc;  // per observation dr/dc (2 x 5) and w J_x^T J_c (3 x 5)
+  double *Hpc, *Sfc, *camsum, *deltac;  // F x (6 x 5) twice; H_cc (15, packed lower), b_c (5), S_cc (15), s_c (5); the step over all five
 };
+
+/** a camera as the kernels read it */
+struct Camera {
+  int model;
+  double c[kCam], radius;
+};
+
+__device__ __forceinline__ Camera loadCamera(const GbaParams &p, bool candidate) {
+  Camera cam;
+  cam.model = p.model;
+  const double *rec = p.camrec + (candidate ? 8 : 0);
+#pragma unroll
+  for (int k = 0; k < kCam; ++k) cam.c[k] = rec[k];
+  cam.radius = rec[5];
+  return cam;
+}
 
 __device__ __forceinline__ bool insideRoi(double x, double y, const GbaParams &p) { return x >= 4.0 && x <= p.xmax && y >= 4.0 && y <= p.ymax; }
 
@@ -75,6 +113,26 @@ __device__ __forceinline__ bool project(const double *T, const double *X, const 
   q[0] = p.fx * pc[0] / pc[2] + p.cx;
   q[1] = p.fy * pc[1] / pc[2] + p.cy;
   return insideRoi(q[0], q[1], p);
+}
+
+/** the same for a camera of the camera block.  Pinhole: as above.  Simple radial (simple_radial.hpp:133-160): u = p_x / p_z, v = p_y / p_z,
+ *  rho2 = u u + v v, d = (1 + k1 rho2) + (k2 rho2) rho2, q = f (d (u, v)) + (cx, cy); false when sqrt(rho2) > max_valid_radius or q leaves
+ *  the ROI; no test on p_z */
+__device__ __forceinline__ bool projectCamera(const double *T, const double *X, const GbaParams &p, const Camera &cam, double *pc, double *q) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) pc[r] = T[3 * r] * X[0] + T[3 * r + 1] * X[1] + T[3 * r + 2] * X[2] + T[9 + r];
+  q[0] = q[1] = 0.0;
+  if (cam.model == DSOPP_HIP_GEOMETRIC_BA_PINHOLE) {
+    if (!(pc[2] >= 0.001)) return false;
+    q[0] = cam.c[0] * pc[0] / pc[2] + cam.c[2];
+    q[1] = cam.c[1] * pc[1] / pc[2] + cam.c[3];
+    return insideRoi(q[0], q[1], p);
+  }
+  const double u = pc[0] / pc[2], v = pc[1] / pc[2], rho2 = u * u + v * v;
+  const double d = (1.0 + cam.c[3] * rho2) + (cam.c[4] * rho2) * rho2;
+  q[0] = cam.c[0] * (d * u) + cam.c[1];
+  q[1] = cam.c[0] * (d * v) + cam.c[2];
+  return sqrt(rho2) <= cam.radius && insideRoi(q[0], q[1], p);
 }
 
 /** Huber: the weight rho'(s) and rho(s) */
@@ -90,9 +148,16 @@ __device__ __forceinline__ void huber(double s, double a, double &w, double &rho
 }
 
 /** the residual of one observation: valid, r (0 when invalid) */
-__device__ __forceinline__ bool residualOf(const double *T, const double *X, const double *obs, const GbaParams &p, double *r, double *pc) {
+template <bool CAM>
+__device__ __forceinline__ bool residualOf(const double *T, const double *X, const double *obs, const GbaParams &p, const Camera &cam, double *r,
+                                           double *pc) {
   double q[2];
-  const bool ok = project(T, X, p, pc, q);
+  bool ok;
+  if constexpr (CAM) {
+    ok = projectCamera(T, X, p, cam, pc, q);
+  } else {
+    ok = project(T, X, p, pc, q);
+  }
   r[0] = ok ? obs[0] - q[0] : 0.0;
   r[1] = ok ? obs[1] - q[1] : 0.0;
   return ok;
@@ -185,10 +250,70 @@ __device__ __forceinline__ double blockSum(double v, double *s_wave) {
 
 // ---------------------------------------------------------------------------------------------------------------- linearise
 
+/** the camera block of one valid observation: J_x = -G R (2 x 3) and J_c = dr / dc (2 x 5; a pinhole's fifth column is zero) */
+__device__ __forceinline__ void cameraJacobians(const double *T, const double *pc, const Camera &cam, double J[2][3], double Jc[2][kCam]) {
+  if (cam.model == DSOPP_HIP_GEOMETRIC_BA_PINHOLE) {
+    // J_x exactly as the instance without a camera block has it
+    const double fx = cam.c[0], fy = cam.c[1];
+    const double iz = 1.0 / pc[2];
+    const double g00 = fx * iz, g02 = -fx * pc[0] * iz * iz, g11 = fy * iz, g12 = -fy * pc[1] * iz * iz;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      J[0][k] = -(g00 * T[k] + g02 * T[6 + k]);
+      J[1][k] = -(g11 * T[3 + k] + g12 * T[6 + k]);
+    }
+    const double u = pc[0] / pc[2], v = pc[1] / pc[2];
+    Jc[0][0] = -u;
+    Jc[0][1] = 0.0;
+    Jc[0][2] = -1.0;
+    Jc[0][3] = 0.0;
+    Jc[0][4] = 0.0;
+    Jc[1][0] = 0.0;
+    Jc[1][1] = -v;
+    Jc[1][2] = 0.0;
+    Jc[1][3] = -1.0;
+    Jc[1][4] = 0.0;
+    return;
+  }
+  // simple radial: G as simple_radial.hpp:190-199 writes it
+  const double f = cam.c[0], k1 = cam.c[3], k2 = cam.c[4];
+  const double x = pc[0], y = pc[1], z = pc[2];
+  const double u = x / z, v = y / z, rho2 = u * u + v * v;
+  const double d = (1.0 + k1 * rho2) + (k2 * rho2) * rho2;
+  const double common = (2.0 * k1 + 4.0 * k2 * rho2) / z / z;
+  const double last = -3.0 * k1 * rho2 - 5.0 * k2 * rho2 * rho2 - 1.0;
+  double G[2][3];
+  G[0][0] = f * (x * x * common + d) / z;
+  G[0][1] = f * x * y * common / z;
+  G[1][0] = G[0][1];
+  G[1][1] = f * (y * y * common + d) / z;
+  G[0][2] = f * x / z / z * last;
+  G[1][2] = f * y / z / z * last;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    J[0][k] = -(G[0][0] * T[k] + G[0][1] * T[3 + k] + G[0][2] * T[6 + k]);
+    J[1][k] = -(G[1][0] * T[k] + G[1][1] * T[3 + k] + G[1][2] * T[6 + k]);
+  }
+  const double f2 = f * rho2, f4 = f * (rho2 * rho2);
+  Jc[0][0] = -(d * u);
+  Jc[0][1] = -1.0;
+  Jc[0][2] = 0.0;
+  Jc[0][3] = -(f2 * u);
+  Jc[0][4] = -(f4 * u);
+  Jc[1][0] = -(d * v);
+  Jc[1][1] = 0.0;
+  Jc[1][2] = -1.0;
+  Jc[1][3] = -(f2 * v);
+  Jc[1][4] = -(f4 * v);
+}
+
+template <bool CAM>
 __global__ void __launch_bounds__(kBlock) gbaLinearise(const GbaParams p) {
   if (p.st->done || !p.st->relin) return;
   const int l = static_cast<int>(blockIdx.x) * kBlock + threadIdx.x;
   if (l >= p.L) return;
+  Camera cam;
+  if constexpr (CAM) cam = loadCamera(p, false);
   const double X[3] = {p.X[3 * static_cast<size_t>(l)], p.X[3 * static_cast<size_t>(l) + 1], p.X[3 * static_cast<size_t>(l) + 2]};
   double H[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0}, cost = 0.0;
   int nv = 0;
@@ -196,20 +321,41 @@ __global__ void __launch_bounds__(kBlock) gbaLinearise(const GbaParams p) {
     const double *T = p.poses + 12 * static_cast<size_t>(p.ofr[o]);
     const double obs[2] = {p.oxy[2 * static_cast<size_t>(o)], p.oxy[2 * static_cast<size_t>(o) + 1]};
     double r[2], pc[3], w = 0.0, C[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, c[3] = {0.0, 0.0, 0.0};
-    const bool ok = residualOf(T, X, obs, p, r, pc);
+    const bool ok = residualOf<CAM>(T, X, obs, p, cam, r, pc);
+    if constexpr (CAM) {
+      // the camera's columns: zero for an observation that is not valid
+      double *Jo = p.Jc + 2 * kCam * static_cast<size_t>(o), *Wo = p.Wc + 3 * kCam * static_cast<size_t>(o);
+#pragma unroll
+      for (int k = 0; k < 2 * kCam; ++k) Jo[k] = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3 * kCam; ++k) Wo[k] = 0.0;
+    }
     if (ok) {
       double rho;
       huber(r[0] * r[0] + r[1] * r[1], p.a, w, rho);
       cost += rho;
       ++nv;
       // J_x = -G R, G = dq / dp
-      const double iz = 1.0 / pc[2];
-      const double g00 = p.fx * iz, g02 = -p.fx * pc[0] * iz * iz, g11 = p.fy * iz, g12 = -p.fy * pc[1] * iz * iz;
       double J[2][3];
+      if constexpr (CAM) {
+        double Jc[2][kCam];
+        cameraJacobians(T, pc, cam, J, Jc);
+        double *Jo = p.Jc + 2 * kCam * static_cast<size_t>(o), *Wo = p.Wc + 3 * kCam * static_cast<size_t>(o);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        J[0][k] = -(g00 * T[k] + g02 * T[6 + k]);
-        J[1][k] = -(g11 * T[3 + k] + g12 * T[6 + k]);
+        for (int a = 0; a < kCam; ++a) {
+          Jo[a] = Jc[0][a];
+          Jo[kCam + a] = Jc[1][a];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) Wo[kCam * k + a] = w * (J[0][k] * Jc[0][a] + J[1][k] * Jc[1][a]);
+        }
+      } else {
+        const double iz = 1.0 / pc[2];
+        const double g00 = p.fx * iz, g02 = -p.fx * pc[0] * iz * iz, g11 = p.fy * iz, g12 = -p.fy * pc[1] * iz * iz;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          J[0][k] = -(g00 * T[k] + g02 * T[6 + k]);
+          J[1][k] = -(g11 * T[3 + k] + g12 * T[6 + k]);
+        }
       }
       C[0] = w * (J[0][0] * J[0][0] + J[1][0] * J[1][0]);
       C[1] = w * (J[0][0] * J[0][1] + J[1][0] * J[1][1]);
@@ -302,8 +448,138 @@ __device__ __forceinline__ int pairIndex(int F, int fa, int fb) {  // 1 <= fa <=
   return a * n - a * (a - 1) / 2 + (fb - fa);
 }
 
+/** W_lc = sum over the landmark's observations, in list order, of w J_x^T J_c (3 x 5) */
+__device__ __forceinline__ void landmarkCameraBlock(const GbaParams &p, int l, double W[3][kCam]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int a = 0; a < kCam; ++a) W[r][a] = 0.0;
+  for (int o = p.off[l]; o < p.off[l + 1]; ++o) {
+    const double *Wo = p.Wc + 3 * kCam * static_cast<size_t>(o);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int a = 0; a < kCam; ++a) W[r][a] += Wo[kCam * r + a];
+  }
+}
+
+/** Y_c = L^-1 W_lc, 3 x 5 */
+__device__ __forceinline__ void cameraSchurFactor(const double *Li, const double W[3][kCam], double Y[3][kCam]) {
+#pragma unroll
+  for (int a = 0; a < kCam; ++a) {
+    const double v[3] = {W[0][a], W[1][a], W[2][a]};
+    double y[3];
+    lowerApply(Li, v, y);
+    Y[0][a] = y[0];
+    Y[1][a] = y[1];
+    Y[2][a] = y[2];
+  }
+}
+
+/** the workgroup's sums of `count` values a thread: every value down its wave's butterfly, one barrier, then the waves in order into out */
+template <int kCount>
+__device__ __forceinline__ void blockSums(const double *v, double (*s_part)[84], double *out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kCount; ++k) {
+    const double s = waveSum(v[k]);
+    if (lane == 0) s_part[wave][k] = s;
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < kCount) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += s_part[w][k];
+    out[k] = s;
+  }
+}
+
+/** the (frame f, camera) workgroup: H_pc = sum A^T (w J_x^T J_c) over the frame's observations and S_fc = sum_l Y_f^T Y_c */
+__device__ __forceinline__ void reduceFrameCamera(const GbaParams &p, int f, double lambda, double (*s_part)[84]) {
+  double acc[2 * 6 * kCam];  // H_pc, then S_fc
+#pragma unroll
+  for (int k = 0; k < 2 * 6 * kCam; ++k) acc[k] = 0.0;
+  const bool eliminate = !(p.fixed & kFixLandmarks);
+  for (int l = threadIdx.x; l < p.L; l += kBlock) {
+    const int oa = observationIn(p, l, f);
+    if (oa < 0) continue;
+    const double X[3] = {p.X[3 * static_cast<size_t>(l)], p.X[3 * static_cast<size_t>(l) + 1], p.X[3 * static_cast<size_t>(l) + 2]};
+    double A[3][6];
+    poseMap(X, A);
+    const double *Wo = p.Wc + 3 * kCam * static_cast<size_t>(oa);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int a = 0; a < kCam; ++a) acc[kCam * r + a] += A[0][r] * Wo[a] + A[1][r] * Wo[kCam + a] + A[2][r] * Wo[2 * kCam + a];
+    double Li[6];
+    if (!eliminate || !landmarkFactor(p.Hll + 6 * static_cast<size_t>(l), lambda, Li)) continue;
+    double Ya[3][6], W[3][kCam], Yc[3][kCam];
+    schurFactor(Li, p.C + 9 * static_cast<size_t>(oa), A, Ya);
+    landmarkCameraBlock(p, l, W);
+    cameraSchurFactor(Li, W, Yc);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int a = 0; a < kCam; ++a) acc[6 * kCam + kCam * r + a] += Ya[0][r] * Yc[0][a] + Ya[1][r] * Yc[1][a] + Ya[2][r] * Yc[2][a];
+  }
+  // Hpc and Sfc lie one behind the other, F x 30 each
+  blockSums<6 * kCam>(acc, s_part, p.Hpc + 6 * kCam * static_cast<size_t>(f));
+  __syncthreads();
+  blockSums<6 * kCam>(acc + 6 * kCam, s_part, p.Sfc + 6 * kCam * static_cast<size_t>(f));
+}
+
+/** the (camera, camera) workgroup: H_cc = sum w J_c^T J_c, b_c = sum w J_c^T r, S_cc = sum_l Y_c^T Y_c, s_c = sum_l Y_c^T L^-1 b_l */
+__device__ __forceinline__ void reduceCameraCamera(const GbaParams &p, double lambda, double (*s_part)[84]) {
+  double acc[40];  // H_cc (15, packed lower), b_c (5), S_cc (15), s_c (5)
+#pragma unroll
+  for (int k = 0; k < 40; ++k) acc[k] = 0.0;
+  const bool eliminate = !(p.fixed & kFixLandmarks);
+  for (int l = threadIdx.x; l < p.L; l += kBlock) {
+    for (int o = p.off[l]; o < p.off[l + 1]; ++o) {
+      const double *Jo = p.Jc + 2 * kCam * static_cast<size_t>(o);
+      const double w = p.wgt[o], r0 = p.res[2 * static_cast<size_t>(o)], r1 = p.res[2 * static_cast<size_t>(o) + 1];
+#pragma unroll
+      for (int a = 0; a < kCam; ++a) {
+#pragma unroll
+        for (int b = 0; b <= a; ++b) acc[a * (a + 1) / 2 + b] += w * (Jo[a] * Jo[b] + Jo[kCam + a] * Jo[kCam + b]);
+        acc[15 + a] += w * (Jo[a] * r0 + Jo[kCam + a] * r1);
+      }
+    }
+    double Li[6];
+    if (!eliminate || !landmarkFactor(p.Hll + 6 * static_cast<size_t>(l), lambda, Li)) continue;
+    double W[3][kCam], Yc[3][kCam], z[3];
+    landmarkCameraBlock(p, l, W);
+    cameraSchurFactor(Li, W, Yc);
+    lowerApply(Li, p.bl + 3 * static_cast<size_t>(l), z);
+#pragma unroll
+    for (int a = 0; a < kCam; ++a) {
+#pragma unroll
+      for (int b = 0; b <= a; ++b) acc[20 + a * (a + 1) / 2 + b] += Yc[0][a] * Yc[0][b] + Yc[1][a] * Yc[1][b] + Yc[2][a] * Yc[2][b];
+      acc[35 + a] += Yc[0][a] * z[0] + Yc[1][a] * z[1] + Yc[2][a] * z[2];
+    }
+  }
+  blockSums<40>(acc, s_part, p.camsum);
+}
+
+/** The workgroups of the instance with a camera block: the frame pairs first (none with fixed poses), then a (frame, camera) workgroup
+ *  per free frame, then the (camera, camera) workgroup (the host leaves the last two out when no intrinsic is free). */
+template <bool CAM>
 __global__ void __launch_bounds__(kBlock) gbaReduce(const GbaParams p) {
+  __shared__ double s_part[kBlock / 64][84];
   if (p.st->done) return;
+  if constexpr (CAM) {
+    const int pairs = p.npose > 0 ? (p.F - 1) * p.F / 2 : 0, frames = p.npose > 0 ? p.F - 1 : 0;
+    const int role = static_cast<int>(blockIdx.x) - pairs;
+    if (role >= frames) {
+      reduceCameraCamera(p, p.st->lambda, s_part);
+      return;
+    }
+    if (role >= 0) {
+      reduceFrameCamera(p, 1 + role, p.st->lambda, s_part);
+      return;
+    }
+  }
   int fa = 1, rest = static_cast<int>(blockIdx.x);
   while (rest >= p.F - fa) {
     rest -= p.F - fa;
@@ -340,6 +616,9 @@ __global__ void __launch_bounds__(kBlock) gbaReduce(const GbaParams p) {
         bpv[r] += A[0][r] * Ca[6] + A[1][r] * Ca[7] + A[2][r] * Ca[8];
       }
     }
+    if constexpr (CAM) {
+      if (p.fixed & kFixLandmarks) continue;  // no elimination: S = 0
+    }
     double Li[6];
     if (!landmarkFactor(p.Hll + 6 * static_cast<size_t>(l), lambda, Li)) continue;
     double Ya[3][6], Yb[3][6];
@@ -362,7 +641,6 @@ __global__ void __launch_bounds__(kBlock) gbaReduce(const GbaParams p) {
       for (int c = 0; c < 6; ++c) acc[6 * r + c] += Ya[0][r] * Yb[0][c] + Ya[1][r] * Yb[1][c] + Ya[2][r] * Yb[2][c];
   }
   // the workgroup's sums: every value down its wave's butterfly (independent chains), one barrier, then the four waves in order
-  __shared__ double s_part[kBlock / 64][84];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 36; ++k) {
@@ -430,16 +708,23 @@ __device__ __forceinline__ Unknown unknownOf(int i, const double Bt[3][2]) {
 
 __device__ __forceinline__ int packed(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
 
+/** entry (a, b) of a camera sum's packed lower triangle */
+__device__ __forceinline__ double packedSym(const double *v, int a, int b) { return a >= b ? v[packed(a, b)] : v[packed(b, a)]; }
+
+template <bool CAM>
 __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
-  __shared__ double s_L[(kMaxUnknowns + 1) * (kMaxUnknowns + 2) / 2];  // the lower triangle, packed; row n is the right-hand side
-  __shared__ double s_x[kMaxUnknowns];
+  constexpr int kUnknowns = kMaxUnknowns + (CAM ? kCam : 0);       // 89, or 94 with the camera's rows behind the poses'
+  __shared__ double s_L[(kUnknowns + 1) * (kUnknowns + 2) / 2];  // the lower triangle, packed; row n is the right-hand side
+  __shared__ double s_x[kUnknowns];
   __shared__ double s_Bt[3][2], s_basis[6];
   __shared__ int s_fail;
   if (p.st->done) return;
-  const int tid = threadIdx.x, n = 6 * (p.F - 1) - 1;
+  const int tid = threadIdx.x;
+  const int npose = CAM ? p.npose : 6 * (p.F - 1) - 1, n = CAM ? p.npose + p.ncam : npose;
   const double lambda = p.st->lambda;
   const double *T1 = p.poses + 12;
-  if (tid == 0) {
+  if (tid == 0) s_fail = 0;
+  if (tid == 0 && npose > 0) {
     // frame 1: t = |t_1| d; the tangent directions b1, b2 at d; upsilon = R^T |t_1| (alpha b1 + beta b2)
     const double tn = sqrt(T1[9] * T1[9] + T1[10] * T1[10] + T1[11] * T1[11]);
     const double d[3] = {T1[9] / tn, T1[10] / tn, T1[11] / tn};
@@ -452,7 +737,6 @@ __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
       s_basis[r] = b1[r];
       s_basis[3 + r] = b2[r];
     }
-    s_fail = 0;
   }
   __syncthreads();
   double Bt[3][2];
@@ -467,6 +751,31 @@ __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
     while (packed(i, 0) > e) --i;
     while (packed(i + 1, 0) <= e) ++i;
     const int j = e - packed(i, 0);
+    if constexpr (CAM) {
+      if (i >= npose) {
+        // a camera row: H_pc - S_fc through the frame's basis, then H_cc - S_cc with the damping on its own diagonal
+        const int a = p.cidx[i - npose];
+        double v;
+        if (j < npose) {
+          const Unknown uj = unknownOf(j, Bt);
+          const double *H = p.Hpc + 6 * kCam * static_cast<size_t>(uj.frame), *S = p.Sfc + 6 * kCam * static_cast<size_t>(uj.frame);
+          double hp = 0.0, sc = 0.0;
+          for (int b = 0; b < uj.count; ++b) {
+            hp += uj.coef[b] * H[kCam * (uj.first + b) + a];
+            sc += uj.coef[b] * S[kCam * (uj.first + b) + a];
+          }
+          v = hp - sc;
+        } else {
+          const int b = p.cidx[j - npose];
+          const double hp = packedSym(p.camsum, a, b), sc = packedSym(p.camsum + 20, a, b);
+          v = (hp - sc) + (i == j ? lambda * hp : 0.0);
+        }
+        s_L[e] = v;
+        p.sysH[static_cast<size_t>(i) * n + j] = v;
+        p.sysH[static_cast<size_t>(j) * n + i] = v;
+        continue;
+      }
+    }
     const Unknown ui = unknownOf(i, Bt), uj = unknownOf(j, Bt);  // uj.frame <= ui.frame
     const double *S = p.Spair + 36 * static_cast<size_t>(pairIndex(p.F, uj.frame, ui.frame));
     const double *H = p.Hpp + 36 * static_cast<size_t>(ui.frame);
@@ -483,6 +792,15 @@ __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
     p.sysH[static_cast<size_t>(j) * n + i] = v;
   }
   for (int i = tid; i < n; i += kBlock) {
+    if constexpr (CAM) {
+      if (i >= npose) {
+        const int a = p.cidx[i - npose];
+        const double g = p.camsum[15 + a] - p.camsum[35 + a];
+        s_L[packed(n, i)] = -g;
+        p.sysb[i] = -g;
+        continue;
+      }
+    }
     const Unknown u = unknownOf(i, Bt);
     double g = 0.0;
     for (int a = 0; a < u.count; ++a) g += u.coef[a] * (p.bp[6 * u.frame + u.first + a] - p.rs[6 * u.frame + u.first + a]);
@@ -536,7 +854,7 @@ __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
     const double *T = p.poses + 12 * static_cast<size_t>(f);
     double *Tc = p.cand_poses + 12 * static_cast<size_t>(f);
     double d6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (f == 0 || failed) {
+    if (f == 0 || failed || npose == 0) {
 #pragma unroll
       for (int k = 0; k < 12; ++k) Tc[k] = T[k];
     } else if (f == 1) {
@@ -576,21 +894,46 @@ __global__ void __launch_bounds__(kBlock) gbaSolve(const GbaParams p) {
   }
   if (tid == 0) {
     double step = 0.0, state = 0.0;
-    for (int i = 0; i < n; ++i) step += s_x[i] * s_x[i];
-    for (int f = 1; f < p.F; ++f) {
+    for (int i = 0; i < n; ++i) step += s_x[i] * s_x[i];  // (the camera's step is among them)
+    for (int f = 1; f < p.F && npose > 0; ++f) {
       const double *t = p.poses + 12 * static_cast<size_t>(f) + 9;
       state += t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + 1.0;
+    }
+    bool camera_failed = false;
+    if constexpr (CAM) {
+      // the candidate camera c + delta_c, its radius, and the rule that fails the step
+      double dc[kCam] = {0.0, 0.0, 0.0, 0.0, 0.0}, c[kCam];
+      for (int k = 0; k < p.ncam; ++k) {
+        dc[p.cidx[k]] = s_x[npose + k];
+        state += p.camrec[p.cidx[k]] * p.camrec[p.cidx[k]];
+      }
+      for (int k = 0; k < kCam; ++k) {
+        c[k] = p.camrec[k] + dc[k];
+        p.deltac[k] = dc[k];
+        p.camrec[8 + k] = c[k];
+        if (!(fabs(c[k]) <= DBL_MAX)) camera_failed = true;
+      }
+      double radius = 0.0;
+      if (p.model == DSOPP_HIP_GEOMETRIC_BA_PINHOLE) {
+        if (!(c[0] > 0.0) || !(c[1] > 0.0)) camera_failed = true;
+      } else {
+        if (!(c[0] > 0.0)) camera_failed = true;
+        radius = radial::maxValidRadius(p.width, p.height, c[0], c[1], c[2], c[3], c[4]);
+        if (!(radius > 0.0) || !(radius <= DBL_MAX)) camera_failed = true;
+      }
+      p.camrec[13] = radius;
     }
     GbaState &s = *p.st;
     s.step_sq = step;
     s.state_sq = state;
     s.system_lambda = lambda;
-    s.solve_failed = failed ? 1 : 0;
+    s.solve_failed = failed || camera_failed ? 1 : 0;
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- update
 
+template <bool CAM>
 __global__ void __launch_bounds__(kBlock) gbaUpdate(const GbaParams p) {
   if (p.st->done) return;
   const int l = static_cast<int>(blockIdx.x) * kBlock + threadIdx.x;
@@ -598,7 +941,13 @@ __global__ void __launch_bounds__(kBlock) gbaUpdate(const GbaParams p) {
   const double lambda = p.st->lambda;
   const double X[3] = {p.X[3 * static_cast<size_t>(l)], p.X[3 * static_cast<size_t>(l) + 1], p.X[3 * static_cast<size_t>(l) + 2]};
   double Li[6], d[3] = {0.0, 0.0, 0.0};
-  if (landmarkFactor(p.Hll + 6 * static_cast<size_t>(l), lambda, Li)) {
+  Camera cam;
+  bool moves = true;  // fixed landmarks take no step
+  if constexpr (CAM) {
+    cam = loadCamera(p, true);
+    moves = !(p.fixed & kFixLandmarks);
+  }
+  if (moves && landmarkFactor(p.Hll + 6 * static_cast<size_t>(l), lambda, Li)) {
     // delta_l = -(H_ll + lambda D)^-1 (b_l + sum_f W_f^T delta_f), W_f^T delta_f = C (upsilon + omega x X)
     double v[3] = {p.bl[3 * static_cast<size_t>(l)], p.bl[3 * static_cast<size_t>(l) + 1], p.bl[3 * static_cast<size_t>(l) + 2]};
     for (int o = p.off[l]; o < p.off[l + 1]; ++o) {
@@ -608,6 +957,18 @@ __global__ void __launch_bounds__(kBlock) gbaUpdate(const GbaParams p) {
       loadSym(p.C + 9 * static_cast<size_t>(o), C);
 #pragma unroll
       for (int r = 0; r < 3; ++r) v[r] += C[r][0] * u[0] + C[r][1] * u[1] + C[r][2] * u[2];
+    }
+    if (CAM && p.ncam > 0) {
+      // + W_lc delta_c, W_lc the landmark's sum as the reducers take it
+      double W[3][kCam];
+      landmarkCameraBlock(p, l, W);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double t = 0.0;
+#pragma unroll
+        for (int a = 0; a < kCam; ++a) t += W[r][a] * p.deltac[a];
+        v[r] += t;
+      }
     }
     double y[3];
     lowerApply(Li, v, y);
@@ -621,7 +982,7 @@ __global__ void __launch_bounds__(kBlock) gbaUpdate(const GbaParams p) {
   for (int o = p.off[l]; o < p.off[l + 1]; ++o) {
     const double obs[2] = {p.oxy[2 * static_cast<size_t>(o)], p.oxy[2 * static_cast<size_t>(o) + 1]};
     double r[2], pc[3];
-    if (residualOf(p.cand_poses + 12 * static_cast<size_t>(p.ofr[o]), Xc, obs, p, r, pc)) {
+    if (residualOf<CAM>(p.cand_poses + 12 * static_cast<size_t>(p.ofr[o]), Xc, obs, p, cam, r, pc)) {
       double w, rho;
       huber(r[0] * r[0] + r[1] * r[1], p.a, w, rho);
       cost += rho;
@@ -632,12 +993,13 @@ __global__ void __launch_bounds__(kBlock) gbaUpdate(const GbaParams p) {
   for (int k = 0; k < 3; ++k) p.candX[3 * static_cast<size_t>(l) + k] = Xc[k];
   p.lm[4 * static_cast<size_t>(l) + 1] = cost;
   p.lm[4 * static_cast<size_t>(l) + 2] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-  p.lm[4 * static_cast<size_t>(l) + 3] = X[0] * X[0] + X[1] * X[1] + X[2] * X[2];
+  p.lm[4 * static_cast<size_t>(l) + 3] = moves ? X[0] * X[0] + X[1] * X[1] + X[2] * X[2] : 0.0;  // fixed landmarks: no part in the state norm
   p.lmn[2 * static_cast<size_t>(l) + 1] = nv;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- decide
 
+template <bool CAM>
 __global__ void __launch_bounds__(kBlock) gbaDecide(const GbaParams p) {
   __shared__ double s_wave[kBlock / 64];
   __shared__ int s_accept;
@@ -697,6 +1059,9 @@ __global__ void __launch_bounds__(kBlock) gbaDecide(const GbaParams p) {
   if (!s_accept) return;
   for (int k = threadIdx.x; k < 3 * p.L; k += kBlock) p.X[k] = p.candX[k];
   for (int k = threadIdx.x; k < 12 * p.F; k += kBlock) p.poses[k] = p.cand_poses[k];
+  if constexpr (CAM) {
+    if (threadIdx.x < 6) p.camrec[threadIdx.x] = p.camrec[8 + threadIdx.x];  // the intrinsics and their radius
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- pruning, triangulation
@@ -708,7 +1073,7 @@ __global__ void __launch_bounds__(kBlock) gbaFlagOutliers(const GbaParams p, dou
   for (int o = p.off[l]; o < p.off[l + 1]; ++o) {
     const double obs[2] = {p.oxy[2 * static_cast<size_t>(o)], p.oxy[2 * static_cast<size_t>(o) + 1]};
     double r[2], pc[3];
-    const bool ok = residualOf(p.poses + 12 * static_cast<size_t>(p.ofr[o]), X, obs, p, r, pc);
+    const bool ok = residualOf<false>(p.poses + 12 * static_cast<size_t>(p.ofr[o]), X, obs, p, Camera(), r, pc);
     flags[o] = (!ok || sqrt(r[0] * r[0] + r[1] * r[1]) > threshold) ? 1 : 0;
   }
 }
@@ -833,14 +1198,15 @@ size_t aligned(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255);
 struct GbaLayout {
   size_t state, poses, X, oxy, off, ofr, has, upload_end;
   size_t cand_poses, candX, C, res, wgt, valid, Hll, bl, lm, lmn, Spair, Hpp, bp, rs, delta6, sysH, sysb, sysx, trace, flags, bytes;
-  GbaLayout(size_t F, size_t L, size_t M, size_t max_it) {
+  size_t camrec, Jc, Wc, Hpc, Sfc, camsum, deltac;  // the camera block: sized only for the *_camera calls
+  GbaLayout(size_t F, size_t L, size_t M, size_t max_it, bool camera = false) {
     size_t at = 0;
     auto take = [&](size_t bytes) {
       const size_t here = at;
       at += aligned(bytes);
       return here;
     };
-    const size_t n = 6 * (F > 1 ? F - 1 : 1), pairs = F * (F + 1) / 2;
+    const size_t n = 6 * (F > 1 ? F - 1 : 1) + (camera ? kCam : 0), pairs = F * (F + 1) / 2;
     state = take(sizeof(GbaState));
     poses = take(96 * F);
     X = take(24 * L);
@@ -848,6 +1214,7 @@ struct GbaLayout {
     off = take(4 * (L + 1));
     ofr = take(4 * M);
     has = take(L);
+    camrec = take(camera ? 8 * 16 : 0);
     upload_end = at;
     cand_poses = take(96 * F);
     candX = take(24 * L);
@@ -869,6 +1236,12 @@ struct GbaLayout {
     sysx = take(8 * n);
     trace = take(sizeof(dsopp_hip_geometric_ba_trace) * (max_it > 0 ? max_it : 1));
     flags = take(M > L ? M : L);
+    Jc = take(camera ? 8 * 2 * kCam * M : 0);
+    Wc = take(camera ? 8 * 3 * kCam * M : 0);
+    Hpc = take(camera ? 8 * 6 * kCam * F : 0);
+    Sfc = take(camera ? 8 * 6 * kCam * F : 0);
+    camsum = take(camera ? 8 * 40 : 0);
+    deltac = take(camera ? 8 * kCam : 0);
     bytes = at;
   }
 };
@@ -880,7 +1253,7 @@ bool finiteAll(const double *v, size_t n) {
 }
 
 /** the checks every call shares; positions are checked by the calls that read them */
-void validate(const dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, int min_frames) {
+void validate(const dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, int min_frames, bool own_camera = true) {
   if (!h) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null geometric ba");
   if (!pr) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (pr->num_frames > kMaxFrames) fail(DSOPP_HIP_ERR_CAPACITY, "%d frames: the object takes %d", pr->num_frames, kMaxFrames);
@@ -889,7 +1262,7 @@ void validate(const dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_prob
   if (pr->num_observations < 0 || pr->num_observations > (1 << 26)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "%d observations", pr->num_observations);
   if (pr->width < 9 || pr->height < 9) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a %d x %d image has no region of interest", pr->width, pr->height);
   const double cam[4] = {pr->fx, pr->fy, pr->cx, pr->cy};
-  if (!finiteAll(cam, 4) || pr->fx == 0.0 || pr->fy == 0.0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the camera is not finite or has a zero focal length");
+  if (own_camera && (!finiteAll(cam, 4) || pr->fx == 0.0 || pr->fy == 0.0)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the camera is not finite or has a zero focal length");
   if (!pr->poses || !pr->landmark_offsets) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const int L = pr->num_landmarks, M = pr->num_observations, F = pr->num_frames;
   if ((L > 0 && !pr->positions) || (M > 0 && (!pr->obs_frame || !pr->obs_xy))) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
@@ -919,10 +1292,10 @@ struct Call {
 };
 
 /** grows the block, fills the pinned mirror's upload region and enqueues the upload */
-Call begin(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, int max_it, const uint8_t *has_position) {
+Call begin(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, int max_it, const uint8_t *has_position, bool camera = false) {
   h->sr.use();
   const size_t F = static_cast<size_t>(pr->num_frames), L = static_cast<size_t>(pr->num_landmarks), M = static_cast<size_t>(pr->num_observations);
-  Call c{h, GbaLayout(F, L, M, static_cast<size_t>(max_it > 0 ? max_it : 0)), GbaParams(), nullptr, nullptr, h->sr.stream, F, L, M};
+  Call c{h, GbaLayout(F, L, M, static_cast<size_t>(max_it > 0 ? max_it : 0), camera), GbaParams(), nullptr, nullptr, h->sr.stream, F, L, M};
   const GbaLayout &lay = c.lay;
   if (h->capacity < lay.bytes) {
     size_t cap = h->capacity ? h->capacity : 65536;
@@ -982,6 +1355,17 @@ Call begin(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, 
   p.sysb = reinterpret_cast<double *>(d + lay.sysb);
   p.sysx = reinterpret_cast<double *>(d + lay.sysx);
   p.trace = reinterpret_cast<dsopp_hip_geometric_ba_trace *>(d + lay.trace);
+  p.model = p.fixed = p.npose = p.ncam = 0;
+  for (int &i : p.cidx) i = 0;
+  p.width = static_cast<double>(pr->width);
+  p.height = static_cast<double>(pr->height);
+  p.camrec = reinterpret_cast<double *>(d + lay.camrec);
+  p.Jc = reinterpret_cast<double *>(d + lay.Jc);
+  p.Wc = reinterpret_cast<double *>(d + lay.Wc);
+  p.Hpc = reinterpret_cast<double *>(d + lay.Hpc);
+  p.Sfc = reinterpret_cast<double *>(d + lay.Sfc);
+  p.camsum = reinterpret_cast<double *>(d + lay.camsum);
+  p.deltac = reinterpret_cast<double *>(d + lay.deltac);
   return c;
 }
 
@@ -1003,20 +1387,75 @@ void requireFinitePositions(const dsopp_hip_geometric_ba_problem *pr) {
     fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a landmark position is not finite");
 }
 
-void evaluate(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, double a, double *cost, int32_t *valid_residuals, uint8_t *obs_valid,
-              double *obs_residual, double *obs_weight) {
-  validate(h, pr, 1);
+/** the camera of a *_camera call after its checks: what the device record and the kernels' parameters take */
+struct CameraSetup {
+  int model, fixed, ncam, cidx[kCam];
+  double c[kCam], radius;
+};
+
+CameraSetup checkCamera(const dsopp_hip_geometric_ba_problem *pr, const dsopp_hip_geometric_ba_camera *cam) {
+  if (!cam) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null camera");
+  if (cam->model != DSOPP_HIP_GEOMETRIC_BA_PINHOLE && cam->model != DSOPP_HIP_GEOMETRIC_BA_SIMPLE_RADIAL)
+    fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "unknown camera model %d", cam->model);
+  const int known = DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL | DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER | DSOPP_HIP_GEOMETRIC_BA_FIX_MODEL_SPECIFIC | kFixPoses | kFixLandmarks;
+  if (cam->fixed & ~known) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "unknown fixed bits %d", cam->fixed);
+  const bool radial = cam->model == DSOPP_HIP_GEOMETRIC_BA_SIMPLE_RADIAL;
+  const int count = radial ? 5 : 4;
+  CameraSetup cs{};
+  cs.model = cam->model;
+  cs.fixed = cam->fixed;
+  for (int k = 0; k < count; ++k) cs.c[k] = cam->intrinsics[k];
+  if (!finiteAll(cs.c, static_cast<size_t>(count))) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "an intrinsic is not finite");
+  if (!(cs.c[0] > 0.0) || (!radial && !(cs.c[1] > 0.0))) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "a focal length is not positive");
+  if (radial) {
+    cs.radius = radial::maxValidRadius(static_cast<double>(pr->width), static_cast<double>(pr->height), cs.c[0], cs.c[1], cs.c[2], cs.c[3], cs.c[4]);
+    if (!(cs.radius > 0.0) || !std::isfinite(cs.radius)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the camera's max_valid_radius is %g", cs.radius);
+  }
+  // constantParameterSet: focal, centre, model-specific
+  const int group_pinhole[4] = {DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL, DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL, DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER,
+                                DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER};
+  const int group_radial[5] = {DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL, DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER, DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER,
+                               DSOPP_HIP_GEOMETRIC_BA_FIX_MODEL_SPECIFIC, DSOPP_HIP_GEOMETRIC_BA_FIX_MODEL_SPECIFIC};
+  for (int k = 0; k < count; ++k)
+    if (!(cam->fixed & (radial ? group_radial[k] : group_pinhole[k]))) cs.cidx[cs.ncam++] = k;
+  return cs;
+}
+
+void installCamera(Call &c, const CameraSetup &cs) {
+  GbaParams &p = c.p;
+  p.model = cs.model;
+  p.fixed = cs.fixed;
+  p.npose = (cs.fixed & kFixPoses) ? 0 : 6 * (p.F - 1) - 1;
+  p.ncam = cs.ncam;
+  for (int k = 0; k < kCam; ++k) p.cidx[k] = cs.cidx[k];
+  double *rec = reinterpret_cast<double *>(c.host + c.lay.camrec);
+  for (int half = 0; half < 2; ++half) {
+    for (int k = 0; k < kCam; ++k) rec[8 * half + k] = cs.c[k];
+    rec[8 * half + 5] = cs.radius;
+  }
+}
+
+template <bool CAM>
+void evaluate(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *pr, dsopp_hip_geometric_ba_camera *camera, double a, double *cost,
+              int32_t *valid_residuals, uint8_t *obs_valid, double *obs_residual, double *obs_weight) {
+  validate(h, pr, 1, !CAM);
   requireFinitePositions(pr);
+  CameraSetup cs{};
+  if constexpr (CAM) {
+    cs = checkCamera(pr, camera);
+    camera->max_valid_radius = cs.radius;
+  }
   if (!cost || !valid_residuals) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (!(a > 0.0) || !std::isfinite(a)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the Huber width must be positive and finite");
   *cost = 0.0;
   *valid_residuals = 0;
   if (pr->num_observations == 0) return;
-  Call c = begin(h, pr, 0, nullptr);
+  Call c = begin(h, pr, 0, nullptr, CAM);
   c.p.a = a;
+  if constexpr (CAM) installCamera(c, cs);
   reinterpret_cast<GbaState *>(c.host + c.lay.state)->relin = 1;
   upload(c);
-  gbaLinearise<<<blocksFor(c.L), kBlock, 0, c.st>>>(c.p);
+  gbaLinearise<CAM><<<blocksFor(c.L), kBlock, 0, c.st>>>(c.p);
   HIP_CHECK(hipGetLastError());
   gbaInitialCost<<<1, kBlock, 0, c.st>>>(c.p);
   HIP_CHECK(hipGetLastError());
@@ -1033,10 +1472,21 @@ void evaluate(dsopp_hip_geometric_ba *h, const dsopp_hip_geometric_ba_problem *p
   if (obs_weight) std::memcpy(obs_weight, c.host + c.lay.wgt, 8 * c.M);
 }
 
-void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, const dsopp_hip_geometric_ba_options *opt,
-           dsopp_hip_geometric_ba_result *result, const dsopp_hip_geometric_ba_debug *dbg) {
-  validate(h, pr, 2);
+template <bool CAM>
+void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, dsopp_hip_geometric_ba_camera *camera,
+           const dsopp_hip_geometric_ba_options *opt, dsopp_hip_geometric_ba_result *result, const dsopp_hip_geometric_ba_debug *dbg,
+           const dsopp_hip_geometric_ba_camera_debug *cdbg) {
+  validate(h, pr, 2, !CAM);
   requireFinitePositions(pr);
+  CameraSetup cs{};
+  bool poses_free = true;
+  if constexpr (CAM) {
+    cs = checkCamera(pr, camera);
+    poses_free = !(cs.fixed & kFixPoses);
+    if (!poses_free && (cs.fixed & kFixLandmarks) && cs.ncam == 0)
+      fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "nothing is free: poses, landmarks and every intrinsic are fixed");
+    camera->max_valid_radius = cs.radius;
+  }
   if (!opt || !result) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const double o[6] = {opt->a, opt->lambda_0, opt->function_tolerance, opt->parameter_tolerance, opt->decrease_factor, opt->increase_factor};
   if (!finiteAll(o, 6) || !(opt->a > 0.0) || !(opt->lambda_0 >= 0.0) || !(opt->decrease_factor > 0.0) || !(opt->increase_factor > 0.0))
@@ -1045,17 +1495,18 @@ void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, const 
   if (opt->iteration_group < 0) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "an iteration group of %d", opt->iteration_group);
   const double *t1 = pr->poses + 12 + 9;
   const double norm1 = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
-  if (!(norm1 > 0.0) || !std::isfinite(norm1)) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "frame 1 has no translation: its direction is not defined");
+  if (poses_free && (!(norm1 > 0.0) || !std::isfinite(norm1))) fail(DSOPP_HIP_ERR_INVALID_ARGUMENT, "frame 1 has no translation: its direction is not defined");
   std::memset(result, 0, sizeof(*result));
   result->final_lambda = opt->lambda_0;
-  const int n = 6 * (pr->num_frames - 1) - 1;
+  const int n = (poses_free ? 6 * (pr->num_frames - 1) - 1 : 0) + cs.ncam;
   if (pr->num_observations == 0) {
     // nothing is valid: the driver's loop does not start
     result->reason = DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL;
     return;
   }
-  Call c = begin(h, pr, opt->max_iterations, nullptr);
+  Call c = begin(h, pr, opt->max_iterations, nullptr, CAM);
   GbaParams &p = c.p;
+  if constexpr (CAM) installCamera(c, cs);
   p.a = opt->a;
   p.ftol = opt->function_tolerance;
   p.ptol = opt->parameter_tolerance;
@@ -1066,20 +1517,24 @@ void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, const 
   s->lambda = s->system_lambda = opt->lambda_0;
   s->relin = 1;
   upload(c);
-  gbaLinearise<<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
+  gbaLinearise<CAM><<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
   HIP_CHECK(hipGetLastError());
   gbaInitialCost<<<1, kBlock, 0, c.st>>>(p);
   HIP_CHECK(hipGetLastError());
   const int group = opt->iteration_group > 0 ? opt->iteration_group : kDefaultGroup;
-  const unsigned pairs = static_cast<unsigned>((pr->num_frames - 1) * pr->num_frames / 2);
+  // the reducers: a workgroup per pair of free frames; with a camera block one per free frame and one for the camera behind them
+  const unsigned frame_pairs = static_cast<unsigned>((pr->num_frames - 1) * pr->num_frames / 2);
+  // (no free intrinsic: the camera's sums are not read, and with free poses its reducers are not launched)
+  const unsigned camera_reducers = cs.ncam > 0 ? static_cast<unsigned>(pr->num_frames - 1) + 1u : 0u;
+  const unsigned pairs = !CAM ? frame_pairs : poses_free ? frame_pairs + camera_reducers : 1u;
   for (int launched = 0; launched < opt->max_iterations;) {
     const int now = std::min(group, opt->max_iterations - launched);
     for (int k = 0; k < now; ++k) {
-      gbaLinearise<<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
-      gbaReduce<<<pairs, kBlock, 0, c.st>>>(p);
-      gbaSolve<<<1, kBlock, 0, c.st>>>(p);
-      gbaUpdate<<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
-      gbaDecide<<<1, kBlock, 0, c.st>>>(p);
+      gbaLinearise<CAM><<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
+      gbaReduce<CAM><<<pairs, kBlock, 0, c.st>>>(p);
+      gbaSolve<CAM><<<1, kBlock, 0, c.st>>>(p);
+      gbaUpdate<CAM><<<blocksFor(c.L), kBlock, 0, c.st>>>(p);
+      gbaDecide<CAM><<<1, kBlock, 0, c.st>>>(p);
     }
     HIP_CHECK(hipGetLastError());
     launched += now;
@@ -1102,6 +1557,10 @@ void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, const 
     if (dbg->candidate_poses) fetch(c, lay.cand_poses, 96 * c.F);
     if (dbg->candidate_positions) fetch(c, lay.candX, 24 * c.L);
     if (dbg->trace && opt->max_iterations > 0) fetch(c, lay.trace, sizeof(dsopp_hip_geometric_ba_trace) * static_cast<size_t>(opt->max_iterations));
+  }
+  if constexpr (CAM) {
+    fetch(c, lay.camrec, 8 * 16);
+    if (cdbg && cdbg->obs_camera_jacobian) fetch(c, lay.Jc, 8 * 2 * kCam * c.M);
   }
   wait(c);
   if (s->it < 0 || s->it > opt->max_iterations) fail(DSOPP_HIP_ERR_HIP, "the device returned %d iterations of %d", s->it, opt->max_iterations);
@@ -1129,6 +1588,17 @@ void solve(dsopp_hip_geometric_ba *h, dsopp_hip_geometric_ba_problem *pr, const 
     if (dbg->candidate_poses) std::memcpy(dbg->candidate_poses, c.host + (ran ? lay.cand_poses : lay.poses), 96 * c.F);
     if (dbg->candidate_positions && c.L) std::memcpy(dbg->candidate_positions, c.host + (ran ? lay.candX : lay.X), 24 * c.L);
     if (dbg->trace && s->it > 0) std::memcpy(dbg->trace, c.host + lay.trace, sizeof(dsopp_hip_geometric_ba_trace) * static_cast<size_t>(s->it));
+  }
+  if constexpr (CAM) {
+    const double *rec = reinterpret_cast<const double *>(c.host + lay.camrec);
+    std::memcpy(camera->intrinsics, rec, 8 * static_cast<size_t>(cs.model == DSOPP_HIP_GEOMETRIC_BA_SIMPLE_RADIAL ? 5 : 4));
+    camera->max_valid_radius = rec[5];
+    if (cdbg) {
+      const bool ran = s->it > 0;  // without an iteration the candidate is the state
+      if (cdbg->obs_camera_jacobian) std::memcpy(cdbg->obs_camera_jacobian, c.host + lay.Jc, 8 * 2 * kCam * c.M);
+      if (cdbg->candidate_intrinsics) std::memcpy(cdbg->candidate_intrinsics, rec + (ran ? 8 : 0), 8 * kCam);
+      if (cdbg->candidate_max_valid_radius) *cdbg->candidate_max_valid_radius = rec[(ran ? 8 : 0) + 5];
+    }
   }
 }
 
@@ -1210,12 +1680,24 @@ void dsopp_hip_geometric_ba_destroy(dsopp_hip_geometric_ba *b) {
 
 int dsopp_hip_geometric_ba_evaluate(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem, double a, double *cost,
                                     int32_t *valid_residuals, uint8_t *obs_valid, double *obs_residual, double *obs_weight) {
-  return guarded([&] { evaluate(b, problem, a, cost, valid_residuals, obs_valid, obs_residual, obs_weight); });
+  return guarded([&] { evaluate<false>(b, problem, nullptr, a, cost, valid_residuals, obs_valid, obs_residual, obs_weight); });
+}
+
+int dsopp_hip_geometric_ba_evaluate_camera(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem, dsopp_hip_geometric_ba_camera *camera,
+                                           double a, double *cost, int32_t *valid_residuals, uint8_t *obs_valid, double *obs_residual,
+                                           double *obs_weight) {
+  return guarded([&] { evaluate<true>(b, problem, camera, a, cost, valid_residuals, obs_valid, obs_residual, obs_weight); });
 }
 
 int dsopp_hip_geometric_ba_solve(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const dsopp_hip_geometric_ba_options *options,
                                  dsopp_hip_geometric_ba_result *result, const dsopp_hip_geometric_ba_debug *debug) {
-  return guarded([&] { solve(b, problem, options, result, debug); });
+  return guarded([&] { solve<false>(b, problem, nullptr, options, result, debug, nullptr); });
+}
+
+int dsopp_hip_geometric_ba_solve_camera(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, dsopp_hip_geometric_ba_camera *camera,
+                                        const dsopp_hip_geometric_ba_options *options, dsopp_hip_geometric_ba_result *result,
+                                        const dsopp_hip_geometric_ba_camera_debug *debug) {
+  return guarded([&] { solve<true>(b, problem, camera, options, result, debug ? &debug->base : nullptr, debug); });
 }
 
 int dsopp_hip_geometric_ba_triangulate(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const uint8_t *has_position,

@@ -1658,30 +1658,39 @@ class HipRefineTrack {
   dsopp_hip_geometric_ba_result optimizeTransformations(std::vector<RefineLandmark> &landmarks, std::deque<RefineFrame> &frames, const PinholeModel &model,
                                                         double reprojection_threshold = 1.5, size_t number_of_frames_to_optimize = 10,
                                                         const dsopp_hip_geometric_ba_options *options = nullptr) {
-    const size_t number_of_frames = std::min(frames.size(), number_of_frames_to_optimize), start = frames.size() - number_of_frames;
-    std::vector<size_t> chosen, local;
-    for (size_t l = 0; l < landmarks.size(); ++l) {
-      bool exists_in_window = false;
-      for (size_t i = start; i < frames.size(); ++i)
-        if (landmarks[l].has_position && landmarks[l].projection(frames[i].frame_id)) exists_in_window = true;
-      if (exists_in_window) chosen.push_back(l);
+    return optimize(landmarks, frames, model, nullptr, reprojection_threshold, number_of_frames_to_optimize, options);
+  }
+
+  /** ParameterParameterization (ceres_geometric_bundle_adjustment.hpp:16-27) with the reference's defaults */
+  struct ParameterParameterization {
+    bool fix_focal = true, fix_center = true, fix_model_specific = true, fix_poses = false, fix_landmarks = false;
+    int32_t bits() const {
+      return (fix_focal ? DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL : 0) | (fix_center ? DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER : 0) |
+             (fix_model_specific ? DSOPP_HIP_GEOMETRIC_BA_FIX_MODEL_SPECIFIC : 0) | (fix_poses ? DSOPP_HIP_GEOMETRIC_BA_FIX_POSES : 0) |
+             (fix_landmarks ? DSOPP_HIP_GEOMETRIC_BA_FIX_LANDMARKS : 0);
     }
-    for (size_t i = start; i < frames.size(); ++i)
-      if (frames[i].initialized) local.push_back(i);
-    dsopp_hip_geometric_ba_result result{};
-    if (local.size() < 2) return result;
-    Problem p = gather(landmarks, frames, local, chosen, model, true);
-    dsopp_hip_geometric_ba_options o;
-    if (options) {
-      o = *options;
-    } else {
-      dsopp_hip_geometric_ba_default_options(&o);
-      o.a = reprojection_threshold;
-    }
-    check(dsopp_hip_geometric_ba_solve(b_, &p.c, &o, &result, nullptr));
-    for (size_t f = 0; f < local.size(); ++f) frames[local[f]].t_world_agent = inverse(p.poses.data() + 12 * f);
-    for (size_t k = 0; k < chosen.size(); ++k)
-      for (size_t r = 0; r < 3; ++r) landmarks[chosen[k]].position[r] = p.positions[3 * k + r];
+  };
+  /** the camera model of the OPTIMIZE_CAMERA form: PinholeCamera (fx, fy, cx, cy) or SimpleRadialCamera (f, cx, cy, k1, k2) */
+  enum class CameraModel { kPinhole = DSOPP_HIP_GEOMETRIC_BA_PINHOLE, kSimpleRadial = DSOPP_HIP_GEOMETRIC_BA_SIMPLE_RADIAL };
+
+  /** optimizeTransformations<Model, true>(landmarks, camera_intrinsics, image_size, frames, reprojection_threshold,
+   *  number_of_frames_to_optimize, parameterization): as above with the intrinsics as a third parameter block, written back as
+   *  refine_track.cpp:80-82 does.  `max_valid_radius` (NULL-able) receives the simple-radial constant of the intrinsics left. */
+  dsopp_hip_geometric_ba_result optimizeTransformations(std::vector<RefineLandmark> &landmarks, std::vector<double> &camera_intrinsics,
+                                                        CameraModel camera_model, std::deque<RefineFrame> &frames,
+                                                        const ParameterParameterization &parameterization, double reprojection_threshold = 1.5,
+                                                        size_t number_of_frames_to_optimize = 10,
+                                                        const dsopp_hip_geometric_ba_options *options = nullptr, double *max_valid_radius = nullptr) {
+    const size_t count = camera_model == CameraModel::kPinhole ? 4 : 5;
+    if (camera_intrinsics.size() != count) throw SolverError(DSOPP_HIP_ERR_INVALID_ARGUMENT, "the camera model takes other intrinsics");
+    dsopp_hip_geometric_ba_camera camera{};
+    camera.model = static_cast<int32_t>(camera_model);
+    camera.fixed = parameterization.bits();
+    for (size_t k = 0; k < count; ++k) camera.intrinsics[k] = camera_intrinsics[k];
+    const dsopp_hip_geometric_ba_result result =
+        optimize(landmarks, frames, PinholeModel{}, &camera, reprojection_threshold, number_of_frames_to_optimize, options);
+    for (size_t k = 0; k < count; ++k) camera_intrinsics[k] = camera.intrinsics[k];
+    if (max_valid_radius) *max_valid_radius = camera.max_valid_radius;
     return result;
   }
 
@@ -1753,6 +1762,37 @@ class HipRefineTrack {
                                          static_cast<int32_t>(chosen.size()), static_cast<int32_t>(p.obs_frame.size()), 0, p.poses.data(),
                                          p.positions.data(), p.offsets.data(), p.obs_frame.data(), p.obs_xy.data()};
     return p;
+  }
+  /** the body both forms of optimizeTransformations share: the window, exists_in_window, the local frames, the solve — with `camera` as
+   *  a parameter block when one is given (the problem's own camera is then not read) — and the write-back of poses and positions */
+  dsopp_hip_geometric_ba_result optimize(std::vector<RefineLandmark> &landmarks, std::deque<RefineFrame> &frames, const PinholeModel &model,
+                                         dsopp_hip_geometric_ba_camera *camera, double reprojection_threshold, size_t number_of_frames_to_optimize,
+                                         const dsopp_hip_geometric_ba_options *options) {
+    const size_t number_of_frames = std::min(frames.size(), number_of_frames_to_optimize), start = frames.size() - number_of_frames;
+    std::vector<size_t> chosen, local;
+    for (size_t l = 0; l < landmarks.size(); ++l) {
+      bool exists_in_window = false;
+      for (size_t i = start; i < frames.size(); ++i)
+        if (landmarks[l].has_position && landmarks[l].projection(frames[i].frame_id)) exists_in_window = true;
+      if (exists_in_window) chosen.push_back(l);
+    }
+    for (size_t i = start; i < frames.size(); ++i)
+      if (frames[i].initialized) local.push_back(i);
+    dsopp_hip_geometric_ba_result result{};
+    if (local.size() < 2) return result;
+    Problem p = gather(landmarks, frames, local, chosen, model, true);
+    dsopp_hip_geometric_ba_options o;
+    if (options) {
+      o = *options;
+    } else {
+      dsopp_hip_geometric_ba_default_options(&o);
+      o.a = reprojection_threshold;
+    }
+    check(camera ? dsopp_hip_geometric_ba_solve_camera(b_, &p.c, camera, &o, &result, nullptr) : dsopp_hip_geometric_ba_solve(b_, &p.c, &o, &result, nullptr));
+    for (size_t f = 0; f < local.size(); ++f) frames[local[f]].t_world_agent = inverse(p.poses.data() + 12 * f);
+    for (size_t k = 0; k < chosen.size(); ++k)
+      for (size_t r = 0; r < 3; ++r) landmarks[chosen[k]].position[r] = p.positions[3 * k + r];
+    return result;
   }
   dsopp_hip_geometric_ba *b_ = nullptr;
   int width_, height_;

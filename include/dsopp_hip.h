@@ -534,8 +534,11 @@ int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, 
  * them, with the triangulation before it and the pruning after it (replaces, per bootstrap frame once the initialiser has succeeded —
  * src/feature_based_slam/tracker/src/monocular_tracker.cpp:54-68 —, triangulatePoints — triangulate_points.cpp:47-71, triangulation.hpp:52-64 —,
  * optimizeTransformations — refine_track.cpp:16-83, which runs Ceres SPARSE_SCHUR with a Huber loss through
- * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  Not built: the
- * SimpleRadialCamera instantiation, intrinsics optimisation, fix_poses and fix_landmarks (estimateSE3PnP is dsopp_hip_pnp_ransac_* below;
+ * ceres_geometric_bundle_adjustment_solver.cpp:33-108 — and removeOutliers — remove_outliers.cpp:15-47).  The OPTIMIZE_CAMERA form of
+ * optimizeTransformations — the intrinsics as a third parameter block, PinholeCamera or SimpleRadialCamera, with
+ * ParameterParameterization's fix_focal, fix_center, fix_model_specific, fix_poses and fix_landmarks — is the pair
+ * dsopp_hip_geometric_ba_evaluate_camera / _solve_camera, stated under "The camera block" below.  Not built: triangulation and pruning
+ * with a simple-radial camera (they need unproject), the autocalibration initialiser (estimateSE3PnP is dsopp_hip_pnp_ransac_* below;
  * the essential-matrix RANSAC and the two-view triangulatePoints that only initializePoses calls are dsopp_hip_two_view_ransac_* below it).
  *
  * The arithmetic is fixed here; tests/geometric_ba_model.py is its NumPy form.  Everything is binary64.
@@ -579,6 +582,35 @@ int dsopp_hip_rotation_ransac_estimate(dsopp_hip_rotation_ransac *r, double fx, 
  *     eigenvector of A's smallest eigenvalue divided by its last entry.  Any backward-stable route serves (the device: cyclic Jacobi);
  *     the result is unpinned where the two smallest eigenvalues nearly coincide.
  *   Pruning: observation (f, l) is flagged iff it is not valid or sqrt(|obs - q|^2) > outlier_threshold (0.5, strict).
+ *   The camera block (evaluate_camera, solve_camera; tests/geometric_ba_camera_model.py is its NumPy form).  The camera is the call's
+ *     dsopp_hip_geometric_ba_camera; problem->fx .. cy are ignored, width and height bound the ROI as above.
+ *     Pinhole, intrinsics (fx, fy, cx, cy): residual and validity as above; with u = p_x / p_z, v = p_y / p_z,
+ *     dr/d(fx, fy, cx, cy) = -[[u, 0, 1, 0], [0, v, 0, 1]].
+ *     Simple radial, intrinsics (f, cx, cy, k1, k2) (simple_radial.hpp:133-160, the projection without a Jacobian, which the cost functor
+ *     calls): rho2 = u u + v v, d = (1 + k1 rho2) + (k2 rho2) rho2, q = f (d (u, v)) + (cx, cy); valid iff sqrt(rho2) <= max_valid_radius
+ *     and roi(q).  There is no test on p_z (the reference has none): p_z = 0 gives a q that is not finite and fails roi.
+ *     dq/df = d (u, v), dq/d(cx, cy) = I, dq/dk1 = (f rho2) (u, v), dq/dk2 = (f (rho2 rho2)) (u, v); G = dq / dp as simple_radial.hpp:190-199
+ *     writes it: c = (2 k1 + 4 k2 rho2) / p_z / p_z, G_00 = f (p_x p_x c + d) / p_z, G_01 = G_10 = f p_x p_y c / p_z,
+ *     G_11 = f (p_y p_y c + d) / p_z, G_i2 = f p_i / p_z / p_z (-3 k1 rho2 - 5 k2 rho2 rho2 - 1).  max_valid_radius is the constructor's
+ *     constant (simple_radial.hpp:47-77, the routine stated with dsopp_hip_camera_model_to_pinhole above, dsopp_amd/csrc/
+ *     simple_radial_radius.hpp) of the CURRENT intrinsics and the problem's width and height — Ceres rebuilds the model at every
+ *     evaluation —; it enters the validity branch only, no derivative flows through it.
+ *     Free intrinsics (constantParameterSet): pinhole focal = {fx, fy}, centre = {cx, cy}, FIX_MODEL_SPECIFIC ignored; simple radial
+ *     focal = {f}, centre = {cx, cy}, model-specific = {k1, k2}.  The free ones, in parameter order, follow the pose unknowns in the
+ *     reduced system: n = (pose unknowns) + Dc <= 94.  With FIX_POSES there are no pose unknowns (frame 1's basis and |t_1| are unused,
+ *     |t_1| = 0 is allowed); the increment is additive, c <- c + delta_c.
+ *     System: H_cc = sum w J_c^T J_c, b_c = sum w J_c^T r, H_pc = sum w J_p^T J_c per frame, W_lc = sum_o w J_x^T J_c over all of a
+ *     landmark's observations; damping lambda diag(H_cc) like everywhere else.  The Schur complement takes the camera as one more block
+ *     row and column: Y_c,l = L_l^-1 W_lc, S_fc = sum_l Y_f^T Y_c, S_cc = sum_l Y_c^T Y_c, the right-hand side alike;
+ *     delta_l = -(L_l L_l^T)^-1 (b_l + sum_f W_lf^T delta_f + W_lc delta_c).  With FIX_LANDMARKS there is no elimination: the system is
+ *     H + lambda D over poses and camera and delta_l = 0.  A pivot that is <= 0 or not finite — now also a camera diagonal that carries no
+ *     information — fails the step as above.
+ *     Candidate: the step also fails when the candidate camera has a focal length <= 0, an intrinsic that is not finite or, simple radial,
+ *     a max_valid_radius that is not finite or <= 0 (the candidate poses and intrinsics are still handed out as computed).
+ *     Control: the driver above; the step norm gains |delta_c|^2, the state norm sum c_i^2 over the free intrinsics; fixed poses and fixed
+ *     landmarks contribute to neither norm.
+ *     Pinning: a pinhole with FIX_FOCAL | FIX_CENTER | FIX_MODEL_SPECIFIC and free poses and landmarks returns the bytes of
+ *     dsopp_hip_geometric_ba_solve given the same intrinsics: poses, positions, result and trace.
  * There is no CPU fallback: without a device create fails with DSOPP_HIP_ERR_HIP.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dsopp_hip_geometric_ba dsopp_hip_geometric_ba;
@@ -647,6 +679,38 @@ int dsopp_hip_geometric_ba_evaluate(dsopp_hip_geometric_ba *b, const dsopp_hip_g
  * a factor <= 0, max_iterations < 0, iteration_group < 0.  M = 0 returns at once with DSOPP_HIP_GEOMETRIC_BA_NO_VALID_RESIDUAL. */
 int dsopp_hip_geometric_ba_solve(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const dsopp_hip_geometric_ba_options *options,
                                  dsopp_hip_geometric_ba_result *result, const dsopp_hip_geometric_ba_debug *debug);
+/* The camera block: evaluate and solve with the camera as a parameter block of its own (optimizeTransformations<Model, OPTIMIZE_CAMERA>). */
+enum { DSOPP_HIP_GEOMETRIC_BA_PINHOLE = 0, DSOPP_HIP_GEOMETRIC_BA_SIMPLE_RADIAL = 1 };
+enum {
+  DSOPP_HIP_GEOMETRIC_BA_FIX_FOCAL = 1,
+  DSOPP_HIP_GEOMETRIC_BA_FIX_CENTER = 2,
+  DSOPP_HIP_GEOMETRIC_BA_FIX_MODEL_SPECIFIC = 4,
+  DSOPP_HIP_GEOMETRIC_BA_FIX_POSES = 8,
+  DSOPP_HIP_GEOMETRIC_BA_FIX_LANDMARKS = 16
+};
+typedef struct dsopp_hip_geometric_ba_camera {
+  int32_t model, fixed;    /* fixed: the DSOPP_HIP_GEOMETRIC_BA_FIX_* bits (ParameterParameterization) */
+  double intrinsics[5];    /* pinhole fx fy cx cy (the fifth is ignored and kept) | simple radial f cx cy k1 k2; solve updates them in place */
+  double max_valid_radius; /* out: simple radial, of the intrinsics the call leaves; 0 for a pinhole */
+} dsopp_hip_geometric_ba_camera;
+/* The debug record of solve_camera: base as above with reduced_H, reduced_b and pose_step at n = (pose unknowns: 6 (F - 1) - 1, or 0 with
+ * FIX_POSES) + (free intrinsics), the camera's rows last; obs_camera_jacobian (M x 2 x 5: dr/dc of the last linearisation over all five
+ * parameter slots, fixed ones included, a pinhole's fifth zero, zero where not valid); candidate_intrinsics (5) and
+ * candidate_max_valid_radius (1) of the last iteration's candidate. */
+typedef struct dsopp_hip_geometric_ba_camera_debug {
+  dsopp_hip_geometric_ba_debug base;
+  double *obs_camera_jacobian, *candidate_intrinsics, *candidate_max_valid_radius;
+} dsopp_hip_geometric_ba_camera_debug;
+/* Both calls are also invalid with an unknown model or fixed bit, an intrinsic that is not finite, a focal length <= 0, or a simple-radial
+ * camera whose max_valid_radius is not finite or not positive.  evaluate_camera: as evaluate; writes camera->max_valid_radius. */
+int dsopp_hip_geometric_ba_evaluate_camera(dsopp_hip_geometric_ba *b, const dsopp_hip_geometric_ba_problem *problem,
+                                           dsopp_hip_geometric_ba_camera *camera, double a, double *cost, int32_t *valid_residuals,
+                                           uint8_t *obs_valid, double *obs_residual, double *obs_weight);
+/* As solve; the intrinsics are updated in place with poses and positions.  Also invalid: nothing free (FIX_POSES, FIX_LANDMARKS and every
+ * intrinsic fixed).  |t_1| = 0 is invalid only when the poses are free.  Two frames are required with fixed poses too. */
+int dsopp_hip_geometric_ba_solve_camera(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, dsopp_hip_geometric_ba_camera *camera,
+                                        const dsopp_hip_geometric_ba_options *options, dsopp_hip_geometric_ba_result *result,
+                                        const dsopp_hip_geometric_ba_camera_debug *debug);
 /* has_position, triangulated: num_landmarks bytes.  Writes problem->positions of the landmarks it triangulated (triangulated[l] = 1) and
  * leaves the others; positions are not read.  Also invalid: min_number_of_projections < 2 (the reference's CHECK_GE).  One wait. */
 int dsopp_hip_geometric_ba_triangulate(dsopp_hip_geometric_ba *b, dsopp_hip_geometric_ba_problem *problem, const uint8_t *has_position,
